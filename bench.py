@@ -11,8 +11,11 @@ U(-1,1) actions already resident in HBM.  For N>1 each rank owns 8192 envs (weak
 collective inside the physics) and every step ends with the RCCL gather of (obs, reward, discount, step_type)
 to rank 0 that a central learner needs.
 
-One JSON line on rank 0; `roofline` is measured live with HIP events on the launch stream; `cpu_baseline` times
-the float64 CPU oracle (oracle/, the checker - never the product) on the host cores, at N=1 only.
+One JSON line on rank 0.  A plain run sets up, warms up, times the K steps and reports them (`value`, `ms_per_step`);
+`--dump-outputs DIR` also writes what the last timed step returned (observation, reward, discount, step_type) as
+DIR/<name>.npy.  `--full` adds the measurements that take runs of their own: `roofline` (HIP events on the launch
+stream), `async_groups`, `capacity`, and `cpu_baseline`, which times the float64 CPU oracle (oracle/, the checker -
+never the product) on the host cores, at N=1 only.
 """
 import argparse
 import json
@@ -28,6 +31,7 @@ ALGO_BYTES_PER_ENV_STEP = 1408  # reads 624 + writes 784
 BALL_ENVS_PER_GPU = 4096        # BASELINE.json configs[2]: walk_on_ball, contacts + solver, batch 4096 on one MI355X
 BALL_ALGO_BYTES_PER_ENV_STEP = 4412  # reads 1740 + writes 2672
 HBM_PEAK_GBS = 8000.0           # MI355X_MICROARCH.md: 8.0 TB/s spec
+DUMP_LIMIT_BYTES = 64 << 20     # --dump-outputs: larger outputs are written as a fixed, seeded sample of rows
 
 
 def _cpu_worker(args):
@@ -105,6 +109,25 @@ def cpu_baseline(target_seconds=20.0, workload="flight_imitation"):
                       f"(single-core {per_core:.0f} env-steps/s; pool wall {time.perf_counter() - t0:.1f}s)"}
 
 
+def dump_outputs(outdir, arrays):
+    """Writes {name: [rows, ...] array} as outdir/<name>.npy in float32 (integer step types convert exactly).  Above
+    DUMP_LIMIT_BYTES in all, every array keeps the same fixed, seeded sample of rows (sorted), so that two builds compare
+    row for row."""
+    import numpy as np
+
+    os.makedirs(outdir, exist_ok=True)
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float32) for k, v in arrays.items()}
+    rows = len(next(iter(arrays.values())))
+    nbytes = sum(a.nbytes for a in arrays.values())
+    if nbytes > DUMP_LIMIT_BYTES:
+        keep = max(1, int(rows * DUMP_LIMIT_BYTES // nbytes))
+        idx = np.sort(np.random.RandomState(0).choice(rows, keep, replace=False))
+        arrays = {k: a[idx] for k, a in arrays.items()}
+        np.save(os.path.join(outdir, "sample_rows.npy"), idx.astype(np.float64))
+    for k, a in arrays.items():
+        np.save(os.path.join(outdir, k + ".npy"), a)
+
+
 class _FakeEnv:
     """Stand-in with the BatchedFlyEnv surface on CPU tensors: lets the tests rehearse the multi-process control flow
     (sharding, double-buffered gather, barriers, max-over-ranks timing) with gloo.  Never used for a reported number."""
@@ -137,14 +160,57 @@ class _FakeEnv:
         return 1.0
 
 
+def roofline(ball, B, world, value, k_ms, k_ms_region, fake):
+    """--full: the dominant kernel's achieved HBM bandwidth against peak, with the committed PMC traffic and FLOP counts."""
+    # HBM traffic of the dominant kernel from the committed rocprofv3 PMC passes of this same command (separate
+    # FETCH_SIZE / WRITE_SIZE runs; KiB units; read side doubled per the gfx950 note in MI355X_MICROARCH.md - an
+    # upper bound here, since these are 4-byte-per-lane reads, not the wide streams the x2 was calibrated on)
+    traffic, traffic_src = None, None
+    pj = os.path.join(ROOT, "profiles", "r03_pmc_ball_kernel.json" if ball else "r03_pmc_flight_kernel.json")
+    # (counters of an earlier round's kernel are not this kernel's: without the file, traffic is null)
+    valu_frac = None
+    flop = None
+    if os.path.exists(pj) and B == (BALL_ENVS_PER_GPU if ball else ENVS_PER_GPU) and not fake and (not ball or BALL_AMP == 0.2):
+        with open(pj) as f:
+            pm = json.load(f)
+        if "FETCH_SIZE" in pm and "WRITE_SIZE" in pm:
+            traffic = int((2 * pm["FETCH_SIZE"]["median"] + pm["WRITE_SIZE"]["median"]) * 1024)
+            traffic_src = "profiles/" + os.path.basename(pj) + " (2*FETCH_SIZE + WRITE_SIZE, per launch)"
+        if "SQ_INSTS_VALU" in pm and "GRBM_GUI_ACTIVE" in pm:
+            # secondary roofline: VALU issue.  A wave64 VALU instruction occupies its SIMD-32 for 2 cycles (MI355X_MICROARCH.md);
+            # kernel cycles = GRBM_GUI_ACTIVE / 8 XCDs; 1024 SIMDs.  From the committed PMC passes of this same command.
+            valu_frac = round(pm["SQ_INSTS_VALU"]["median"] * 2.0 / (pm["GRBM_GUI_ACTIVE"]["median"] / 8.0 * 1024.0), 4)
+    fj = os.path.join(ROOT, "profiles", "r02_oracle_flop_count.json")
+    if os.path.exists(fj) and not fake:
+        with open(fj) as f:
+            fc = json.load(f)["walk_on_ball" if ball else "flight_imitation"]
+        per = fc["total_without_constraint_solve"] if ball else fc["total"]
+    if os.path.exists(fj) and not fake:
+        flop = {"flop_per_env_step": round(per), "achieved_tflops": round(value / world * per / 1e12, 3), "peak_fp32_tflops": 157.3,
+                "frac": round(value / world * per / 157.3e12, 5),
+                "source": "profiles/r02_oracle_flop_count.json (instrumented float64 oracle, tools/count_flops.py" +
+                          ("; smooth dynamics only - the oracle's dense constraint solver is not the kernel's algorithm)" if ball else "; counted before the fly's own contacts existed: collision and contact rows excluded)")}
+    algo = BALL_ALGO_BYTES_PER_ENV_STEP if ball else ALGO_BYTES_PER_ENV_STEP
+    achieved = algo * B / (k_ms * 1e-3) / 1e9
+    return {"bound": "hbm", "achieved": round(achieved, 4), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+            "frac": round(achieved / HBM_PEAK_GBS, 8), "traffic": traffic, "traffic_source": traffic_src,
+            "kernel": "ball_step_kernel" if ball else "flight_step_kernel", "kernel_ms": round(k_ms, 4), "timed_region_ms_per_launch_incl_order_kernel": round(k_ms_region, 4),
+            "algorithmic_bytes_per_launch": algo * B, "valu_frac": valu_frac, "flop": flop,
+            "note": "fused wave-per-env step keeps state on chip; VALU/LDS-latency bound, not HBM bound (DESIGN.md)"}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=300)
     ap.add_argument("--warmup", type=int, default=30)
     ap.add_argument("--envs-per-gpu", type=int, default=None)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-async-groups", action="store_true", help="skip the extra measurement of the same envs as two asynchronous groups")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure roofline, async_groups, capacity and cpu_baseline (runs of their own); a plain run times the steps only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (observation, reward, discount, step_type) as DIR/<name>.npy, float32")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip cpu_baseline")
+    ap.add_argument("--no-async-groups", action="store_true", help="with --full: skip the extra measurement of the same envs as two asynchronous groups")
     ap.add_argument("--action-amplitude", type=float, default=0.2,
                     help="walk_on_ball: raw actions U(-a, a)^59; 0.2 = BASELINE configs[2] (task_utils.py:13-24), 1.0 = every actuator saturating")
     ap.add_argument("--rehearse-gather", action="store_true",
@@ -172,7 +238,7 @@ def main():
     multi = world > 1 or os.environ.get("FLYBODY_BENCH_FORCE_MULTI") == "1"
     forced = multi and world == 1
     cpu = None
-    if rank == 0 and not multi and not args.no_cpu_baseline:
+    if rank == 0 and not multi and args.full and not args.no_cpu_baseline:
         cpu = cpu_baseline(workload=args.workload)  # before any GPU initialisation (uses fork)
 
     import torch
@@ -275,13 +341,14 @@ def main():
     # HIP events on the launch stream (the env launches on torch's current stream) bracket the same K launches the wall
     # clock times: the step kernel is the only thing queued on that stream, back to back, so elapsed / K is its mean duration
     ev0 = ev1 = None
-    if not fake:
+    if args.full and not fake:
         ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     t0 = time.perf_counter()
     if ev0 is not None:
         ev0.record()
+    ts = None
     for k in range(args.steps):
-        one_step(k)
+        ts = one_step(k)
     if ev1 is not None:
         ev1.record()
     fence()
@@ -290,6 +357,18 @@ def main():
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+
+    if args.dump_outputs and rank == 0 and ts is not None:
+        # what the caller of the timed path receives from its last step: N = 1 the env's TimeStep, N > 1 rank 0's gathered
+        # [N * B, obs_dim + 3] buffer (reward, discount, step_type in the last three columns; fence() has waited on it)
+        if multi:
+            packed = torch.cat(gathers[(args.steps - 1) & 1].out).cpu().numpy()
+            od = env.spec.obs_dim
+            out_arrays = {"observation": packed[:, :od], "reward": packed[:, od], "discount": packed[:, od + 1], "step_type": packed[:, od + 2]}
+        else:
+            out_arrays = {"observation": env.flat_observation.cpu().numpy(), "reward": ts.reward.cpu().numpy(),
+                          "discount": ts.discount.cpu().numpy(), "step_type": ts.step_type.cpu().numpy()}
+        dump_outputs(args.dump_outputs, out_arrays)
 
     rehearsal = None
     if args.rehearse_gather and not multi and not fake:
@@ -312,17 +391,19 @@ def main():
     # kernel_ms = HIP events immediately around each launch of the step kernel alone (ffe_time_kernel: the duration rocprofv3's
     # kernel trace reports for it); the timed region's own events also span the 6-12 us launch-order kernel that follows every step
     # (one launch per call, cycling through the same action pool as the timed region: same workload)
-    nk = min(args.steps, 100)
-    kacts = [acts[k % npool] for k in range(nk)] if not multi else [scatters[0].local] * nk  # (N > 1: the block last received)
-    k_ms = (sum(env.time_kernel(kacts[k], 1) for k in range(nk)) / nk) if hasattr(env, "time_kernel") else env.time_steps(kacts[0], nk)
-    sync()
-    k_ms_region = ev0.elapsed_time(ev1) / args.steps if ev0 is not None else k_ms
+    k_ms = k_ms_region = None
+    if args.full:
+        nk = min(args.steps, 100)
+        kacts = [acts[k % npool] for k in range(nk)] if not multi else [scatters[0].local] * nk  # (N > 1: the block last received)
+        k_ms = (sum(env.time_kernel(kacts[k], 1) for k in range(nk)) / nk) if hasattr(env, "time_kernel") else env.time_steps(kacts[0], nk)
+        sync()
+        k_ms_region = ev0.elapsed_time(ev1) / args.steps if ev0 is not None else k_ms
 
     # What an asynchronous consumer gets from the same envs on this GPU (reported beside the headline, never as `value`): the batch as two
     # groups of B / 2 envs, each stepped on its own HIP stream, ordered only against its own previous step - the reference's actors are
     # separate processes that never wait for each other.  One group's drain overlaps the other's start.
     async_groups = None
-    if not multi and not fake and not args.no_async_groups and B % 2 == 0:
+    if args.full and not multi and not fake and not args.no_async_groups and B % 2 == 0:
         from flybody_amd.groups import EnvGroups
 
         fence()
@@ -348,38 +429,8 @@ def main():
 
 
     if rank == 0:
-        # HBM traffic of the dominant kernel from the committed rocprofv3 PMC passes of this same command (separate
-        # FETCH_SIZE / WRITE_SIZE runs; KiB units; read side doubled per the gfx950 note in MI355X_MICROARCH.md - an
-        # upper bound here, since these are 4-byte-per-lane reads, not the wide streams the x2 was calibrated on)
-        traffic, traffic_src = None, None
-        pj = os.path.join(ROOT, "profiles", "r03_pmc_ball_kernel.json" if ball else "r03_pmc_flight_kernel.json")
-        # (counters of an earlier round's kernel are not this kernel's: without the file, traffic is null)
-        valu_frac = None
-        flop = None
-        if os.path.exists(pj) and B == (BALL_ENVS_PER_GPU if ball else ENVS_PER_GPU) and not fake and (not ball or BALL_AMP == 0.2):
-            with open(pj) as f:
-                pm = json.load(f)
-            if "FETCH_SIZE" in pm and "WRITE_SIZE" in pm:
-                traffic = int((2 * pm["FETCH_SIZE"]["median"] + pm["WRITE_SIZE"]["median"]) * 1024)
-                traffic_src = "profiles/" + os.path.basename(pj) + " (2*FETCH_SIZE + WRITE_SIZE, per launch)"
-            if "SQ_INSTS_VALU" in pm and "GRBM_GUI_ACTIVE" in pm:
-                # secondary roofline: VALU issue.  A wave64 VALU instruction occupies its SIMD-32 for 2 cycles (MI355X_MICROARCH.md);
-                # kernel cycles = GRBM_GUI_ACTIVE / 8 XCDs; 1024 SIMDs.  From the committed PMC passes of this same command.
-                valu_frac = round(pm["SQ_INSTS_VALU"]["median"] * 2.0 / (pm["GRBM_GUI_ACTIVE"]["median"] / 8.0 * 1024.0), 4)
-        fj = os.path.join(ROOT, "profiles", "r02_oracle_flop_count.json")
-        if os.path.exists(fj) and not fake:
-            with open(fj) as f:
-                fc = json.load(f)["walk_on_ball" if ball else "flight_imitation"]
-            per = fc["total_without_constraint_solve"] if ball else fc["total"]
         total_env_steps = world * B * args.steps
         value = total_env_steps / elapsed
-        if os.path.exists(fj) and not fake:
-            flop = {"flop_per_env_step": round(per), "achieved_tflops": round(value / world * per / 1e12, 3), "peak_fp32_tflops": 157.3,
-                    "frac": round(value / world * per / 157.3e12, 5),
-                    "source": "profiles/r02_oracle_flop_count.json (instrumented float64 oracle, tools/count_flops.py" +
-                              ("; smooth dynamics only - the oracle's dense constraint solver is not the kernel's algorithm)" if ball else "; counted before the fly's own contacts existed: collision and contact rows excluded)")}
-        algo = BALL_ALGO_BYTES_PER_ENV_STEP if ball else ALGO_BYTES_PER_ENV_STEP
-        achieved = algo * B / (k_ms * 1e-3) / 1e9
         out = {
             "metric": "env-steps/sec (whole node), fruitfly " + ("walk_on_ball task" if ball else "flight-imitation task"),
             "value": round(value, 1), "unit": "env-steps/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -390,14 +441,11 @@ def main():
                                    "flight_imitation (BASELINE configs[3]): 4 substeps @5e-5 s (joint limits, fluid forces, the fly's own contacts) + WBPG + obs/reward/termination/auto-reset",
                        "envs_per_gpu": B, "global_batch": world * B, "parallelism": f"env-sharded x{world}" + (" + RCCL action scatter from / timestep gather to rank 0" if multi else "") + (" (one-rank rehearsal: FLYBODY_BENCH_FORCE_MULTI)" if forced else ""),
                        "actions": f"raw U(-{BALL_AMP:g}, {BALL_AMP:g})^59, resident in HBM" if ball else "uniform over the raw action spec (canonical U(-1,1)), resident in HBM"},
-            "roofline": {"bound": "hbm", "achieved": round(achieved, 4), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": round(achieved / HBM_PEAK_GBS, 8), "traffic": traffic, "traffic_source": traffic_src,
-                         "kernel": "ball_step_kernel" if ball else "flight_step_kernel", "kernel_ms": round(k_ms, 4), "timed_region_ms_per_launch_incl_order_kernel": round(k_ms_region, 4),
-                         "algorithmic_bytes_per_launch": algo * B, "valu_frac": valu_frac, "flop": flop,
-                         "note": "fused wave-per-env step keeps state on chip; VALU/LDS-latency bound, not HBM bound (DESIGN.md)"},
             "physics_substeps_per_s": round(value * env.spec.nsub, 1),
         }
-        if hasattr(env, "get_task_state") and not fake:
+        if args.full:
+            out["roofline"] = roofline(ball, B, world, value, k_ms, k_ms_region, fake)
+        if args.full and hasattr(env, "get_task_state") and not fake:
             # envs that met more simultaneous contacts / constraint rows than the kernel carries (the deepest are kept):
             # walk_on_ball: the flag is sticky over the episode; flight: a position stage of the last control step
             ints = env.get_task_state()[0]

@@ -93,7 +93,7 @@ def test_bench_multiprocess_control_flow_on_gloo():
     env = dict(os.environ, FLYBODY_BENCH_FAKE="1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "6", "--warmup", "2",
-           "--envs-per-gpu", "64"]
+           "--envs-per-gpu", "64", "--full"]
     out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=280)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]

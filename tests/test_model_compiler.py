@@ -2,7 +2,7 @@
 import numpy as np
 import pytest
 
-from conftest import BLOB, HAVE_REFERENCE
+from conftest import BLOB
 from flybody_amd.model.blob import read_blob
 
 
@@ -61,27 +61,23 @@ def test_welded_links_conserve_mass_and_com(blob):
     assert len(blob["fbox_link"]) + 2 == (blob["body_fluid_kind"] > 0).sum()
 
 
-@pytest.mark.skipif(not HAVE_REFERENCE, reason="needs the reference assets")
-def test_recompile_matches_committed_blob(blob):
+def test_recompile_matches_committed_blob(blob, flight_model):
     from flybody_amd.model.blob import model_tensors
-    from flybody_amd.model.compiler import build_flight_model
 
-    m, L = build_flight_model()
+    m, L = flight_model
     t = model_tensors(m, L)
     for k, v in t.items():
         np.testing.assert_allclose(np.asarray(v, dtype=np.float64), blob[k], rtol=1e-12, atol=1e-15, err_msg=k)
 
 
-@pytest.mark.skipif(not HAVE_REFERENCE, reason="needs the reference assets")
-def test_com_offset_known_answer():
+def test_com_offset_known_answer(flight_model):
     """Whole-fly CoM relative to the root in the thorax frame, `tasks/task_utils.py:188`.  The constant
     was taken at an unstated wing pose; with wings at the joint zero the agreement is ~2e-3 cm, which
     bounds the combined error of mesh inertias (incl. the five .msh substitutes and the rebuilt eye
     caps) and of the leg retraction."""
     from flybody_amd.model import pyref
-    from flybody_amd.model.compiler import build_flight_model
 
-    m, _ = build_flight_model()
+    m, _ = flight_model
     k = pyref.kinematics(m, m.qpos0)
     com, _ = pyref.subtree_com(m, k)
     off = com[1] - k["xpos"][1]
