@@ -711,6 +711,63 @@ CVX_FN float separation_bound(const Geom &a, const Geom &b) {
   return best;
 }
 
+// ---------------------------------------------------------------------------------------------------------------------------
+// The same bounds in one form for every geom type (the flight kernel's broad phase, where one wave holds pairs of every class and
+// a type branch runs all of its paths).  A geom is a segment of half-length h along its local z, Minkowski-summed with an ellipsoid
+// of radii (ex, ey, ez): sphere h = 0, (r, r, r); capsule h = half, (r, r, r); ellipsoid h = 0, (s0, s1, s2); cylinder h = half,
+// (r, r, 0) - a flat disc.  With l = R'n its support point is c + R (E^2 l / |E l| + sign(l_z) h e_z) and its support value
+// n.c + |E l| + h |l_z|: the same instructions on every lane.  The core segment (core_segment) is a local axis and a half-length.
+// The radii, h and the core segment depend on the type and size only: per-geom constants made on the host by `ushape`.
+struct UShape { float ex, ey, ez, h, kx, ky, kz, kh; };
+#ifdef CVX_HOST
+static inline
+#else
+__host__ __device__ inline
+#endif
+UShape ushape(int type, float s0, float s1, float s2) {
+  UShape u{s0, s0, s0, 0.f, 0.f, 0.f, 1.f, 0.f};
+  if (type == ELLIPSOID) {
+    const float mx = fmaxf(fmaxf(s0, s1), s2), mid = s0 + s1 + s2 - mx - fminf(fminf(s0, s1), s2);
+    u.ey = s1; u.ez = s2;
+    u.kx = s0 == mx ? 1.f : 0.f; u.ky = s0 != mx && s1 == mx ? 1.f : 0.f; u.kz = s0 != mx && s1 != mx ? 1.f : 0.f;
+    u.kh = mx - mid;
+  } else if (type == CAPSULE) {
+    u.h = u.kh = s1;
+  } else if (type == CYLINDER) {
+    u.ez = 0.f; u.h = u.kh = s1;
+  }
+  return u;
+}
+// centre, rotation, radii, segment half-length, core segment (world axis, half-length)
+struct GeomU { V3 c; M3 R; float ex, ey, ez, h; V3 ka; float kh; };
+CVX_FN GeomU make_u(V3 c, Q4 q, const UShape &s) {
+  GeomU g;
+  g.c = c; g.R = q2m(q);
+  g.ex = s.ex; g.ey = s.ey; g.ez = s.ez; g.h = s.h;
+  g.ka = mv(g.R, V3{s.kx, s.ky, s.kz}); g.kh = s.kh;
+  return g;
+}
+// support value in the world direction n (unit) less n.c: the same for n and -n.  The bounds need no support point, so no type's
+// special case remains (n along a cylinder's axis: |E l| = 0, the whole disc).
+CVX_FN float hsupport_u(const GeomU &g, V3 n) {
+  const V3 l = mtv(g.R, n), el = {g.ex * l.x, g.ey * l.y, g.ez * l.z};
+  return fsqrt(dot(el, el)) + g.h * fabsf(l.z);
+}
+// overlap(a, b, u)
+CVX_FN float overlap_u(const GeomU &a, const GeomU &b, V3 u) { return hsupport_u(a, u) + hsupport_u(b, u) - dot(u, b.c - a.c); }
+// separation_bound(a, b)
+CVX_FN float separation_bound_u(const GeomU &a, const GeomU &b) {
+  float x1, x2, best = -1e30f;
+  segment_closest(a.c, a.ka, a.kh, b.c, b.ka, b.kh, x1, x2);
+  V3 u = (b.c + x2 * b.ka) - (a.c + x1 * a.ka);
+  float ul = fsqrt(dot(u, u));
+  if (ul > 1e-12f) best = -overlap_u(a, b, frcp(ul) * u);
+  u = b.c - a.c;
+  ul = fsqrt(dot(u, u));
+  if (ul > 1e-12f) best = fmaxf(best, -overlap_u(a, b, frcp(ul) * u));
+  return best;
+}
+
 // mj: mjc_CapsuleCapsule (closest points of the two axis segments, one contact); a sphere is a capsule of zero length, for which
 // the same formulas are mjc_SphereCapsule / mjraw_SphereSphere
 CVX_FN Contact capsule_capsule(const Geom &a, const Geom &b) {

@@ -13,6 +13,8 @@
 #include <string>
 #include <vector>
 
+#include "convex.hpp"  // cvx::ushape: the broad phase's per-geom constants
+
 // Pointers stored inside structs that live in device memory lose their address space when the compiler cannot trace
 // them back to a kernel argument, and are then dereferenced with FLAT loads (slower, and they tie the LDS and vector
 // memory wait counters together).  Declaring them global on the device side makes every table read a global_load.
@@ -136,6 +138,7 @@ struct DevModel {
   unsigned long long cg_mmask[2];  // geoms that carry the margin / gap (labrum, claws)
   const int FFE_GLOBAL *cg_link, *cg_type;
   const float FFE_GLOBAL *cg_pos, *cg_quat, *cg_size, *cg_brad, *cg_invw;
+  const float4 FFE_GLOBAL *cg_ush;  // [kMaxGeom][2] the broad phase's form of each geom (cvx::ushape): radii + segment half-length, core segment
   const unsigned short FFE_GLOBAL *cp_pair;
   const unsigned long long FFE_GLOBAL *l_dofmask;
 };
@@ -207,7 +210,7 @@ struct HostModel {
     fix(dst.a_fhi);
     fix(dst.wing_dof); fix(dst.wing_qadr); fix(dst.wing_action); fix(dst.wing_ctrl); fix(dst.obsj_qadr); fix(dst.obsj_dof);
     fix(dst.qpos0);
-    fix(dst.cg_link); fix(dst.cg_type); fix(dst.cg_pos); fix(dst.cg_quat); fix(dst.cg_size); fix(dst.cg_brad); fix(dst.cg_invw);
+    fix(dst.cg_link); fix(dst.cg_type); fix(dst.cg_pos); fix(dst.cg_quat); fix(dst.cg_size); fix(dst.cg_brad); fix(dst.cg_invw); fix(dst.cg_ush);
     fix(dst.cp_pair); fix(dst.l_dofmask);
   }
 };
@@ -552,6 +555,8 @@ inline HostModel build_host_model(const Blob &b) {
   // ---- collision ------------------------------------------------------------------------------------
   std::vector<int> cg_link(kMaxGeom, 0), cg_type(kMaxGeom, 0);
   std::vector<float> cg_pos(3 * kMaxGeom, 0.f), cg_quat(4 * kMaxGeom, 0.f), cg_size(3 * kMaxGeom, 0.f), cg_brad(kMaxGeom, 0.f), cg_invw(kMaxGeom, 0.f);
+  std::vector<cvx::UShape> cg_ush(kMaxGeom, cvx::UShape{});
+  static_assert(sizeof(cvx::UShape) == 2 * sizeof(float4), "cg_ush rows are read as two float4");
   std::vector<unsigned short> cp_pair(kMaxPair, 0xffffu);
   std::vector<unsigned long long> l_dofmask(kMaxLink + 1, 0ull);
   V.ncg = V.ncp = 0; V.cg_mmask[0] = V.cg_mmask[1] = 0ull;
@@ -581,6 +586,7 @@ inline HostModel build_host_model(const Blob &b) {
       const double s0 = gs.f(3 * g), s1 = gs.f(3 * g + 1), s2 = gs.f(3 * g + 2);
       cg_brad[g] = static_cast<float>(ty == 2 ? s0 : ty == 3 ? s0 + s1 : ty == 5 ? std::sqrt(s0 * s0 + s1 * s1) : std::fmax(s0, std::fmax(s1, s2)));
       cg_invw[g] = static_cast<float>(biw.f(2 * gb.i(g)));
+      cg_ush[g] = cvx::ushape(ty, cg_size[g], cg_size[kMaxGeom + g], cg_size[2 * kMaxGeom + g]);
       // mj_contactParam mixes equal parameters of equal weights: uniform K, B, solimp over the fly's geoms
       double tc = gsr.f(2 * g), dr = gsr.f(2 * g + 1), dmax = std::fmin(std::fmax(gsi.f(5 * g + 1), 1e-4), 0.9999), K, B;
       if (tc > 0) { tc = std::fmax(tc, 2 * h); K = 1.0 / std::fmax(1e-15, dmax * dmax * tc * tc * dr * dr); B = 2.0 / std::fmax(1e-15, dmax * tc); }
@@ -638,7 +644,7 @@ inline HostModel build_host_model(const Blob &b) {
   set_off(V.obsj_qadr, A.put(obsj_qadr)); set_off(V.obsj_dof, A.put(obsj_dof));
   set_off(V.qpos0, A.put(qpos0));
   set_off(V.cg_link, A.put(cg_link)); set_off(V.cg_type, A.put(cg_type)); set_off(V.cg_pos, A.put(cg_pos)); set_off(V.cg_quat, A.put(cg_quat));
-  set_off(V.cg_size, A.put(cg_size)); set_off(V.cg_brad, A.put(cg_brad)); set_off(V.cg_invw, A.put(cg_invw));
+  set_off(V.cg_size, A.put(cg_size)); set_off(V.cg_brad, A.put(cg_brad)); set_off(V.cg_invw, A.put(cg_invw)); set_off(V.cg_ush, A.put(cg_ush));
   set_off(V.cp_pair, A.put(cp_pair)); set_off(V.l_dofmask, A.put(l_dofmask));
   H.arena = A.bytes();
   return H;

@@ -464,10 +464,16 @@ __device__ __forceinline__ cvx::Geom load_geom(const CollA &A, const DevModel FF
   return cvx::Geom{dm::V3{cc.x, cc.y, cc.z}, dm::Q4{qq.x, qq.y, qq.z, qq.w}, M.cg_size[g], M.cg_size[kMaxGeom + g], M.cg_size[2 * kMaxGeom + g], M.cg_type[g]};
 }
 
+// the broad phase's per-geom constants (cvx::ushape, made on the host)
+__device__ __forceinline__ cvx::UShape ush(const DevModel FFE_CONST &M, int g) {
+  const float4 u = M.cg_ush[2 * g], k = M.cg_ush[2 * g + 1];
+  return cvx::UShape{u.x, u.y, u.z, u.w, k.x, k.y, k.z, k.w};
+}
+
 // Broad phase: MuJoCo's bounding-sphere test over the static candidate list, then a rigorous lower bound of the distance from a
-// separating direction (two generic ones, cvx::separation_bound, and the one the narrow phase found for the pair on the last
-// substep it ran: `sdc` in, `sdn` out).  Narrow phase: one lane per remaining pair (cvx::collide: mjc_CapsuleCapsule / the general
-// convex collider restated in convex.hpp).  A contact inside its margin but outside margin - gap exerts no force and - with no
+// separating direction (two generic ones, cvx::separation_bound_u, and the one the narrow phase found for the pair on the last
+// substep it ran: `sdc` + the lane-resident pair ids in, `sdn` out).  Narrow phase: one lane per remaining pair (cvx::collide:
+// mjc_CapsuleCapsule / the general convex collider restated in convex.hpp).  A contact inside its margin but outside margin - gap exerts no force and - with no
 // adhesion actuator in the flight model - takes part in nothing: dropped.  The contacts (at most kMC, the deepest) are left in
 // `rec`.  Returns count | overflow << 8 | new cache count << 16.
 // Narrow phase + contact selection over the `n2` pairs the broad phase left in `cl2` (one lane per pair).  WITH_RARE = false leaves out
@@ -530,7 +536,7 @@ __device__ __forceinline__ int collide_narrow(Tile &T, const DevModel FFE_CONST 
 }
 
 
-__device__ __noinline__ int flight_collide_a(Tile *Tp, const DevModel FFE_CONST *Mp, const int lane, const int ncache) {
+__device__ __noinline__ int flight_collide_a(Tile *Tp, const DevModel FFE_CONST *Mp, const int lane, const int ncache_, const int cpid) {
   Tile &T = *Tp;
   const DevModel FFE_CONST &M = *Mp;
   CollA &A = coll_a(T);
@@ -578,6 +584,10 @@ __device__ __noinline__ int flight_collide_a(Tile *Tp, const DevModel FFE_CONST 
   if (n1 > 128) { n1 = 128; ovf = 1; }
   SYNC();
   CSTAMP(17);  // geom frames + bounding spheres
+  // The cache's pairs, one per lane (lane k < ncache: entry k), with the key of the borrowing rule below (first geom | second geom's type << 8)
+  const int ncache = __builtin_amdgcn_readfirstlane(ncache_);
+  int ckey = -1;
+  if (lane < ncache) ckey = (cpid & 255) | (M.cg_type[min((cpid >> 8) & 255, kMaxGeom - 1)] << 8);
   int n2 = 0, nk = 0;
   bool any_rare = false;
 #pragma unroll 1
@@ -589,24 +599,34 @@ __device__ __noinline__ int flight_collide_a(Tile *Tp, const DevModel FFE_CONST 
     if (base + lane < n1) {
       w = B.cl1[base + lane];
       const int a = w & 255, b = w >> 8;
-      const cvx::Geom ga = load_geom(A, M, a), gb = load_geom(A, M, b);
+      const float4 ca = A.gc[a], qa = A.gq[a], cb = A.gc[b], qb = A.gq[b];
+      const cvx::UShape sa = ush(M, a), sb = ush(M, b);
+      const cvx::GeomU ga = cvx::make_u(dm::V3{ca.x, ca.y, ca.z}, dm::Q4{qa.x, qa.y, qa.z, qa.w}, sa), gb = cvx::make_u(dm::V3{cb.x, cb.y, cb.z}, dm::Q4{qb.x, qb.y, qb.z, qb.w}, sb);
+      const int ta = M.cg_type[a], tb = M.cg_type[b];
       const float margin = pair_margin(a, b), incl = margin - (margin != 0.f ? M.c_gap : 0.f);  // (only a contact inside margin - gap matters here)
-      pass = cvx::separation_bound(ga, gb) <= incl;
+      pass = cvx::separation_bound_u(ga, gb) <= incl;
+      // the pair's cache entry, and the last entry of its first geom against a geom of its second one's type (wave-uniform reads of the
+      // lane-resident cache: no LDS round trips)
+      int hit = -1, alt = -1;
+      const int akey = a | (tb << 8);
+#pragma unroll 1
+      for (int k = 0; k < ncache; k++) {
+        const int pk = __builtin_amdgcn_readlane(cpid, k), kk = __builtin_amdgcn_readlane(ckey, k);
+        if (pk == (int)w) hit = k;
+        else if (kk == akey) alt = k;
+      }
       if (pass) {
-        int alt = -1;
-        for (int k = 0; k < ncache; k++) {
-          const int pk = __float_as_int(A.sdc[k][3]);
-          if (pk == (int)w) {
-            kn = dm::V3{A.sdc[k][0], A.sdc[k][1], A.sdc[k][2]};
-            kt = A.sdc[k][4];
-            have_kn = true;
-          } else if ((pk & 255) == a && M.cg_type[pk >> 8] == gb.type) alt = k;
-        }
         // A wing sweeps over the abdomen's stacked segments, a new pair every substep or two: a pair seen for the first time borrows the
         // direction its ellipsoid holds against a neighbouring geom of the same kind.  As a bound any direction is rigorous; as a start it
         // saves the narrow phase its search from scratch (the most expensive thing a wave does: it set the length of whole launches).
-        if (!have_kn && alt >= 0 && ga.type == cvx::ELLIPSOID) { kn = dm::V3{A.sdc[alt][0], A.sdc[alt][1], A.sdc[alt][2]}; have_kn = true; }
-        if (have_kn) keep = -cvx::overlap(ga, gb, kn) > incl;
+        const int k = hit >= 0 ? hit : (ta == cvx::ELLIPSOID ? alt : -1);
+        if (k >= 0) {
+          const float *o = A.sdc[k];
+          kn = dm::V3{o[0], o[1], o[2]};
+          kt = hit >= 0 ? o[4] : 0.f;
+          have_kn = true;
+          keep = -cvx::overlap_u(ga, gb, kn) > incl;
+        }
         pass = !keep;
       }
     }
@@ -647,7 +667,7 @@ __device__ __forceinline__ void flight_collide(Ctx &c) {
 #ifdef FFE_TRACE
   const unsigned long long tr_c0 = __builtin_amdgcn_s_memrealtime();
 #endif
-  int r = __builtin_amdgcn_readfirstlane(flight_collide_a(&T, c.Mp, c.lane, c.sd_cnt));
+  int r = __builtin_amdgcn_readfirstlane(flight_collide_a(&T, c.Mp, c.lane, c.sd_cnt, c.sd_pid));
   if (r & 0x40000000) {
     r = __builtin_amdgcn_readfirstlane(flight_collide_b(&T, c.Mp, c.lane, r));
     c.nrare++;
