@@ -28,6 +28,7 @@ class FlightTask(C.Structure):
         ("future_steps", C.c_int32), ("time_limit_steps", C.c_int32), ("episode_limit_steps", C.c_int32), ("terminal_com_dist", C.c_double),
         ("ghost_accel_z", C.c_double), ("pad_first_obs", C.c_int32), ("physics_flags", C.c_int32),
         ("canonical_actions", C.c_int32), ("clip_actions", C.c_int32),
+        ("contact_capacity", C.c_int32),
     ]
 
 

@@ -63,15 +63,22 @@ class BatchedFlyEnv:
     def __init__(self, wbpg, ref_qpos, ref_qvel=None, *, batch_size: int, device: int = 0, seed: int = 0, env_id_base: int = 0,
                  future_steps: int = 5, time_limit: float = 0.6, terminal_com_dist: float = 2.0, pad_first_obs: bool = False,
                  physics_flags: int = 0, canonical_actions: bool = False, clip_actions: bool = False, double_buffer: bool = False,
-                 blob_path: str = FLIGHT_BLOB):
+                 blob_path: str = FLIGHT_BLOB, contact_capacity: int = 6):
         """`ref_qpos` / `ref_qvel`: preprocessed reference set, either stacked arrays (N,T,7) / (N,T,6) or one
-        `tasks.trajectories.RefSet` (trajectories of individual lengths)."""
+        `tasks.trajectories.RefSet` (trajectories of individual lengths).
+
+        `contact_capacity`: simultaneous self-contacts the solver carries per env, 6 (default, the benchmarked kernel) or 12
+        (a second instantiation of the step kernel: same physics up to six contacts, constraint rows for up to twelve).  The
+        library rejects every other value."""
         import json
 
         import torch
 
         if not torch.cuda.is_available():
             raise RuntimeError("BatchedFlyEnv needs a HIP device (MI355X); there is no CPU fallback")
+        if isinstance(contact_capacity, bool) or int(contact_capacity) != contact_capacity:
+            raise TypeError(f"contact_capacity must be an integer (6 or 12), got {contact_capacity!r}")
+        self.contact_capacity = int(contact_capacity)
         self._torch = torch
         self._L = _capi.lib()
         self.batch_size = int(batch_size)
@@ -107,7 +114,8 @@ class BatchedFlyEnv:
             future_steps=future_steps, time_limit_steps=int(round(time_limit / wbpg.dt_ctrl)),
             episode_limit_steps=time_limit_control_steps(time_limit, h_phys, nsub),
             terminal_com_dist=float(terminal_com_dist), ghost_accel_z=ghost_accel_z, pad_first_obs=int(pad_first_obs),
-            physics_flags=int(physics_flags), canonical_actions=int(canonical_actions), clip_actions=int(clip_actions))
+            physics_flags=int(physics_flags), canonical_actions=int(canonical_actions), clip_actions=int(clip_actions),
+            contact_capacity=self.contact_capacity)
         h = C.c_void_p()
         rc = self._L.ffe_create_flight(blob, len(blob), C.byref(task), self.batch_size, device, seed, env_id_base, C.byref(h))
         if rc != 0:

@@ -27,9 +27,7 @@ def needs_build() -> bool:
     return any(os.path.getmtime(os.path.join(CSRC, f)) > t for f in SOURCES + HEADERS)
 
 
-def build(force: bool = False, verbose: bool = False) -> str:
-    if not force and not needs_build():
-        return LIB
+def _common_flags() -> list:
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
     # -fno-slp-vectorize: the SLP vectoriser packs scalar FMAs whose multiplier sits in an SGPR (v_readlane broadcasts) into
     # v_pk_mul + moves, which costs more than it saves in both kernels (+3 % env-steps/s without it, measured).
@@ -37,6 +35,37 @@ def build(force: bool = False, verbose: bool = False) -> str:
     # loops through one SGPR; the ILP scheduler batches the broadcasts (walk_on_ball +8.6 %, flight +0.8 %, measured)
     common = [hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fno-slp-vectorize",
               "-mllvm", "-amdgpu-sched-strategy=iterative-ilp"]
+    return common
+
+
+def kernel_resource_usage(src: str = "fly_env.hip", match: str = "flight_step_kernel") -> dict:
+    """Compiles `src` with the library's own flags plus -Rpass-analysis=kernel-resource-usage (nothing is kept) and returns
+    {mangled kernel name: {"VGPRs", "TotalSGPRs", "ScratchSize", "Occupancy", "SGPRs Spill", "VGPRs Spill", "LDS Size"}} for the
+    kernels whose name contains `match`: the flight step kernel's instantiations, one per contact capacity."""
+    import re
+    import tempfile
+
+    with tempfile.TemporaryDirectory() as tmp:
+        cmd = _common_flags() + PER_SOURCE_FLAGS.get(src, []) + ["--cuda-device-only", "-Rpass-analysis=kernel-resource-usage", "-c",
+                                                                 os.path.join(CSRC, src), "-o", os.path.join(tmp, "dev.o")]
+        text = subprocess.run(cmd, check=True, stderr=subprocess.PIPE, stdout=subprocess.DEVNULL, text=True).stderr
+    out, cur = {}, None
+    for line in text.splitlines():
+        m = re.search(r"remark: Function Name: (\S+)", line)
+        if m:
+            cur = out.setdefault(m.group(1), {}) if match in m.group(1) else None
+            continue
+        m = re.search(r"remark:\s+([A-Za-z ]+?)(?: \[[^\]]*\])?: (\d+)", line)
+        if m and cur is not None:
+            cur[m.group(1).strip()] = int(m.group(2))
+    return out
+
+
+def build(force: bool = False, verbose: bool = False) -> str:
+    if not force and not needs_build():
+        return LIB
+    common = _common_flags()
+    hipcc = common[0]
     objs = []
     for src in SOURCES:
         obj = os.path.join(CSRC, "_obj_" + os.path.splitext(src)[0] + ".o")

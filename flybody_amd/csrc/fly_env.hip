@@ -33,7 +33,8 @@
 
 namespace ffe {
 
-constexpr int kMC = 6;   // contacts per env the solver carries (deepest kept; more is flagged)
+constexpr int kMC = 6;   // contacts per env the solver carries (deepest kept; more is flagged): the default capacity, and the record layout below
+constexpr int kMCX = 12;  // the selectable larger capacity (ffe_flight_task::contact_capacity): a second instantiation of the step kernel
 constexpr int kNSD = 16;  // convex pairs whose separating direction is remembered from substep to substep (a wing near the abdomen brings six
                          // ellipsoid - cylinder pairs at once, whose search from scratch is the most expensive thing a wave can do: 25 - 100 us)
 
@@ -63,6 +64,23 @@ struct alignas(64) EnvState {
   int sd_pid[kNSD];
   int nct, sd_cnt, ct_pad[2];
 };
+// The record of a capacity-12 handle: the same record with contacts 6 .. 11 of the carried-over position stage behind it, so that
+// everything that is not the step kernel addresses either kind as an EnvState at a stride (state_at).
+struct alignas(64) EnvStateX {
+  EnvState s;
+  float ctx_f[kMCX - kMC][9];
+  int ctx_i[kMCX - kMC][3];
+};
+static_assert(offsetof(EnvStateX, s) == 0, "EnvStateX starts with the common record");
+template <int MC> struct StateOf { using type = EnvState; };
+template <> struct StateOf<kMCX> { using type = EnvStateX; };
+__device__ __forceinline__ EnvState &common(EnvState &S) { return S; }
+__device__ __forceinline__ EnvState &common(EnvStateX &S) { return S.s; }
+__device__ __forceinline__ float *ct_f_row(EnvState &S, int k) { return S.ct_f[k]; }
+__device__ __forceinline__ int *ct_i_row(EnvState &S, int k) { return S.ct_i[k]; }
+__device__ __forceinline__ float *ct_f_row(EnvStateX &S, int k) { return k < kMC ? S.s.ct_f[k] : S.ctx_f[k - kMC]; }
+__device__ __forceinline__ int *ct_i_row(EnvStateX &S, int k) { return k < kMC ? S.s.ct_i[k] : S.ctx_i[k - kMC]; }
+__device__ __forceinline__ EnvState &state_at(void *states, size_t stride, int i) { return *reinterpret_cast<EnvState *>(static_cast<char *>(states) + stride * (size_t)i); }
 
 struct TaskDev {
   int nfreq, ntraj, future_steps, time_limit_steps, episode_limit_steps, pad_first_obs, flags, obs_dim, canonical, clip;
@@ -453,11 +471,11 @@ enum { DBG_SKIP_FACTOR = 1 << 16, DBG_SKIP_SOLVE = 1 << 17, DBG_SKIP_STAGE1 = 1 
 // with the factor's workspace (T.LD) and the link scratch arrays (T.la .. T.lc) - both idle between stage 1 and stage 2 - as scratch.
 struct CollA { float4 gc[kMaxGeom], gq[kMaxGeom]; float lq[kMaxLink][4]; float sdc[kNSD][5], sdn[kNSD][5]; };                                        // over T.LD
 constexpr int kCL2 = 24;  // pairs one narrow phase takes (typical: the touching ones, 2 - 6)
-struct CollB { unsigned short cl1[128], cl2[kCL2]; float rec[kMC][12]; float cl2n[kCL2][5]; };  // over T.la .. T.lc
+template <int MC> struct CollB { unsigned short cl1[128], cl2[kCL2]; float rec[MC][12]; float cl2n[kCL2][5]; };  // over T.la .. T.lc
 static_assert(sizeof(CollA) <= sizeof(Tile::LD), "collision scratch A");
-static_assert(sizeof(CollB) <= sizeof(Tile::lT) + sizeof(Tile::lb) + sizeof(Tile::lc) && offsetof(Tile, lc) == offsetof(Tile, lT) + sizeof(Tile::lT) + sizeof(Tile::lb), "collision scratch B");
+static_assert(sizeof(CollB<kMC>) == 1072 && sizeof(CollB<kMCX>) == 1360 && sizeof(CollB<kMCX>) <= sizeof(Tile::lT) + sizeof(Tile::lb) + sizeof(Tile::lc) && offsetof(Tile, lc) == offsetof(Tile, lT) + sizeof(Tile::lT) + sizeof(Tile::lb), "collision scratch B");
 __device__ __forceinline__ CollA &coll_a(Tile &T) { return *reinterpret_cast<CollA *>(&T.LD[0]); }
-__device__ __forceinline__ CollB &coll_b(Tile &T) { return *reinterpret_cast<CollB *>(&T.lT[0][0]); }
+template <int MC> __device__ __forceinline__ CollB<MC> &coll_b(Tile &T) { return *reinterpret_cast<CollB<MC> *>(&T.lT[0][0]); }
 
 __device__ __forceinline__ cvx::Geom load_geom(const CollA &A, const DevModel FFE_CONST &M, int g) {
   const float4 cc = A.gc[g], qq = A.gq[g];
@@ -474,14 +492,14 @@ __device__ __forceinline__ cvx::UShape ush(const DevModel FFE_CONST &M, int g) {
 // separating direction (two generic ones, cvx::separation_bound_u, and the one the narrow phase found for the pair on the last
 // substep it ran: `sdc` + the lane-resident pair ids in, `sdn` out).  Narrow phase: one lane per remaining pair (cvx::collide:
 // mjc_CapsuleCapsule / the general convex collider restated in convex.hpp).  A contact inside its margin but outside margin - gap exerts no force and - with no
-// adhesion actuator in the flight model - takes part in nothing: dropped.  The contacts (at most kMC, the deepest) are left in
+// adhesion actuator in the flight model - takes part in nothing: dropped.  The contacts (at most MC, the deepest) are left in
 // `rec`.  Returns count | overflow << 8 | new cache count << 16.
 // Narrow phase + contact selection over the `n2` pairs the broad phase left in `cl2` (one lane per pair).  WITH_RARE = false leaves out
 // the two classes that need the most registers (ellipsoid - cylinder: a wing near the abdomen; cylinder - cylinder) - see flight_collide.
-template <bool WITH_RARE>
+template <bool WITH_RARE, int MC>
 __device__ __forceinline__ int collide_narrow(Tile &T, const DevModel FFE_CONST &M, const int lane, int n2, int nk, int ovf) {
   CollA &A = coll_a(T);
-  CollB &B = coll_b(T);
+  CollB<MC> &B = coll_b<MC>(T);
   const unsigned long long mm0 = M.cg_mmask[0], mm1 = M.cg_mmask[1];
   const float mclass = M.c_margin;
   auto pair_margin = [&](int a, int b) {
@@ -513,7 +531,7 @@ __device__ __forceinline__ int collide_narrow(Tile &T, const DevModel FFE_CONST 
   }
   nk = min(nk + n2, kNSD);
   unsigned long long bal = __ballot(hit);
-  if (__popcll(bal) > kMC) {  // more contacts than the solver carries: the env is flagged and the deepest are kept
+  if (__popcll(bal) > MC) {  // more contacts than the solver carries: the env is flagged and the deepest are kept
     ovf = 1;
     int rank = 0;
     for (unsigned long long m = bal; m; m &= m - 1) {
@@ -521,7 +539,7 @@ __device__ __forceinline__ int collide_narrow(Tile &T, const DevModel FFE_CONST 
       const float dj = __shfl(dist, j);
       if (dj < dist || (dj == dist && j < lane)) rank++;
     }
-    hit = hit && rank < kMC;
+    hit = hit && rank < MC;
     bal = __ballot(hit);
   }
   const int n = __popcll(bal), idx = __popcll(bal & ((1ull << lane) - 1ull));
@@ -536,11 +554,12 @@ __device__ __forceinline__ int collide_narrow(Tile &T, const DevModel FFE_CONST 
 }
 
 
+template <int MC>
 __device__ __noinline__ int flight_collide_a(Tile *Tp, const DevModel FFE_CONST *Mp, const int lane, const int ncache_, const int cpid) {
   Tile &T = *Tp;
   const DevModel FFE_CONST &M = *Mp;
   CollA &A = coll_a(T);
-  CollB &B = coll_b(T);
+  CollB<MC> &B = coll_b<MC>(T);
   const int ncg = M.ncg;
   CSTAMP_DECL;
   for (int g = lane; g < ncg; g += kWave) {
@@ -644,32 +663,34 @@ __device__ __noinline__ int flight_collide_a(Tile *Tp, const DevModel FFE_CONST 
   // The narrow phase of the classes that run every substep is part of this (leaf) function: it stays within the caller-saved registers, so
   // the call costs no save / restore traffic.  A pair of a rare class sends the whole narrow phase to the second function.
   if (any_rare) return 0x40000000 | n2 | (nk << 8) | (ovf << 16);
-  const int r = collide_narrow<false>(T, M, lane, n2, nk, ovf);
+  const int r = collide_narrow<false, MC>(T, M, lane, n2, nk, ovf);
   CSTAMP(19);  // narrow phase (common classes)
   return r;
 }
 
 // the same with every pair class (entered only when the broad phase left an ellipsoid - cylinder or cylinder - cylinder pair)
+template <int MC>
 __device__ __noinline__ int flight_collide_b(Tile *Tp, const DevModel FFE_CONST *Mp, const int lane, const int packed) {
-  return collide_narrow<true>(*Tp, *Mp, lane, packed & 0xff, (packed >> 8) & 0xff, (packed >> 16) & 1);
+  return collide_narrow<true, MC>(*Tp, *Mp, lane, packed & 0xff, (packed >> 8) & 0xff, (packed >> 16) & 1);
 }
 
 // the position stage's collision: cache in, contacts + cache out (lane-resident, see Ctx)
+template <int MC>
 __device__ __forceinline__ void flight_collide(Ctx &c) {
   const DevModel FFE_CONST &M = model(c);
   Tile &T = c.T;
   c.nct = 0;
   if (M.ncg == 0 || (c.flags & FFE_NO_CONTACT)) return;
   CollA &A = coll_a(T);
-  CollB &B = coll_b(T);
+  CollB<MC> &B = coll_b<MC>(T);
   if (c.lane < kNSD) { float *o = A.sdc[c.lane]; o[0] = c.sd_nx; o[1] = c.sd_ny; o[2] = c.sd_nz; o[3] = __int_as_float(c.sd_pid); o[4] = c.sd_t; }
   SYNC();
 #ifdef FFE_TRACE
   const unsigned long long tr_c0 = __builtin_amdgcn_s_memrealtime();
 #endif
-  int r = __builtin_amdgcn_readfirstlane(flight_collide_a(&T, c.Mp, c.lane, c.sd_cnt, c.sd_pid));
+  int r = __builtin_amdgcn_readfirstlane(flight_collide_a<MC>(&T, c.Mp, c.lane, c.sd_cnt, c.sd_pid));
   if (r & 0x40000000) {
-    r = __builtin_amdgcn_readfirstlane(flight_collide_b(&T, c.Mp, c.lane, r));
+    r = __builtin_amdgcn_readfirstlane(flight_collide_b<MC>(&T, c.Mp, c.lane, r));
     c.nrare++;
   }
 #ifdef FFE_TRACE
@@ -679,7 +700,7 @@ __device__ __forceinline__ void flight_collide(Ctx &c) {
   c.ct_ovf |= (r >> 8) & 0xff;
   c.sd_cnt = r >> 16;
   if (c.lane < kNSD) { const float *o = A.sdn[c.lane]; c.sd_nx = o[0]; c.sd_ny = o[1]; c.sd_nz = o[2]; c.sd_pid = __float_as_int(o[3]); c.sd_t = o[4]; }
-  if (c.lane < kMC) {
+  if (c.lane < MC) {
     const float *o = B.rec[c.lane];
     c.ct_nx = o[0]; c.ct_ny = o[1]; c.ct_nz = o[2]; c.ct_px = o[3]; c.ct_py = o[4]; c.ct_pz = o[5]; c.ct_dist = o[6]; c.ct_incl = o[7]; c.ct_invw = o[8];
     c.ct_l1 = __float_as_int(o[9]); c.ct_l2 = __float_as_int(o[10]); c.ct_pid = __float_as_int(o[11]);
@@ -1165,6 +1186,7 @@ __device__ __forceinline__ float2 bsolve(Ctx &c, float rhs, float rhs_b = 0.f) {
 
 // Stage 2 = mj_fwdActuation, mj_fwdAcceleration, mj_fwdConstraint (joint limits), accelerometer, mj_Euler.
 // `ctrl_force` is the per-dof generalized actuator force, already assembled.
+template <int MC>
 __device__ __forceinline__ V3 stage2(Ctx &c, float qfrc_act, bool integrate, bool with_ghost, double ghost_accel_z, unsigned long long &lo_mask,
                      unsigned long long &hi_mask, unsigned long long &in_lo, unsigned long long &in_hi, int &iters_out) {
   const DevModel FFE_CONST &M = model(c);
@@ -1220,16 +1242,16 @@ __device__ __forceinline__ V3 stage2(Ctx &c, float qfrc_act, bool integrate, boo
   //      J = n . (jacp of geom2's body - jacp of geom1's at the contact point), mj_makeImpedance, mj_referenceConstraint).  The row is
   //      kept by columns: this lane's dof entry of every contact's row in jk[]; lane k computes contact k's D and aref.
   const int nct = c.nct;
-  float jk[kMC], cD = 0.f, car = 0.f;
+  float jk[MC], cD = 0.f, car = 0.f;
 #pragma unroll
-  for (int k = 0; k < kMC; k++) jk[k] = 0.f;
+  for (int k = 0; k < MC; k++) jk[k] = 0.f;
   if (nct) {
     const S6 cd = is_dof ? ld6(T.cdof[lane]) : zero6();
     const V3 com = get_com(c);
     float dmin = fminf(fmaxf(M.c_solimp[0], 1e-4f), 0.9999f), dmax = fminf(fmaxf(M.c_solimp[1], 1e-4f), 0.9999f), width = fmaxf(0.f, M.c_solimp[2]),
           mid = fminf(fmaxf(M.c_solimp[3], 1e-4f), 0.9999f), power = fmaxf(1.f, M.c_solimp[4]);
 #pragma unroll
-    for (int k = 0; k < kMC; k++) {
+    for (int k = 0; k < MC; k++) {
       if (k < nct) {
         const V3 n = {rl_f(c.ct_nx, k), rl_f(c.ct_ny, k), rl_f(c.ct_nz, k)}, p = {rl_f(c.ct_px, k), rl_f(c.ct_py, k), rl_f(c.ct_pz, k)};
         const unsigned long long m1 = M.l_dofmask[rl_i(c.ct_l1, k)], m2 = M.l_dofmask[rl_i(c.ct_l2, k)];
@@ -1252,7 +1274,7 @@ __device__ __forceinline__ V3 stage2(Ctx &c, float qfrc_act, bool integrate, boo
     else { a = bsolve<0>(c, f).x; ae = a; }
   } else {
     // Contacts enter the same primal Newton through the matrix inversion lemma: with H0 = M + D_limits (the sparse factorisation) and
-    // the active contact rows J (m <= kMC of them), (H0 + J' D J) a = rhs + J' D aref is solved as
+    // the active contact rows J (m <= MC of them), (H0 + J' D J) a = rhs + J' D aref is solved as
     //   a = y0 + Y f,  y0 = H0^-1 rhs,  Y = H0^-1 J',  (D^-1 + J Y) f = -(J y0 - aref)      (f = the contacts' forces)
     // i.e. m more triangular solves with the resident factor and an m x m system (rows on lanes 0 .. m-1, Gauss-Jordan by readlane).
     // Y's columns live in LDS (T.crb / T.xmat[1..]: dead in stage 2) and are kept while the limit set - hence H0 - does not change.
@@ -1260,7 +1282,7 @@ __device__ __forceinline__ V3 stage2(Ctx &c, float qfrc_act, bool integrate, boo
     if (nct) {                // (a pair drifting apart inside its margin stays that way for many substeps: each of them cost a second pass)
       const int me = c.ct_pid & 0xffff;
 #pragma unroll
-      for (int q = 0; q < kMC; q++) {
+      for (int q = 0; q < MC; q++) {
         const int pq = rl_i(c.pc, q);
         if ((pq & 0x1ffff) == (me | 0x10000)) cact = false;
       }
@@ -1268,8 +1290,28 @@ __device__ __forceinline__ V3 stage2(Ctx &c, float qfrc_act, bool integrate, boo
     float cf = 0.f, y0 = 0.f;
     unsigned ymask = 0u;
     bool lim_changed = true;
-    auto yrow = [&](int k) -> float * { return k < 4 ? &T.crb[0][0] + kMaxDof * k : &T.xmat[1][0] + kMaxDof * (k - 4); };
-    static_assert(sizeof(T.crb) >= 4 * kMaxDof * 4 && sizeof(T.xmat) - 36 >= (kMC - 4) * kMaxDof * 4, "Y columns");
+    // Capacity 12: columns 0 .. 7 run through T.xmat[1..] and T.crb as one block (the two are adjacent), column 8 sits in T.xpos (the link
+    // origins: read by stage 1 and the collision pass only, rewritten by the next stage 1), and columns 9 .. 11 - a lane only ever
+    // touches its own entry of a column - stay with the lane (yx).  The tile is the same 10 128 B for both capacities.
+    constexpr int kYL = MC == kMC ? MC : 9;  // columns kept in LDS
+    auto yrow = [&](int k) -> float * {
+      if (MC == kMC) return k < 4 ? &T.crb[0][0] + kMaxDof * k : &T.xmat[1][0] + kMaxDof * (k - 4);
+      return k < 8 ? &T.xmat[1][0] + kMaxDof * k : &T.xpos[0][0];
+    };
+    static_assert(sizeof(T.crb) >= 4 * kMaxDof * 4 && sizeof(T.xmat) - 36 >= (kMC - 4) * kMaxDof * 4, "Y columns (capacity 6)");
+    static_assert(MC == kMC || (offsetof(Tile, crb) == offsetof(Tile, xmat) + sizeof(T.xmat) && sizeof(T.xmat) - 36 + sizeof(T.crb) >= 8 * kMaxDof * 4 &&
+                                sizeof(T.xpos) >= kMaxDof * 4 && MC - kYL == 3), "Y columns (capacity 12)");
+    float yx[3] = {0.f, 0.f, 0.f};
+    auto yput = [&](int k, float v) {
+      if (MC > kYL && k >= kYL) {
+#pragma unroll
+        for (int q = 0; q < 3; q++) yx[q] = k == kYL + q ? (is_dof ? v : 0.f) : yx[q];
+      } else if (is_dof) yrow(k)[lane] = v;
+    };
+    auto yget = [&](int k) -> float {
+      if (MC > kYL && k >= kYL) return k == kYL ? yx[0] : (k == kYL + 1 ? yx[1] : yx[2]);
+      return is_dof ? yrow(k)[lane] : 0.f;
+    };
 #pragma unroll 1
     for (int it = 0; it < 8; it++) {
       const float add = (act_lo ? D_lo : 0.f) + (act_hi ? D_hi : 0.f);
@@ -1292,10 +1334,10 @@ __device__ __forceinline__ V3 stage2(Ctx &c, float qfrc_act, bool integrate, boo
             todo &= todo - 1u;
             float jv = 0.f;
 #pragma unroll
-            for (int q = 0; q < kMC; q++) jv = k == q ? jk[q] : jv;
+            for (int q = 0; q < MC; q++) jv = k == q ? jk[q] : jv;
             const float2 r2 = bsolve<3>(c, rhs, jv);
             y0 = r2.x;
-            if (is_dof) yrow(k)[lane] = r2.y;
+            yput(k, r2.y);
             ymask |= 1u << k;
           } else y0 = bsolve<0>(c, rhs).x;
         }
@@ -1307,14 +1349,14 @@ __device__ __forceinline__ V3 stage2(Ctx &c, float qfrc_act, bool integrate, boo
           if (k1 >= 0) todo &= todo - 1u;
           float j0 = 0.f, j1 = 0.f;
 #pragma unroll
-          for (int q = 0; q < kMC; q++) { j0 = k0 == q ? jk[q] : j0; j1 = k1 == q ? jk[q] : j1; }
+          for (int q = 0; q < MC; q++) { j0 = k0 == q ? jk[q] : j0; j1 = k1 == q ? jk[q] : j1; }
           if (k1 >= 0) {
             const float2 r2 = bsolve<3>(c, j0, j1);
-            if (is_dof) { yrow(k0)[lane] = r2.x; yrow(k1)[lane] = r2.y; }
+            yput(k0, r2.x); yput(k1, r2.y);
             ymask |= (1u << k0) | (1u << k1);
           } else {
             const float yk = bsolve<0>(c, j0).x;
-            if (is_dof) yrow(k0)[lane] = yk;
+            yput(k0, yk);
             ymask |= 1u << k0;
           }
         }
@@ -1322,18 +1364,18 @@ __device__ __forceinline__ V3 stage2(Ctx &c, float qfrc_act, bool integrate, boo
       a = y0;
       if (am) {
         SYNC();
-        float srow[kMC], r = 0.f;
+        float srow[MC], r = 0.f;
 #pragma unroll
-        for (int j = 0; j < kMC; j++) srow[j] = lane == j ? 1.f : 0.f;   // (inactive rows stay identity: zero force)
+        for (int j = 0; j < MC; j++) srow[j] = lane == j ? 1.f : 0.f;   // (inactive rows stay identity: zero force)
 #pragma unroll
-        for (int i = 0; i < kMC; i++) {
+        for (int i = 0; i < MC; i++) {
           if ((am >> i) & 1u) {
             const float ri = wave_sum(jk[i] * y0);
             if (lane == i) r = -(ri - car);
 #pragma unroll
             for (int j = 0; j <= i; j++) {
               if ((am >> j) & 1u) {
-                const float sv = wave_sum(jk[i] * (is_dof ? yrow(j)[lane] : 0.f));
+                const float sv = wave_sum(jk[i] * yget(j));
                 if (lane == i) srow[j] = sv + (i == j ? __builtin_amdgcn_rcpf(fmaxf(cD, 1e-30f)) : 0.f);
                 if (lane == j && i != j) srow[i] = sv;
               }
@@ -1341,34 +1383,34 @@ __device__ __forceinline__ V3 stage2(Ctx &c, float qfrc_act, bool integrate, boo
           }
         }
 #pragma unroll
-        for (int k = 0; k < kMC; k++) {
+        for (int k = 0; k < MC; k++) {
           if ((am >> k) & 1u) {
             const float ipiv = 1.f / rl_f(srow[k], k), rk = rl_f(r, k);
-            float rowk[kMC];
+            float rowk[MC];
 #pragma unroll
-            for (int j = 0; j < kMC; j++) rowk[j] = rl_f(srow[j], k);
-            if (lane != k && lane < kMC) {
+            for (int j = 0; j < MC; j++) rowk[j] = rl_f(srow[j], k);
+            if (lane != k && lane < MC) {
               const float fac = srow[k] * ipiv;
 #pragma unroll
-              for (int j = 0; j < kMC; j++) srow[j] -= fac * rowk[j];
+              for (int j = 0; j < MC; j++) srow[j] -= fac * rowk[j];
               r -= fac * rk;
             }
           }
         }
         float diag = srow[0];
 #pragma unroll
-        for (int j = 1; j < kMC; j++) diag = lane == j ? srow[j] : diag;
-        cf = (lane < kMC && ((am >> lane) & 1u)) ? r / diag : 0.f;
+        for (int j = 1; j < MC; j++) diag = lane == j ? srow[j] : diag;
+        cf = (lane < MC && ((am >> lane) & 1u)) ? r / diag : 0.f;
 #pragma unroll
-        for (int k = 0; k < kMC; k++)
-          if ((am >> k) & 1u) a += (is_dof ? yrow(k)[lane] : 0.f) * rl_f(cf, k);
+        for (int k = 0; k < MC; k++)
+          if ((am >> k) & 1u) a += yget(k) * rl_f(cf, k);
       } else cf = 0.f;
       iters++;
       const bool n_lo = ex_lo && (a - ar_lo < 0.f);
       const bool n_hi = ex_hi && (-a - ar_hi < 0.f);
       bool n_c = false;
 #pragma unroll
-      for (int k = 0; k < kMC; k++) {
+      for (int k = 0; k < MC; k++) {
         if (k < nct) {
           const float jar = wave_sum(jk[k] * a);
           if (lane == k) n_c = jar - car < 0.f;
@@ -1385,7 +1427,7 @@ __device__ __forceinline__ V3 stage2(Ctx &c, float qfrc_act, bool integrate, boo
       float *o = g_dbgcf[c.dbg_env];
       const unsigned long long bc = __ballot(cact && lane < nct), bl = __ballot(act_lo), bh = __ballot(act_hi);
       if (lane == 0) { o[0] = (float)nct; o[1] = (float)(bc & 63ull); o[2] = (float)iters; o[3] = (float)(__popcll(bl) + __popcll(bh)); }
-      if (lane < kMC) {
+      if (lane < 6) {
         float *q = o + 4 + 12 * lane;
         q[0] = c.ct_dist; q[1] = c.ct_nx; q[2] = c.ct_ny; q[3] = c.ct_nz; q[4] = c.ct_px; q[5] = c.ct_py; q[6] = c.ct_pz; q[7] = (float)c.ct_pid; q[8] = cD; q[9] = car; q[10] = cf; q[11] = c.ct_incl;
       }
@@ -1394,7 +1436,7 @@ __device__ __forceinline__ V3 stage2(Ctx &c, float qfrc_act, bool integrate, boo
     if (act_lo) fc += D_lo * (ar_lo - a);
     if (act_hi) fc -= D_hi * (ar_hi + a);
 #pragma unroll
-    for (int k = 0; k < kMC; k++)
+    for (int k = 0; k < MC; k++)
       if (k < nct) fc += jk[k] * rl_f(cact ? cf : 0.f, k);
     c.pc = lane < nct ? ((c.ct_pid & 0xffff) | (cact ? 0 : 0x10000)) : -1;
     ae = want_euler ? bsolve<1>(c, f + fc).y : a;
@@ -1594,7 +1636,9 @@ __device__ __forceinline__ void load_lane_consts(Ctx &c) {
 // ------------------------------------------------------------------------------------------------ the step kernel
 // One launch = one dm_env step of every env.  mode: 0 = step (auto-reset envs that ended), 1 = reset all,
 // 2 = bare physics: `nphys` mj_steps with ctrl taken verbatim from act[B][nu] (no task, no outputs) - BASELINE config 2.
-__global__ __launch_bounds__(kWave, FFE_WAVES_PER_SIMD) void flight_step_kernel(const DevModel *__restrict__ Mp_, const TaskDev *__restrict__ Kp_, EnvState *__restrict__ states, const float *__restrict__ act,
+// MC = contacts the solver carries: instantiated for kMC (the default) and kMCX; the handle picks one at creation (launch_step).
+template <int MC>
+__global__ __launch_bounds__(kWave, FFE_WAVES_PER_SIMD) void flight_step_kernel(const DevModel *__restrict__ Mp_, const TaskDev *__restrict__ Kp_, typename StateOf<MC>::type *__restrict__ states, const float *__restrict__ act,
                                                               float *__restrict__ obs_out, float *__restrict__ reward_out,
                                                               float *__restrict__ discount_out, int *__restrict__ step_type_out, int batch, int mode, int nphys,
                                                               const int *__restrict__ order, int *__restrict__ cost,
@@ -1612,7 +1656,8 @@ __global__ __launch_bounds__(kWave, FFE_WAVES_PER_SIMD) void flight_step_kernel(
     mode = 1;
   }
   const int lane = threadIdx.x;
-  EnvState &S = states[env];
+  typename StateOf<MC>::type &SX = states[env];
+  EnvState &S = common(SX);
   Ctx c{Mp, T, lane, K.flags, 0.f, 0.f, {0.f, 0.f}, 0u, 0u, 0u, 0u, 0u};
 #ifdef FFE_DBGCF
   c.dbg_env = env;
@@ -1778,16 +1823,17 @@ __global__ __launch_bounds__(kWave, FFE_WAVES_PER_SIMD) void flight_step_kernel(
         if (e < kMaxDof * 6) { (&T.cdof[0][0])[e] = pre_c[k]; (&T.buf[0][0])[e] = pre_b[k]; }
       }
       c.f_smooth_nb = pre_f;
-      if (lane < kMC) {  // the contacts of that position stage
-        const float *o = S.ct_f[lane];
+      if (lane < MC) {  // the contacts of that position stage
+        const float *o = ct_f_row(SX, lane);
         c.ct_nx = o[0]; c.ct_ny = o[1]; c.ct_nz = o[2]; c.ct_px = o[3]; c.ct_py = o[4]; c.ct_pz = o[5]; c.ct_dist = o[6]; c.ct_incl = o[7]; c.ct_invw = o[8];
-        c.ct_l1 = S.ct_i[lane][0]; c.ct_l2 = S.ct_i[lane][1]; c.ct_pid = S.ct_i[lane][2];
+        const int *oi = ct_i_row(SX, lane);
+        c.ct_l1 = oi[0]; c.ct_l2 = oi[1]; c.ct_pid = oi[2];
       }
       c.nct = S.nct;
       if (lane < 9) T.xmat[0][lane] = pre_m;
       else if (lane < 12) T.sens[lane] = pre_m;  // CoM (see set_com)
       SYNC();
-    } else if (!DBG(c, DBG_SKIP_STAGE1) || s == 0) { stage1(c); flight_collide(c); STAMP(16); }
+    } else if (!DBG(c, DBG_SKIP_STAGE1) || s == 0) { stage1(c); flight_collide<MC>(c); STAMP(16); }
     if (lane < 6 && (do_reset || s > 0)) {
       // buffered velocity sensors at the thorax site: gyro = body-frame angular velocity, velocimeter = R^T v
       float add;
@@ -1800,7 +1846,7 @@ __global__ __launch_bounds__(kWave, FFE_WAVES_PER_SIMD) void flight_step_kernel(
     if (!do_reset) qa = actuation(c, lane < kMaxAct ? T.ctrl[lane] : 0.f);
     STAMP(12);  // sensor accumulation + actuation
     int it = 0;
-    const V3 acc = stage2(c, qa, !do_reset, !do_reset && !phys_only && !DBG(c, DBG_SKIP_GHOST), K.ghost_accel_z, lo_mask, hi_mask, in_lo, in_hi, it);
+    const V3 acc = stage2<MC>(c, qa, !do_reset, !do_reset && !phys_only && !DBG(c, DBG_SKIP_GHOST), K.ghost_accel_z, lo_mask, hi_mask, in_lo, in_hi, it);
     if (lane == 0) { T.park_i[4] += it; if (s < 4) T.park_i[5] |= min(c.nct, 15) << (4 * s); }
     if (lane < 3) T.sens[lane] += lane == 0 ? acc.x : (lane == 1 ? acc.y : acc.z);
     if (do_reset) break;
@@ -1888,10 +1934,11 @@ __global__ __launch_bounds__(kWave, FFE_WAVES_PER_SIMD) void flight_step_kernel(
   S.s1_f[lane] = c.f_smooth_nb;
   if (lane < 9) S.s1_misc[lane] = T.xmat[0][lane];
   if (lane == 0) { const V3 com_e = get_com(c); S.s1_misc[9] = com_e.x; S.s1_misc[10] = com_e.y; S.s1_misc[11] = com_e.z; S.s1_valid = 1; }
-  if (lane < kMC) {
-    float *o = S.ct_f[lane];
+  if (lane < MC) {
+    float *o = ct_f_row(SX, lane);
     o[0] = c.ct_nx; o[1] = c.ct_ny; o[2] = c.ct_nz; o[3] = c.ct_px; o[4] = c.ct_py; o[5] = c.ct_pz; o[6] = c.ct_dist; o[7] = c.ct_incl; o[8] = c.ct_invw;
-    S.ct_i[lane][0] = c.ct_l1; S.ct_i[lane][1] = c.ct_l2; S.ct_i[lane][2] = c.ct_pid;
+    int *oi = ct_i_row(SX, lane);
+    oi[0] = c.ct_l1; oi[1] = c.ct_l2; oi[2] = c.ct_pid;
   }
   if (lane < kNSD) { S.sd_n[lane][0] = c.sd_nx; S.sd_n[lane][1] = c.sd_ny; S.sd_n[lane][2] = c.sd_nz; S.sd_n[lane][3] = c.sd_t; S.sd_pid[lane] = c.sd_pid; }
   if (lane == 0) { S.nct = c.nct; S.sd_cnt = c.sd_cnt; S.ct_pad[0] = c.ct_ovf; S.ct_pad[1] = T.park_i[5]; }
@@ -1902,47 +1949,48 @@ __global__ __launch_bounds__(kWave, FFE_WAVES_PER_SIMD) void flight_step_kernel(
   TRACE_END(blockIdx.x, (unsigned long long)((unsigned)(iters & 0xff) | ((unsigned)(__popcll(lo_mask) + __popcll(hi_mask)) << 8) | ((unsigned)(tr_prev & 0xffff) << 16)) | ((unsigned long long)(T.park_i[5] & 0xffff) << 32), TRACE_HI(c));  // this step's solver iterations, active limits at its end, the sort key it was launched with, the contacts each substep used (4 bits each)
 }
 
-__global__ void init_states_kernel(EnvState *states, int *order, int *cost, int batch) {
+__global__ void init_states_kernel(void *states, size_t stride, int *order, int *cost, int batch) {
   int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= batch) return;
   EnvState z;
   memset(&z, 0, sizeof(z));
   z.needs_reset = 1; z.forced_traj = -1;
-  states[i] = z;
+  state_at(states, stride, i) = z;
+  if (stride > sizeof(EnvState)) memset(reinterpret_cast<char *>(&state_at(states, stride, i)) + sizeof(EnvState), 0, stride - sizeof(EnvState));
   order[i] = i;
   cost[i] = 0;
 }
 
-__global__ void get_state_kernel(const EnvState *states, double *qpos, double *qvel, int batch, int nq, int nv) {
+__global__ void get_state_kernel(void *states, size_t stride, double *qpos, double *qvel, int batch, int nq, int nv) {
   int env = blockIdx.x, lane = threadIdx.x;
   if (env >= batch) return;
-  const EnvState &S = states[env];
+  const EnvState &S = state_at(states, stride, env);
   if (lane < nq) qpos[(size_t)env * nq + lane] = lane < 3 ? S.rootpos[lane] : (double)S.qpos[lane];
   if (lane < nv) qvel[(size_t)env * nv + lane] = (double)S.qvel[lane];
 }
-__global__ void set_state_kernel(EnvState *states, const double *qpos, const double *qvel, int batch, int nq, int nv) {
+__global__ void set_state_kernel(void *states, size_t stride, const double *qpos, const double *qvel, int batch, int nq, int nv) {
   int env = blockIdx.x, lane = threadIdx.x;
   if (env >= batch) return;
-  EnvState &S = states[env];
+  EnvState &S = state_at(states, stride, env);
   if (lane < nq) { if (lane < 3) S.rootpos[lane] = qpos[(size_t)env * nq + lane]; else S.qpos[lane] = (float)qpos[(size_t)env * nq + lane]; }
   if (lane < nv) S.qvel[lane] = (float)qvel[(size_t)env * nv + lane];
   if (lane == 0) { S.lo_mask = 0; S.hi_mask = 0; S.in_lo_mask = 0; S.in_hi_mask = 0; S.s1_valid = 0; }
 }
-__global__ void get_task_state_kernel(const EnvState *states, int *ints, double *reals, int batch) {
+__global__ void get_task_state_kernel(void *states, size_t stride, int *ints, double *reals, int batch) {
   int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= batch) return;
-  const EnvState &S = states[i];
+  const EnvState &S = state_at(states, stride, i);
   int *o = ints + (size_t)i * 8;
-  o[0] = S.wb_step; o[1] = S.wb_freq_idx; o[2] = S.step_counter; o[3] = S.traj_idx; o[4] = S.needs_reset; o[5] = S.nactive; o[6] = S.solver_iters; o[7] = S.nct | ((S.ct_pad[0] & 255) << 8) | (S.ct_pad[1] << 16);  // contacts of the current position stage | some position stage of the last step met more contacts than the solver carries (the deepest kMC were kept) | contacts each of the last step's substeps used, 4 bits each
+  o[0] = S.wb_step; o[1] = S.wb_freq_idx; o[2] = S.step_counter; o[3] = S.traj_idx; o[4] = S.needs_reset; o[5] = S.nactive; o[6] = S.solver_iters; o[7] = S.nct | ((S.ct_pad[0] & 255) << 8) | (S.ct_pad[1] << 16);  // contacts of the current position stage | some position stage of the last step met more contacts than the solver carries (the deepest were kept: 6 or 12, the handle's capacity) | contacts each of the last step's substeps used, 4 bits each
   double *r = reals + (size_t)i * 8;
   r[0] = S.wb_ctrl_freq;
   for (int k = 0; k < 7; k++) r[1 + k] = S.ghost[k];
 }
-__global__ void force_next_kernel(EnvState *states, const int *traj, const double *phase, int batch) {
+__global__ void force_next_kernel(void *states, size_t stride, const int *traj, const double *phase, int batch) {
   int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= batch) return;
-  states[i].forced_traj = traj[i];
-  states[i].forced_phase = phase[i];
+  state_at(states, stride, i).forced_traj = traj[i];
+  state_at(states, stride, i).forced_phase = phase[i];
 }
 __global__ void test_quat_kernel(int op, const float *a, const float *b, float *out, int n) {
   int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -1970,7 +2018,9 @@ struct ffe_env {
   DevModel *dm_dev = nullptr;
   TaskDev *task_dev = nullptr;
   HostModel host;
-  EnvState *states = nullptr;
+  void *states = nullptr;       // EnvState records at `state_stride` bytes (EnvStateX for capacity 12)
+  size_t state_stride = sizeof(EnvState);
+  int contact_capacity = kMC;
   int *order = nullptr, *cost = nullptr;  // launch order of the envs and its sort keys (launch_order.hpp)
   bool timing = false; double timing_ms = 0.0;  // ffe_time_kernel: events around the step kernel alone
   unsigned char *arena = nullptr;
@@ -2076,6 +2126,10 @@ int ffe_create_flight(const void *model_blob, size_t blob_size, const ffe_flight
     if (t.wb_nfreq <= 0 || !t.wb_beat_freqs || !t.wb_tab_off || !t.wb_traj || !t.wb_phase || t.ntraj <= 0 || t.traj_len <= 0 || !t.ref_qpos || !t.ref_qvel)
       throw std::runtime_error("ffe_create_flight: incomplete task tables");
     if (t.future_steps + 1 > kMaxFuture) throw std::runtime_error("future_steps too large");
+    if (t.contact_capacity != 0 && t.contact_capacity != kMC && t.contact_capacity != kMCX)
+      throw std::runtime_error("ffe_create_flight: contact_capacity must be 6 or 12 (0 = 6), got " + std::to_string(t.contact_capacity));
+    h->contact_capacity = t.contact_capacity == kMCX ? kMCX : kMC;
+    h->state_stride = h->contact_capacity == kMCX ? sizeof(EnvStateX) : sizeof(EnvState);
     // per-trajectory row offsets (ref: trajectory_loaders.py:98-100 - trajectories of different lengths)
     std::vector<int> toff((size_t)t.ntraj + 1);
     for (int i = 0; i <= t.ntraj; i++) toff[i] = t.traj_off ? t.traj_off[i] : i * t.traj_len;
@@ -2117,13 +2171,13 @@ int ffe_create_flight(const void *model_blob, size_t blob_size, const ffe_flight
     h->host.nobs = K.obs_dim;
     h->dm_dev = upload(h.get(), &h->dm, 1);
     h->task_dev = upload(h.get(), &h->task, 1);
-    HIP_OK(hipMalloc(reinterpret_cast<void **>(&h->states), sizeof(EnvState) * (size_t)batch));
+    HIP_OK(hipMalloc(&h->states, h->state_stride * (size_t)batch));
     h->allocs.push_back(h->states);
     HIP_OK(hipMalloc(reinterpret_cast<void **>(&h->order), sizeof(int) * (size_t)batch));
     h->allocs.push_back(h->order);
     HIP_OK(hipMalloc(reinterpret_cast<void **>(&h->cost), sizeof(int) * (size_t)batch));
     h->allocs.push_back(h->cost);
-    hipLaunchKernelGGL(init_states_kernel, dim3((batch + 255) / 256), dim3(256), 0, 0, h->states, h->order, h->cost, batch);
+    hipLaunchKernelGGL(init_states_kernel, dim3((batch + 255) / 256), dim3(256), 0, 0, h->states, h->state_stride, h->order, h->cost, batch);
     HIP_OK(hipGetLastError());
     HIP_OK(hipDeviceSynchronize());
     HIP_OK(hipEventCreate(&h->ev0));
@@ -2192,8 +2246,12 @@ static int launch_step(ffe_handle h, const float *act, float *obs, float *rew, f
   FFE_BALL_DISPATCH(h, ffb::ball_launch(h->ball, act, obs, rew, disc, st, stream, mode, nphys, mask));
   if (mode != 2 && (!obs || !rew || !disc || !st || (mode == 0 && !act))) { h->err = "null device buffer"; return -1; }
   if (h->timing && hipEventRecord(h->ev0, static_cast<hipStream_t>(stream)) != hipSuccess) return -2;
-  hipLaunchKernelGGL(flight_step_kernel, dim3(h->batch), dim3(kWave), 0, static_cast<hipStream_t>(stream), h->dm_dev, h->task_dev, h->states, act, obs, rew,
-                     disc, st, h->batch, mode, nphys, h->order, h->cost, mask);
+  if (h->contact_capacity == kMCX)
+    hipLaunchKernelGGL(flight_step_kernel<kMCX>, dim3(h->batch), dim3(kWave), 0, static_cast<hipStream_t>(stream), h->dm_dev, h->task_dev, static_cast<EnvStateX *>(h->states), act,
+                       obs, rew, disc, st, h->batch, mode, nphys, h->order, h->cost, mask);
+  else
+    hipLaunchKernelGGL(flight_step_kernel<kMC>, dim3(h->batch), dim3(kWave), 0, static_cast<hipStream_t>(stream), h->dm_dev, h->task_dev, static_cast<EnvState *>(h->states), act, obs, rew,
+                       disc, st, h->batch, mode, nphys, h->order, h->cost, mask);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) { h->err = hipGetErrorString(e); return -2; }
   if (h->timing && hipEventRecord(h->ev1, static_cast<hipStream_t>(stream)) != hipSuccess) return -2;
@@ -2245,7 +2303,7 @@ int ffe_force_next_episode(ffe_handle h, const int32_t *traj, const double *phas
     // is synchronised once so that a second call cannot overwrite the staging buffers under a pending kernel
     HIP_OK(hipMemcpyAsync(h->forced_traj_dev, traj, sizeof(int) * h->batch, hipMemcpyHostToDevice, s));
     HIP_OK(hipMemcpyAsync(h->forced_phase_dev, phase, sizeof(double) * h->batch, hipMemcpyHostToDevice, s));
-    hipLaunchKernelGGL(force_next_kernel, dim3((h->batch + 255) / 256), dim3(256), 0, s, h->states, h->forced_traj_dev, h->forced_phase_dev, h->batch);
+    hipLaunchKernelGGL(force_next_kernel, dim3((h->batch + 255) / 256), dim3(256), 0, s, h->states, h->state_stride, h->forced_traj_dev, h->forced_phase_dev, h->batch);
     HIP_OK(hipGetLastError());
     HIP_OK(hipStreamSynchronize(s));
   } catch (const std::exception &e) { h->err = e.what(); return -1; }
@@ -2256,21 +2314,21 @@ int ffe_get_state(ffe_handle h, double *qpos, double *qvel, void *stream) {
   if (!h || !qpos || !qvel) return -1;
   DeviceGuard guard(h->device);
   FFE_BALL_DISPATCH(h, ffb::ball_get_state(h->ball, qpos, qvel, stream));
-  hipLaunchKernelGGL(get_state_kernel, dim3(h->batch), dim3(kWave), 0, static_cast<hipStream_t>(stream), h->states, qpos, qvel, h->batch, h->dm.nq, h->dm.nv);
+  hipLaunchKernelGGL(get_state_kernel, dim3(h->batch), dim3(kWave), 0, static_cast<hipStream_t>(stream), h->states, h->state_stride, qpos, qvel, h->batch, h->dm.nq, h->dm.nv);
   return hipGetLastError() == hipSuccess ? 0 : -2;
 }
 int ffe_set_state(ffe_handle h, const double *qpos, const double *qvel, void *stream) {
   if (!h || !qpos || !qvel) return -1;
   DeviceGuard guard(h->device);
   FFE_BALL_DISPATCH(h, ffb::ball_set_state(h->ball, qpos, qvel, stream));
-  hipLaunchKernelGGL(set_state_kernel, dim3(h->batch), dim3(kWave), 0, static_cast<hipStream_t>(stream), h->states, qpos, qvel, h->batch, h->dm.nq, h->dm.nv);
+  hipLaunchKernelGGL(set_state_kernel, dim3(h->batch), dim3(kWave), 0, static_cast<hipStream_t>(stream), h->states, h->state_stride, qpos, qvel, h->batch, h->dm.nq, h->dm.nv);
   return hipGetLastError() == hipSuccess ? 0 : -2;
 }
 int ffe_get_task_state(ffe_handle h, int32_t *ints, double *reals, void *stream) {
   if (!h || !ints || !reals) return -1;
   DeviceGuard guard(h->device);
   FFE_BALL_DISPATCH(h, ffb::ball_get_task_state(h->ball, ints, reals, stream));
-  hipLaunchKernelGGL(get_task_state_kernel, dim3((h->batch + 255) / 256), dim3(256), 0, static_cast<hipStream_t>(stream), h->states, ints, reals, h->batch);
+  hipLaunchKernelGGL(get_task_state_kernel, dim3((h->batch + 255) / 256), dim3(256), 0, static_cast<hipStream_t>(stream), h->states, h->state_stride, ints, reals, h->batch);
   return hipGetLastError() == hipSuccess ? 0 : -2;
 }
 

@@ -66,6 +66,10 @@ typedef struct {
    * canonical2real): actions arrive in [-1,1] and are mapped to lo + (a+1)/2 (hi-lo); optional clip to [-1,1] first */
   int32_t canonical_actions;
   int32_t clip_actions;
+  /* simultaneous self-contacts the solver carries per env: 0 or 6 = 6 (the default and the benchmarked configuration), 12 = the
+   * larger step kernel (same physics up to six contacts, rows for up to twelve); anything else fails ffe_create_flight.  Beyond the
+   * capacity the deepest are kept and the env is flagged (ffe_get_task_state, int 7 bits 8-15) */
+  int32_t contact_capacity;
 } ffe_flight_task;
 
 /* Task inputs of fly_envs.walk_on_ball (vnl_ray/fly_envs.py:125-157).  The arena (ball position / radius / density,
@@ -147,8 +151,8 @@ int ffe_set_state(ffe_handle h, const double *qpos_dev, const double *qvel_dev, 
 /* task-side state per env: {wbpg_step, wbpg_freq_idx, step_counter, traj_idx, needs_reset, n_active_limits,
  * solver_iters, contacts} int32[B][8] and {wbpg_ctrl_freq, ghost_pos[3], ghost_quat[4]} float64[B][8].
  * flight handles, int 7 (the fly's own contacts, for the parity tests): bits 0-7 contacts of the current position stage; bits
- * 8-15 non-zero when a position stage of the last control step met more contacts than the solver carries (6; the deepest are
- * kept); bits 16-31 the contacts each of the last step's four substeps used, 4 bits each.
+ * 8-15 non-zero when a position stage of the last control step met more contacts than the solver carries (the
+ * handle's contact_capacity, 6 or 12; the deepest are kept); bits 16-31 the contacts each of the last step's four substeps used, 4 bits each.
  * walk_on_ball handles: {contact history lo, hi, step_counter, fly-fly contacts, needs_reset, contacts, solver_iters, overflow
  * (sticky over the episode; bit 0 more than 16 contacts, bit 1 more than 48 constraint rows, bit 2 more than 24 columns in one
  * block of M)} - the contact history holds, 4 bits per substep for the first 16 substeps of the last control step, the number of
