@@ -15,6 +15,7 @@ SYMBOLS = [
     "ffe_test_quat", "ffe_last_error", "ffe_version", "ffe_create_walk_on_ball", "ffe_get_act", "ffe_set_act",
     "ffe_nstep_create", "ffe_nstep_observe", "ffe_nstep_buffers", "ffe_nstep_destroy", "ffe_nstep_last_error",
     "ffe_pack_timestep", "ffe_episode_stats",
+    "ffe_get_validity", "ffe_validity_stats", "ffe_nstep_create_tracked", "ffe_nstep_observe_flagged", "ffe_nstep_taint_buffer",
 ]
 
 
@@ -98,6 +99,13 @@ def lib():
     L.ffe_pack_timestep.restype = C.c_int
     L.ffe_episode_stats.argtypes = [ip, fp, fp, vp, vp, vp, C.c_int, vp]
     L.ffe_episode_stats.restype = C.c_int
+    L.ffe_get_validity.argtypes = [vp, ip, vp]
+    L.ffe_validity_stats.argtypes = [ip, ip, vp, C.c_int, vp]
+    L.ffe_nstep_create_tracked.argtypes = L.ffe_nstep_create.argtypes
+    L.ffe_nstep_observe_flagged.argtypes = [vp, fp, ip, fp, fp, fp, ip, C.c_int, vp]
+    L.ffe_nstep_taint_buffer.argtypes = [vp, C.POINTER(C.c_void_p)]
+    for s in ("ffe_get_validity", "ffe_validity_stats", "ffe_nstep_create_tracked", "ffe_nstep_observe_flagged", "ffe_nstep_taint_buffer"):
+        getattr(L, s).restype = C.c_int
     L.ffe_nstep_last_error.restype = C.c_char_p
     L.ffe_nstep_last_error.argtypes = [vp]
     for s in ("ffe_nstep_create", "ffe_nstep_observe", "ffe_nstep_buffers", "ffe_nstep_destroy"):

@@ -14,6 +14,26 @@ import time
 from . import _capi
 
 
+def _step_bits_arg(step_bits, batch_size: int, device):
+    """(tensor, stride in ints) of the `step_bits` a tracked writer is fed: the int32 [B, 4] buffer of `env.validity()` (its column 0
+    is read in place) or an int32 [B] tensor - that buffer's first column, or a contiguous one.  Checked here because the C ABI takes
+    a raw device pointer."""
+    import torch
+
+    x = step_bits
+    if hasattr(x, "step_bits") and not isinstance(x, torch.Tensor):  # the Validity tuple itself
+        x = x.step_bits
+    if not isinstance(x, torch.Tensor) or x.dtype != torch.int32:
+        raise TypeError("step_bits must be an int32 tensor: env.validity().step_bits or the [B, 4] validity buffer")
+    if not x.is_cuda or x.device != device:
+        raise ValueError(f"step_bits must live on the writer's device {device}")
+    if x.dim() == 2 and tuple(x.shape) == (batch_size, 4) and x.is_contiguous():
+        return x, 4
+    if x.dim() == 1 and x.shape[0] == batch_size and x.stride(0) >= 1:
+        return x, int(x.stride(0))
+    raise ValueError(f"step_bits must have shape ({batch_size},) or be the contiguous ({batch_size}, 4) validity buffer")
+
+
 class NStepTransitionWriter:
     """Device-resident batched n-step transition adder (`ffe_nstep_*`, flybody_amd/csrc/nstep.hip): what the reference's
     actors do one env at a time through `acme.adders.reverb.NStepTransitionAdder(n_step=50, discount=...)`
@@ -21,25 +41,48 @@ class NStepTransitionWriter:
 
     `observe(action, timestep)` takes the action that was applied and the `TimeStep` the env returned for it (FIRST rows start
     an episode; their action is ignored).  `transitions()` returns views (obs, action, n_step_return, discount, next_obs) of the
-    slots written so far; the learner applies one more factor of `discount` to the bootstrap value, as with acme."""
+    slots written so far; the learner applies one more factor of `discount` to the bootstrap value, as with acme.
+
+    `track_validity=True` adds a taint column to the ring: `observe(..., step_bits=env.validity().step_bits)` (or the `[B, 4]`
+    validity buffer) is then required, and `transitions(with_taint=True)` returns a sixth tensor, uint8 [N], 1 where the transition
+    spans an env-step whose physics was truncated - or the step after one, because a launch's last position stage drives the first
+    substep of the next (include/flybody_env.h, ffe_nstep_observe_flagged).  Off (the default), everything is as without it."""
 
     def __init__(self, batch_size: int, obs_dim: int, act_dim: int, *, n_step: int = 50, discount: float = 0.99, capacity: int = 1 << 20,
-                 device: int = 0):
+                 device: int = 0, track_validity: bool = False):
+        if not isinstance(track_validity, bool):
+            raise TypeError(f"track_validity must be a bool, got {track_validity!r}")
+        for name, v in (("batch_size", batch_size), ("obs_dim", obs_dim), ("act_dim", act_dim), ("n_step", n_step), ("capacity", capacity)):
+            if isinstance(v, bool) or int(v) != v or v <= 0:
+                raise ValueError(f"{name} must be a positive integer, got {v!r}")
         import torch
 
+        self.track_validity = track_validity
         self._t, self._L = torch, _capi.lib()
         self.batch_size, self.obs_dim, self.act_dim, self.n_step, self.discount, self.capacity = batch_size, obs_dim, act_dim, n_step, discount, capacity
         self.device = torch.device("cuda", device)
         h = C.c_void_p()
-        if self._L.ffe_nstep_create(batch_size, obs_dim, act_dim, n_step, float(discount), capacity, device, C.byref(h)) != 0:
+        create = self._L.ffe_nstep_create_tracked if track_validity else self._L.ffe_nstep_create
+        if create(batch_size, obs_dim, act_dim, n_step, float(discount), capacity, device, C.byref(h)) != 0:
             raise RuntimeError("ffe_nstep_create: " + self._L.ffe_nstep_last_error(None).decode())
         self._h = h
         ptr = [C.c_void_p() for _ in range(6)]
         assert self._L.ffe_nstep_buffers(self._h, *[C.byref(p) for p in ptr]) == 0
         self._ptr = [p.value for p in ptr]
+        self._taint_ptr = None
+        if track_validity:
+            tp = C.c_void_p()
+            if self._L.ffe_nstep_taint_buffer(self._h, C.byref(tp)) != 0:
+                raise RuntimeError("ffe_nstep_taint_buffer: " + self._L.ffe_nstep_last_error(self._h).decode())
+            self._taint_ptr = tp.value
 
-    def observe(self, action, timestep, flat_observation):
+    def observe(self, action, timestep, flat_observation, step_bits=None):
         t = self._t
+        if self.track_validity and step_bits is None:
+            raise ValueError("a writer with track_validity=True needs step_bits (env.validity()) with every observe()")
+        if not self.track_validity and step_bits is not None:
+            raise ValueError("step_bits given to a writer created without track_validity=True")
+        bits = _step_bits_arg(step_bits, self.batch_size, self.device) if self.track_validity else None
         st = timestep.step_type
         # the C ABI takes raw device pointers: everything it will read is checked here (a float64 reward, a strided view or a host
         # tensor would otherwise be read as garbage, or fault)
@@ -52,8 +95,12 @@ class NStepTransitionWriter:
         assert ok(st, t.int32, (B,)) and ok(timestep.reward, t.float32, (B,)) and ok(timestep.discount, t.float32, (B,)), \
             "step_type int32 [B], reward / discount float32 [B], contiguous on the writer's device"
         stream = C.c_void_p(t.cuda.current_stream(self.device).cuda_stream)
-        rc = self._L.ffe_nstep_observe(self._h, action.data_ptr(), st.data_ptr(), timestep.reward.data_ptr(), timestep.discount.data_ptr(),
-                                       flat_observation.data_ptr(), stream)
+        if bits is not None:
+            rc = self._L.ffe_nstep_observe_flagged(self._h, action.data_ptr(), st.data_ptr(), timestep.reward.data_ptr(), timestep.discount.data_ptr(),
+                                                   flat_observation.data_ptr(), bits[0].data_ptr(), bits[1], stream)
+        else:
+            rc = self._L.ffe_nstep_observe(self._h, action.data_ptr(), st.data_ptr(), timestep.reward.data_ptr(), timestep.discount.data_ptr(),
+                                           flat_observation.data_ptr(), stream)
         if rc != 0:
             raise RuntimeError("ffe_nstep_observe: " + self._L.ffe_nstep_last_error(self._h).decode())
 
@@ -71,8 +118,8 @@ class NStepTransitionWriter:
     def _view(self, ptr, shape, dtype):
         """torch tensor over library-owned device memory (no copy), via the CUDA array interface."""
         t = self._t
-        itemsize = {t.float32: 4, t.int64: 8}[dtype]
-        typestr = {t.float32: "<f4", t.int64: "<i8"}[dtype]
+        itemsize = {t.float32: 4, t.int64: 8, t.uint8: 1}[dtype]
+        typestr = {t.float32: "<f4", t.int64: "<i8", t.uint8: "|u1"}[dtype]
 
         class _Mem:
             __cuda_array_interface__ = {"shape": tuple(shape), "typestr": typestr, "data": (int(ptr), False), "version": 2, "strides": None}
@@ -80,16 +127,21 @@ class NStepTransitionWriter:
         del itemsize
         return t.as_tensor(_Mem(), device=self.device)
 
-    def transitions(self):
+    def transitions(self, with_taint: bool = False):
         """(obs [N,O], action [N,A], n_step_return [N], discount [N], next_obs [N,O]) views of the N = min(written, capacity) filled slots.
         Slots are claimed before their rows are stored: a reader must be stream-ordered after the last `observe` (this method
-        synchronises the device through `num_written`); after the ring has wrapped the slots are in no particular age order."""
+        synchronises the device through `num_written`); after the ring has wrapped the slots are in no particular age order.
+        `with_taint` (tracked writers only) appends the uint8 [N] taint column."""
+        if with_taint and not self.track_validity:
+            raise ValueError("transitions(with_taint=True) needs a writer created with track_validity=True")
         t, n = self._t, min(self.num_written(), self.capacity)
         o = self._view(self._ptr[0], (self.capacity, self.obs_dim), t.float32)[:n]
         a = self._view(self._ptr[1], (self.capacity, self.act_dim), t.float32)[:n]
         r = self._view(self._ptr[2], (self.capacity,), t.float32)[:n]
         d = self._view(self._ptr[3], (self.capacity,), t.float32)[:n]
         o2 = self._view(self._ptr[4], (self.capacity, self.obs_dim), t.float32)[:n]
+        if with_taint:
+            return o, a, r, d, o2, self._view(self._taint_ptr, (self.capacity,), t.uint8)[:n]
         return o, a, r, d, o2
 
     def close(self):
@@ -105,11 +157,23 @@ class NStepTransitionWriter:
 
 
 class BatchedActorLoop:
-    def __init__(self, env, policy, adder: NStepTransitionWriter | None = None):
+    def __init__(self, env, policy, adder: NStepTransitionWriter | None = None, track_validity: bool = False):
         """`adder`: optional `NStepTransitionWriter`; fed as the reference's actor feeds its adder (`observe_first` on FIRST,
-        `observe(action, next_timestep)` otherwise)."""
+        `observe(action, next_timestep)` otherwise).
+
+        `track_validity`: every iteration also reads `env.validity()`, hands its `step_bits` to the adder (which must then have
+        been created with `track_validity=True` as well) and accumulates batch totals on the device; `run()` then also reports
+        `flagged_env_steps` (MID / LAST env-steps whose physics was truncated), `flagged_episodes` (finished episodes with at least
+        one) and `flagged_steps_per_flagged_episode`.  Off (the default): the launches and result keys are those without it."""
         import torch
 
+        if not isinstance(track_validity, bool):
+            raise TypeError(f"track_validity must be a bool, got {track_validity!r}")
+        if adder is not None and bool(getattr(adder, "track_validity", False)) != track_validity:
+            raise ValueError("the loop and its adder must agree on track_validity")
+        if track_validity and not hasattr(env, "validity"):
+            raise ValueError("track_validity needs an env with validity()")
+        self.track_validity = track_validity
         self._t, self.env, self.policy, self.adder = torch, env, policy, adder
         B, dev = env.batch_size, env.device
         self._ret = torch.zeros(B, device=dev)
@@ -117,6 +181,7 @@ class BatchedActorLoop:
         # episode statistics accumulate on the device: nothing in the loop reads a value back, so launches stay queued ahead
         self._tot = torch.zeros(2, dtype=torch.int64, device=dev)  # finished episodes, sum of their lengths
         self._sum_ret = torch.zeros(1, dtype=torch.float64, device=dev)
+        self._vtot = torch.zeros(3, dtype=torch.int64, device=dev) if track_validity else None  # ffe_validity_stats totals
         self._L = _capi.lib()
 
     @property
@@ -129,7 +194,9 @@ class BatchedActorLoop:
             action = self.policy(self.env.flat_observation)
         action = action.contiguous()
         ts = self.env.step(action)
-        if self.adder is not None:
+        if self.track_validity:
+            self._observe_validity(action, ts)
+        elif self.adder is not None:
             self.adder.observe(action, ts, self.env.flat_observation)
         # per-env return / length and the totals of finished episodes: one fused launch (ffe_episode_stats)
         with t.cuda.device(self.env.device):  # (ffe_episode_stats launches on the current device: make it the env's)
@@ -137,6 +204,24 @@ class BatchedActorLoop:
                                            self._sum_ret.data_ptr(), self.env.batch_size, C.c_void_p(t.cuda.current_stream(self.env.device).cuda_stream))
         if rc != 0:
             raise RuntimeError("ffe_episode_stats failed")
+
+    def _observe_validity(self, action, ts):
+        """validity of the timestep just produced -> the adder's taint column and the batch totals (two or three small launches)"""
+        t = self._t
+        v = self.env.validity()
+        if self.adder is not None:
+            self.adder.observe(action, ts, self.env.flat_observation, step_bits=v.step_bits)
+        with t.cuda.device(self.env.device):
+            rc = self._L.ffe_validity_stats(ts.step_type.data_ptr(), self.env.validity_buffer.data_ptr(), self._vtot.data_ptr(), self.env.batch_size,
+                                            C.c_void_p(t.cuda.current_stream(self.env.device).cuda_stream))
+        if rc != 0:
+            raise RuntimeError("ffe_validity_stats failed")
+
+    def _validity_result(self) -> dict:
+        if not self.track_validity:
+            return {}
+        steps, eps, total = (int(x) for x in self._vtot.tolist())
+        return {"flagged_env_steps": steps, "flagged_episodes": eps, "flagged_steps_per_flagged_episode": total / eps if eps else float("nan")}
 
     def run(self, num_steps: int, graph: bool = False) -> dict:
         """Steps every env `num_steps` times (episodes roll over through the env's auto-reset).  With `graph` one iteration
@@ -165,7 +250,7 @@ class BatchedActorLoop:
             n = int(self._tot[0].item())
             return {"episodes": n, "episode_return": float(self._sum_ret.item()) / n if n else float("nan"),
                     "episode_length": float(self._tot[1].item()) / n if n else float("nan"),
-                    "steps_per_second": num_steps * self.env.batch_size / wall, "capacity_flagged_envs": self._flagged()}
+                    "steps_per_second": num_steps * self.env.batch_size / wall, "capacity_flagged_envs": self._flagged(), **self._validity_result()}
         start = time.perf_counter()
         for _ in range(num_steps):
             self._iteration()
@@ -174,15 +259,18 @@ class BatchedActorLoop:
         n = int(self._tot[0].item())
         return {"episodes": n, "episode_return": float(self._sum_ret.item()) / n if n else float("nan"),
                 "episode_length": float(self._tot[1].item()) / n if n else float("nan"),
-                "steps_per_second": num_steps * self.env.batch_size / wall, "capacity_flagged_envs": self._flagged()}
+                "steps_per_second": num_steps * self.env.batch_size / wall, "capacity_flagged_envs": self._flagged(), **self._validity_result()}
 
     def _begin(self):
         """reset + `observe_first`, statistics zeroed (on torch's current stream)"""
         t = self._t
         ts = self.env.reset()
         self._ret.zero_(); self._len.zero_(); self._tot.zero_(); self._sum_ret.zero_()
+        if self.track_validity:
+            self._vtot.zero_()
         if self.adder is not None:
-            self.adder.observe(t.zeros(self.env.batch_size, self.adder.act_dim, device=self.env.device), ts, self.env.flat_observation)
+            kw = {"step_bits": self.env.validity().step_bits} if self.track_validity else {}
+            self.adder.observe(t.zeros(self.env.batch_size, self.adder.act_dim, device=self.env.device), ts, self.env.flat_observation, **kw)
 
     def _flagged(self) -> int:
         """Envs whose step met more simultaneous contacts / constraint rows than the kernel carries (`ffe_get_task_state` int 7: the
@@ -190,7 +278,7 @@ class BatchedActorLoop:
         if not hasattr(self.env, "get_task_state"):
             return 0
         w = self.env.get_task_state()[0][:, 7]
-        is_flight = hasattr(self.env, "ghost_accel_z")
+        is_flight = self.env.task_kind == "flight_imitation"
         return int((((w >> 8) & 255) != 0).sum()) if is_flight else int((w != 0).sum())
 
 
@@ -201,9 +289,9 @@ class GroupedActorLoop:
     another, as the reference's actor processes do not (`train_dmpo_ray.py:432-452`); one group's launch drains while the next group's
     fills the device.  The policy is shared (its weights are read-only here)."""
 
-    def __init__(self, groups, policy, adders=None):
+    def __init__(self, groups, policy, adders=None, track_validity: bool = False):
         self.groups = groups
-        self.loops = [BatchedActorLoop(e, policy, adders[g] if adders is not None else None) for g, e in enumerate(groups.envs)]
+        self.loops = [BatchedActorLoop(e, policy, adders[g] if adders is not None else None, track_validity) for g, e in enumerate(groups.envs)]
 
     def run(self, num_steps: int, graph: bool = False) -> dict:
         """`graph`: every group's iteration is captured once into a HIP graph on the group's stream and replayed (two dozen launches per
@@ -241,4 +329,11 @@ class GroupedActorLoop:
         ret = sum(float(lp._sum_ret.item()) for lp in self.loops)
         length = sum(int(lp._tot[1].item()) for lp in self.loops)
         return {"episodes": n, "episode_return": ret / n if n else float("nan"), "episode_length": length / n if n else float("nan"),
-                "steps_per_second": num_steps * self.groups.batch_size / wall, "capacity_flagged_envs": sum(lp._flagged() for lp in self.loops)}
+                "steps_per_second": num_steps * self.groups.batch_size / wall, "capacity_flagged_envs": sum(lp._flagged() for lp in self.loops),
+                **self._validity_result()}
+
+    def _validity_result(self) -> dict:
+        if not self.loops or not self.loops[0].track_validity:
+            return {}
+        steps, eps, total = (sum(int(lp._vtot[k].item()) for lp in self.loops) for k in range(3))
+        return {"flagged_env_steps": steps, "flagged_episodes": eps, "flagged_steps_per_flagged_episode": total / eps if eps else float("nan")}

@@ -24,6 +24,10 @@ FLIGHT_BLOB = os.path.join(_ASSETS, "fly_flight.ffmb")
 BALL_BLOB = os.path.join(_ASSETS, "fly_ball.ffmb")
 
 
+# `env.validity()`: four int32 [B] views of one [B, 4] device buffer (include/flybody_env.h, ffe_get_validity)
+Validity = collections.namedtuple("Validity", ["step_bits", "episode_flagged_steps", "episode_bits", "episode_steps"])
+
+
 def _f64(a):
     return np.ascontiguousarray(a, dtype=np.float64)
 
@@ -59,6 +63,8 @@ class BatchedFlyEnv:
     and overwrites on the next call: a consumer that keeps the previous timestep (acme's `observe(action, next_timestep)`
     adders do) must copy it, or construct the env with `double_buffer=True`, which alternates two buffer sets so that the
     timestep returned by call *k* stays valid until call *k + 2*."""
+
+    task_kind = "flight_imitation"
 
     def __init__(self, wbpg, ref_qpos, ref_qvel=None, *, batch_size: int, device: int = 0, seed: int = 0, env_id_base: int = 0,
                  future_steps: int = 5, time_limit: float = 0.6, terminal_com_dist: float = 2.0, pad_first_obs: bool = False,
@@ -280,6 +286,26 @@ class BatchedFlyEnv:
         self._check(self._L.ffe_get_task_state(self._h, ints.data_ptr(), reals.data_ptr(), self._stream()))
         return ints, reals
 
+    def validity(self) -> Validity:
+        """Whether the physics behind the current timestep was truncated (`ffe_get_validity`): `step_bits` of the launch that produced
+        it (flight: bit 0 more contacts than `contact_capacity`, bit 1 the solver's iteration cap; walk_on_ball: the overflow bits of
+        task-state int 7, this launch alone), and per episode the flagged control steps, the OR of their bits and the control steps so
+        far.  The three episode fields are 0 on a FIRST row; read after a LAST row they are that episode's totals.
+
+        The tensors are views of one int32 [B, 4] buffer the env owns (`validity_buffer`), overwritten by the next call.  One launch on
+        the current stream, no synchronisation: usable under HIP-graph capture."""
+        t = self._torch
+        if getattr(self, "_validity", None) is None:
+            with t.cuda.device(self.device):
+                self._validity = t.zeros(self.batch_size, 4, dtype=t.int32, device=self.device)
+        self._check(self._L.ffe_get_validity(self._h, self._validity.data_ptr(), self._stream()))
+        return Validity(*self._validity.unbind(1))
+
+    @property
+    def validity_buffer(self):
+        """The int32 [B, 4] buffer `validity()` fills (None before its first call)."""
+        return getattr(self, "_validity", None)
+
     def time_kernel(self, action, iters: int) -> float:
         """Mean milliseconds of the step kernel alone over `iters` launches (HIP events immediately around it)."""
         ms = C.c_float()
@@ -300,6 +326,8 @@ class BatchedBallEnv(BatchedFlyEnv):
     ball, 10 physics substeps (contacts, elliptic friction cones, noslip, adhesion, filtered actuators) per control step.
     Same dm_env surface and hooks as `BatchedFlyEnv`; `get_state` returns qpos[B, 106] = ball quaternion + 102 hinges and
     qvel[B, 105] = ball angular velocity + hinges."""
+
+    task_kind = "walk_on_ball"
 
     def __init__(self, *, batch_size: int, device: int = 0, time_limit: float = 2.0, control_timestep: float = 2e-3,
                  pad_first_obs: bool = False, physics_flags: int = 0, canonical_actions: bool = False, clip_actions: bool = False,

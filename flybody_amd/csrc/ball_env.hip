@@ -57,12 +57,14 @@ struct alignas(16) BState {
   float q[NDP], v[NDP], act[64];
   float ballq[4], ballw[4];
   float qacc_ws[NDP], wsc[NL][3];  // warm start of the constraint solver: last limit force per dof, last contact force per link
-  int step_counter, needs_reset, overflow, iters, ncon, have_ws, nself, pad1;
+  int step_counter, needs_reset, overflow, iters, ncon, have_ws, nself;
+  int step_bits;  // validity (ffe_get_validity): the overflow bits of the last launch alone (`overflow` is their OR over the episode)
   unsigned con_hist[2];  // active (inside includemargin) contacts of each of the control step's first 16 substeps, 4 bits each: parity tooling
   unsigned det_hist[2];  // detected (inside margin) contacts of its first 12 substeps, 5 bits each
   float sd_n[NSD][4];    // separating-direction cache of the convex pairs (convex_collide)
   unsigned short sd_pid[NSD];
-  int sd_cnt, ws_n, pad2[2];
+  int sd_cnt, ws_n;
+  int ep_flagged, pad2;  // control steps of the current episode whose launch raised an overflow bit
   float ws_f[NC];        // forces of the fly-fly contacts of the last substep, by pair id (warm start)
   unsigned short ws_pid[NC];
 };
@@ -2031,6 +2033,9 @@ __global__ __launch_bounds__(64, 2) void ball_step_kernel(const BallModel *__res
     cost[env] = min(255, iters + 10 * (c.nc + c.nsc));
     if (do_reset) S.overflow = 0; else S.overflow |= c.overflow;  // sticky over the episode: 1 contacts > 10, 2 constraint rows > 32, 4 rows of one block > 12
     S.have_ws = do_reset ? 0 : c.have_ws;
+    // validity: bare physics reports its own launch and leaves the episode's count alone; a FIRST row starts it at zero
+    S.step_bits = c.overflow;
+    if (!phys_only) S.ep_flagged = do_reset ? 0 : S.ep_flagged + (c.overflow ? 1 : 0);
   }
 #ifdef FFB_STAMPS
   BSTAMP(20);  // prologue + state store
@@ -2136,6 +2141,14 @@ __global__ void ball_task_state_kernel(const BState *states, int *ints, double *
   reals[(size_t)i * 8] = (double)((unsigned long long)S.det_hist[0] | ((unsigned long long)S.det_hist[1] << 32));  // (60 bits used: exact up to 10 substeps)
 }
 
+// ffe_get_validity: {step_bits, episode_flagged_steps, episode_bits, episode_steps} per env
+__global__ void ball_validity_kernel(const BState *states, int *info, int batch) {
+  int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= batch) return;
+  const BState &S = states[i];
+  *reinterpret_cast<int4 *>(info + (size_t)i * 4) = make_int4(S.step_bits, S.ep_flagged, S.overflow, S.step_counter);
+}
+
 // ================================================================================================ host side
 #define HIPB_OK(expr)                                                                               \
   do {                                                                                              \
@@ -2236,6 +2249,10 @@ void ball_set_act(BallEnv *e, const double *act, void *stream) {
 }
 void ball_get_task_state(BallEnv *e, int32_t *ints, double *reals, void *stream) {
   hipLaunchKernelGGL(ball_task_state_kernel, dim3((e->batch + 63) / 64), dim3(64), 0, (hipStream_t)stream, e->states, ints, reals, e->batch);
+  HIPB_OK(hipGetLastError());
+}
+void ball_get_validity(BallEnv *e, int32_t *info, void *stream) {
+  hipLaunchKernelGGL(ball_validity_kernel, dim3((e->batch + 63) / 64), dim3(64), 0, (hipStream_t)stream, e->states, info, e->batch);
   HIPB_OK(hipGetLastError());
 }
 #ifdef FFE_TRACE

@@ -26,6 +26,7 @@ void ball_set_state(BallEnv *e, const double *qpos, const double *qvel, void *st
 void ball_get_act(BallEnv *e, double *act, void *stream);
 void ball_set_act(BallEnv *e, const double *act, void *stream);
 void ball_get_task_state(BallEnv *e, int32_t *ints, double *reals, void *stream);
+void ball_get_validity(BallEnv *e, int32_t *info, void *stream);  // int32[B][4], 16-byte aligned
 float ball_time_steps(BallEnv *e, const float *act, float *obs, float *rew, float *disc, int32_t *st, int iters, void *stream);
 float ball_time_kernel(BallEnv *e, const float *act, float *obs, float *rew, float *disc, int32_t *st, int iters, void *stream);
 

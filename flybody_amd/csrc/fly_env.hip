@@ -35,6 +35,7 @@ namespace ffe {
 
 constexpr int kMC = 6;   // contacts per env the solver carries (deepest kept; more is flagged): the default capacity, and the record layout below
 constexpr int kMCX = 12;  // the selectable larger capacity (ffe_flight_task::contact_capacity): a second instantiation of the step kernel
+constexpr int kCapExit = 0x100;  // Ctx::ct_ovf: bits 0-7 contacts beyond the capacity (flight_collide), this bit the solver's iteration cap
 constexpr int kNSD = 16;  // convex pairs whose separating direction is remembered from substep to substep (a wing near the abdomen brings six
                          // ellipsoid - cylinder pairs at once, whose search from scratch is the most expensive thing a wave can do: 25 - 100 us)
 
@@ -63,6 +64,10 @@ struct alignas(64) EnvState {
   float sd_n[kNSD][4];  // direction | the capsule's axis parameter of a capsule - convex pair
   int sd_pid[kNSD];
   int nct, sd_cnt, ct_pad[2];
+  // validity (ffe_get_validity): what went wrong in the launch that produced the current timestep (bit 0 a position stage met more
+  // contacts than the capacity, bit 1 the constraint solve left its active-set loop on the iteration cap), the control steps of
+  // the current episode with such a launch, and the OR of their bits.  A launch that returns FIRST zeroes the two episode fields.
+  int v_step_bits, v_ep_flagged, v_ep_bits, v_pad;
 };
 // The record of a capacity-12 handle: the same record with contacts 6 .. 11 of the carried-over position stage behind it, so that
 // everything that is not the step kernel addresses either kind as an EnvState at a stride (state_at).
@@ -1421,6 +1426,7 @@ __device__ __forceinline__ V3 stage2(Ctx &c, float qfrc_act, bool integrate, boo
       act_lo = n_lo; act_hi = n_hi; cact = n_c;
       lim_changed = __ballot(lch) != 0ULL;
       if (__ballot(changed) == 0ULL) break;
+      if (it == 7) c.ct_ovf |= kCapExit;  // left on the cap with a changed set that got no re-solve (validity bit 1; never part of int 7)
     }
 #ifdef FFE_DBGCF
     if (c.dbg_env < 64) {
@@ -1811,6 +1817,7 @@ __global__ __launch_bounds__(kWave, FFE_WAVES_PER_SIMD) void flight_step_kernel(
   if (lane == 0) {
     T.park_d[0] = wb_cf; T.park_d[1] = __longlong_as_double((long long)episode);
     T.park_i[0] = wb_step; T.park_i[1] = wb_idx; T.park_i[2] = step_counter; T.park_i[3] = traj_idx; T.park_i[4] = 0; T.park_i[5] = 0;
+    T.park_i[6] = S.v_ep_flagged; T.park_i[7] = S.v_ep_bits;
   }
   STAMP(11);  // prologue: state load, WBPG, action mixing (or episode reset)
   const int nst = do_reset ? 1 : nsub;
@@ -1941,7 +1948,13 @@ __global__ __launch_bounds__(kWave, FFE_WAVES_PER_SIMD) void flight_step_kernel(
     oi[0] = c.ct_l1; oi[1] = c.ct_l2; oi[2] = c.ct_pid;
   }
   if (lane < kNSD) { S.sd_n[lane][0] = c.sd_nx; S.sd_n[lane][1] = c.sd_ny; S.sd_n[lane][2] = c.sd_nz; S.sd_n[lane][3] = c.sd_t; S.sd_pid[lane] = c.sd_pid; }
-  if (lane == 0) { S.nct = c.nct; S.sd_cnt = c.sd_cnt; S.ct_pad[0] = c.ct_ovf; S.ct_pad[1] = T.park_i[5]; }
+  if (lane == 0) {
+    S.nct = c.nct; S.sd_cnt = c.sd_cnt; S.ct_pad[0] = c.ct_ovf & 255; S.ct_pad[1] = T.park_i[5];
+    // validity: bare physics reports its own launch and leaves the episode's counts alone; a FIRST row starts them at zero
+    const int vb = ((c.ct_ovf & 255) ? 1 : 0) | ((c.ct_ovf & kCapExit) ? 2 : 0);
+    S.v_step_bits = vb;
+    if (!phys_only) { S.v_ep_flagged = do_reset ? 0 : T.park_i[6] + (vb ? 1 : 0); S.v_ep_bits = do_reset ? 0 : (T.park_i[7] | vb); }
+  }
 #ifdef FFE_STAMPS
   STAMP(10);
   if (lane == 0) for (int k = 0; k < 20; k++) atomicAdd(&g_stamps[k], c.st_acc[k]);
@@ -1985,6 +1998,13 @@ __global__ void get_task_state_kernel(void *states, size_t stride, int *ints, do
   double *r = reals + (size_t)i * 8;
   r[0] = S.wb_ctrl_freq;
   for (int k = 0; k < 7; k++) r[1 + k] = S.ghost[k];
+}
+// ffe_get_validity: {step_bits, episode_flagged_steps, episode_bits, episode_steps} per env
+__global__ void get_validity_kernel(void *states, size_t stride, int *info, int batch) {
+  int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= batch) return;
+  const EnvState &S = state_at(states, stride, i);
+  *reinterpret_cast<int4 *>(info + (size_t)i * 4) = make_int4(S.v_step_bits, S.v_ep_flagged, S.v_ep_bits, S.step_counter);
 }
 __global__ void force_next_kernel(void *states, size_t stride, const int *traj, const double *phase, int batch) {
   int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -2322,6 +2342,14 @@ int ffe_set_state(ffe_handle h, const double *qpos, const double *qvel, void *st
   DeviceGuard guard(h->device);
   FFE_BALL_DISPATCH(h, ffb::ball_set_state(h->ball, qpos, qvel, stream));
   hipLaunchKernelGGL(set_state_kernel, dim3(h->batch), dim3(kWave), 0, static_cast<hipStream_t>(stream), h->states, h->state_stride, qpos, qvel, h->batch, h->dm.nq, h->dm.nv);
+  return hipGetLastError() == hipSuccess ? 0 : -2;
+}
+int ffe_get_validity(ffe_handle h, int32_t *info, void *stream) {
+  if (!h) return -1;
+  if (!info || (reinterpret_cast<uintptr_t>(info) & 15)) { h->err = "ffe_get_validity: info_dev must be a 16-byte aligned device buffer"; return -1; }
+  DeviceGuard guard(h->device);
+  FFE_BALL_DISPATCH(h, ffb::ball_get_validity(h->ball, info, stream));
+  hipLaunchKernelGGL(get_validity_kernel, dim3((h->batch + 255) / 256), dim3(256), 0, static_cast<hipStream_t>(stream), h->states, h->state_stride, info, h->batch);
   return hipGetLastError() == hipSuccess ? 0 : -2;
 }
 int ffe_get_task_state(ffe_handle h, int32_t *ints, double *reals, void *stream) {

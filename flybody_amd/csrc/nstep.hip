@@ -12,6 +12,11 @@
 //   * on LAST the remaining, shorter, transitions are flushed as well (acme's _write_last), all ending in o_{t+1}: an episode of
 //     T < n steps leaves 2 T - 1 transitions, one of T >= n steps leaves T + n - 1;
 //   * FIRST starts a new episode: the ring is cleared and o_0 stored.
+// Validity tracking (ffe_nstep_create_tracked + ffe_nstep_observe_flagged): every call brings the env's step_bits (ffe_get_validity).
+// The position stage a step kernel launch ends with drives the first substep of the next launch, so a flag raised in launch k can
+// reach the physics of step k + 1: the entry appended at step t is marked e_t = (bits_t | bits_{t-1}) != 0 (the bits of a FIRST call
+// count as bits_{t-1} of the episode's first entry), and a transition is tainted when any entry it spans is marked.  For the
+// transitions that start at held entries 0 .. len - 1 and end at the newest that is a suffix OR of the marks: one ballot per env.
 // One wavefront per env: lanes move the observation / action rows (coalesced), lane-parallel products give R and D.
 // Transitions land in a device-resident replay ring (slot = running counter mod capacity); nothing touches the host.
 #include <hip/hip_runtime.h>
@@ -37,6 +42,10 @@ struct Dev {
   // replay ring
   float *t_obs, *t_act, *t_ret, *t_disc, *t_next;
   unsigned long long *written;            // transitions written so far (monotone)
+  // validity tracking (null on a writer created without it)
+  unsigned char *r_mark;                  // [B][n] mark e of each held entry
+  int *prev_bits;                         // [B] step_bits passed with the previous call
+  unsigned char *t_taint;                 // [capacity] taint of each replay slot
 };
 
 // Writes the `total` transitions that start at ring entries 0 .. total - 1 (0 = oldest of `len` held entries) and all end in
@@ -112,9 +121,11 @@ __device__ __forceinline__ void emit_all(const Dev &D, int env, int lane, int fi
 // (the waves' counts are summed through LDS): a device-scope atomic on a single address is served by the memory side, one after
 // the other across all eight XCDs, and one per env (8 192 per call) cost more than everything else in this kernel together.
 constexpr int kEnvsPerBlock = 16;
+// TRACK: the writer keeps the taint column; `step_bits` (null = all zero) is read at `bits_stride` ints per env.
+template <bool TRACK>
 __global__ __launch_bounds__(64 * kEnvsPerBlock) void nstep_observe_kernel(Dev D, const float *__restrict__ action, const int *__restrict__ step_type,
                                                                            const float *__restrict__ reward, const float *__restrict__ discount,
-                                                                           const float *__restrict__ obs) {
+                                                                           const float *__restrict__ obs, const int *__restrict__ step_bits, int bits_stride) {
   __shared__ int s_total[kEnvsPerBlock];
   __shared__ unsigned long long s_base;
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -161,9 +172,15 @@ __global__ __launch_bounds__(64 * kEnvsPerBlock) void nstep_observe_kernel(Dev D
   __syncthreads();
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
   if (!live) return;
+  int bits = 0, mark_new = 0;
+  if (TRACK) {
+    bits = step_bits ? step_bits[(size_t)env * bits_stride] : 0;
+    mark_new = (bits | D.prev_bits[env]) != 0;
+  }
   if (first_step) {  // observe_first: new episode
     for (int k = lane; k < O; k += 64) lo[k] = o_next[k];
     if (lane == 0) { D.head[env] = 0; D.count[env] = 0; }
+    if (TRACK && lane == 0) D.prev_bits[env] = bits;
     return;
   }
   if (total > 0) {
@@ -171,7 +188,26 @@ __global__ __launch_bounds__(64 * kEnvsPerBlock) void nstep_observe_kernel(Dev D
     for (int w = 0; w < wave; w++) base += (unsigned long long)s_total[w];
     // transition 0 starts at the oldest held entry (the n-step transition once the ring is full), the rest (LAST only) start later
     emit_all(D, env, lane, first, total, cnt_new, o_next, base, rew_l, disc_l, in_lanes);
+    if (TRACK) {
+      // taint of the transition that starts at held entry s = OR of the marks of entries s .. cnt_new - 1 (the entry appended by
+      // this call takes its mark from the arguments, as its reward does)
+      const unsigned char *rm = D.r_mark + (size_t)env * n;
+      const unsigned long long cap = (unsigned long long)D.capacity;
+      if (in_lanes) {
+        bool m = false;
+        if (lane < cnt_new) { const int e = (first + lane) % n; m = e == head ? mark_new != 0 : rm[e] != 0; }
+        const unsigned long long marks = __ballot(m);
+        if (lane < total) D.t_taint[(base + lane) % cap] = (marks >> lane) != 0ull ? 1 : 0;
+      } else {
+        for (int s0 = lane; s0 < total; s0 += 64) {
+          int any = 0;
+          for (int i = s0; i < cnt_new; i++) { const int e = (first + i) % n; any |= e == head ? mark_new : (int)rm[e]; }
+          D.t_taint[(base + s0) % cap] = (unsigned char)any;
+        }
+      }
+    }
   }
+  if (TRACK && lane == 0) { D.r_mark[(size_t)env * n + head] = (unsigned char)mark_new; D.prev_bits[env] = bits; }
   for (int k = lane; k < O; k += 64) lo[k] = o_next[k];
   if (lane == 0) { D.head[env] = head_new; D.count[env] = cnt_new; }
 }
@@ -211,10 +247,28 @@ __global__ void episode_stats_kernel(const int *__restrict__ st, const float *__
   }
 }
 
+// batch totals of the validity records (ffe_get_validity), nothing kept per env - the step kernels keep the running counts:
+// {env-steps with step_bits != 0 on MID / LAST rows, finished episodes with flagged steps, sum of their flagged steps}
+__global__ void validity_stats_kernel(const int *__restrict__ st, const int *__restrict__ info, long long *__restrict__ tot, int batch) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  int steps = 0, eps = 0, sum = 0;
+  if (i < batch) {
+    const int s = st[i];
+    const int4 v = *reinterpret_cast<const int4 *>(info + (size_t)i * 4);
+    if (s != FFE_STEP_FIRST && v.x != 0) steps = 1;
+    if (s == FFE_STEP_LAST && v.y > 0) { eps = 1; sum = v.y; }
+  }
+  for (int o = 32; o > 0; o >>= 1) { steps += __shfl_xor(steps, o); eps += __shfl_xor(eps, o); sum += __shfl_xor(sum, o); }
+  if ((threadIdx.x & 63) == 0) {
+    if (steps) atomicAdd((unsigned long long *)&tot[0], (unsigned long long)steps);
+    if (eps) { atomicAdd((unsigned long long *)&tot[1], (unsigned long long)eps); atomicAdd((unsigned long long *)&tot[2], (unsigned long long)sum); }
+  }
+}
+
 struct Handle {
   Dev d{};
   int device = 0;
-  void *allocs[16] = {nullptr};
+  void *allocs[20] = {nullptr};
   int nalloc = 0;
   std::string err;
 };
@@ -231,7 +285,7 @@ static thread_local std::string g_nerr;
 
 extern "C" {
 
-int ffe_nstep_create(int batch, int obs_dim, int act_dim, int n_step, float discount, long long capacity, int device, ffe_nstep_handle *out) {
+static int nstep_create(int batch, int obs_dim, int act_dim, int n_step, float discount, long long capacity, int device, bool tracked, ffe_nstep_handle *out) {
   if (!out) return -1;
   *out = nullptr;
   if (batch <= 0 || obs_dim <= 0 || act_dim <= 0 || n_step <= 0 || capacity <= 0) { g_nerr = "ffe_nstep_create: bad arguments"; return -1; }
@@ -257,6 +311,7 @@ int ffe_nstep_create(int batch, int obs_dim, int act_dim, int n_step, float disc
   D.last_obs = (float *)alloc(B * O * 4); D.head = (int *)alloc(B * 4); D.count = (int *)alloc(B * 4);
   D.t_obs = (float *)alloc(C * O * 4); D.t_act = (float *)alloc(C * A * 4); D.t_ret = (float *)alloc(C * 4); D.t_disc = (float *)alloc(C * 4);
   D.t_next = (float *)alloc(C * O * 4); D.written = (unsigned long long *)alloc(8);
+  if (tracked) { D.r_mark = (unsigned char *)alloc(B * n); D.prev_bits = (int *)alloc(B * 4); D.t_taint = (unsigned char *)alloc(C); }
   (void)hipDeviceSynchronize();
   if (prev >= 0 && prev != device) (void)hipSetDevice(prev);
   if (!ok) {
@@ -266,6 +321,13 @@ int ffe_nstep_create(int batch, int obs_dim, int act_dim, int n_step, float disc
   }
   *out = p.release();
   return 0;
+}
+
+int ffe_nstep_create(int batch, int obs_dim, int act_dim, int n_step, float discount, long long capacity, int device, ffe_nstep_handle *out) {
+  return nstep_create(batch, obs_dim, act_dim, n_step, discount, capacity, device, false, out);
+}
+int ffe_nstep_create_tracked(int batch, int obs_dim, int act_dim, int n_step, float discount, long long capacity, int device, ffe_nstep_handle *out) {
+  return nstep_create(batch, obs_dim, act_dim, n_step, discount, capacity, device, true, out);
 }
 
 int ffe_nstep_destroy(ffe_nstep_handle p) {
@@ -279,17 +341,43 @@ int ffe_nstep_destroy(ffe_nstep_handle p) {
   return 0;
 }
 
-int ffe_nstep_observe(ffe_nstep_handle p, const float *action_dev, const int32_t *step_type_dev, const float *reward_dev, const float *discount_dev,
-                      const float *obs_dev, void *stream) {
+// a tracked writer always runs the tracking kernel: fed through ffe_nstep_observe its bits are zero
+static int nstep_observe(ffe_nstep_handle p, const float *action_dev, const int32_t *step_type_dev, const float *reward_dev, const float *discount_dev,
+                         const float *obs_dev, const int32_t *step_bits_dev, int stride_ints, void *stream) {
   if (!p || !step_type_dev || !reward_dev || !discount_dev || !obs_dev || !action_dev) return -1;
   int prev = -1;
   (void)hipGetDevice(&prev);
   if (prev != p->h.device) (void)hipSetDevice(p->h.device);
-  hipLaunchKernelGGL(ffn::nstep_observe_kernel, dim3((p->h.d.batch + ffn::kEnvsPerBlock - 1) / ffn::kEnvsPerBlock), dim3(64 * ffn::kEnvsPerBlock), 0, static_cast<hipStream_t>(stream), p->h.d, action_dev, step_type_dev,
-                     reward_dev, discount_dev, obs_dev);
+  const dim3 grid((p->h.d.batch + ffn::kEnvsPerBlock - 1) / ffn::kEnvsPerBlock), block(64 * ffn::kEnvsPerBlock);
+  if (p->h.d.t_taint)
+    hipLaunchKernelGGL(ffn::nstep_observe_kernel<true>, grid, block, 0, static_cast<hipStream_t>(stream), p->h.d, action_dev, step_type_dev, reward_dev, discount_dev,
+                       obs_dev, step_bits_dev, stride_ints);
+  else
+    hipLaunchKernelGGL(ffn::nstep_observe_kernel<false>, grid, block, 0, static_cast<hipStream_t>(stream), p->h.d, action_dev, step_type_dev, reward_dev, discount_dev,
+                       obs_dev, static_cast<const int32_t *>(nullptr), 0);
   const hipError_t e = hipGetLastError();
   if (prev >= 0 && prev != p->h.device) (void)hipSetDevice(prev);
   if (e != hipSuccess) { p->h.err = hipGetErrorString(e); return -2; }
+  return 0;
+}
+
+int ffe_nstep_observe(ffe_nstep_handle p, const float *action_dev, const int32_t *step_type_dev, const float *reward_dev, const float *discount_dev,
+                      const float *obs_dev, void *stream) {
+  return nstep_observe(p, action_dev, step_type_dev, reward_dev, discount_dev, obs_dev, nullptr, 0, stream);
+}
+
+int ffe_nstep_observe_flagged(ffe_nstep_handle p, const float *action_dev, const int32_t *step_type_dev, const float *reward_dev, const float *discount_dev,
+                              const float *obs_dev, const int32_t *step_bits_dev, int stride_ints, void *stream) {
+  if (!p) return -1;
+  if (!p->h.d.t_taint) { p->h.err = "ffe_nstep_observe_flagged: the writer was created without validity tracking (ffe_nstep_create_tracked)"; return -1; }
+  if (!step_bits_dev || stride_ints < 1) { p->h.err = "ffe_nstep_observe_flagged: null step_bits_dev or stride_ints < 1"; return -1; }
+  return nstep_observe(p, action_dev, step_type_dev, reward_dev, discount_dev, obs_dev, step_bits_dev, stride_ints, stream);
+}
+
+int ffe_nstep_taint_buffer(ffe_nstep_handle p, uint8_t **taint) {
+  if (!p || !taint) return -1;
+  if (!p->h.d.t_taint) { p->h.err = "ffe_nstep_taint_buffer: the writer was created without validity tracking (ffe_nstep_create_tracked)"; return -1; }
+  *taint = p->h.d.t_taint;
   return 0;
 }
 
@@ -321,6 +409,12 @@ int ffe_episode_stats(const int32_t *step_type_dev, const float *reward_dev, flo
   if (!step_type_dev || !reward_dev || !episode_return_dev || !episode_length_dev || !totals_i64_dev || !total_return_dev || batch <= 0) return -1;
   hipLaunchKernelGGL(ffn::episode_stats_kernel, dim3((batch + 255) / 256), dim3(256), 0, static_cast<hipStream_t>(stream), step_type_dev, reward_dev,
                      episode_return_dev, episode_length_dev, totals_i64_dev, total_return_dev, batch);
+  return hipGetLastError() == hipSuccess ? 0 : -2;
+}
+
+int ffe_validity_stats(const int32_t *step_type_dev, const int32_t *info_dev, long long *totals_dev, int batch, void *stream) {
+  if (!step_type_dev || !info_dev || !totals_dev || batch <= 0 || (reinterpret_cast<uintptr_t>(info_dev) & 15)) return -1;
+  hipLaunchKernelGGL(ffn::validity_stats_kernel, dim3((batch + 255) / 256), dim3(256), 0, static_cast<hipStream_t>(stream), step_type_dev, info_dev, totals_dev, batch);
   return hipGetLastError() == hipSuccess ? 0 : -2;
 }
 

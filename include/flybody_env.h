@@ -160,6 +160,25 @@ int ffe_set_state(ffe_handle h, const double *qpos_dev, const double *qvel_dev, 
  * DETECTED inside their margin (adhesion is shared over those); the other reals are zero */
 int ffe_get_task_state(ffe_handle h, int32_t *ints_dev, double *reals_dev, void *stream);
 
+/* Validity of the physics behind each env's current timestep.  Stands in for what MuJoCo tells a dm_control user through its
+ * warnings (mjWARN_CONTACTFULL / mjWARN_CNSTRFULL in physics.data.warning, surfaced by dm_control's Physics.check_invalid_state,
+ * mujoco/engine.py): the step kernels carry a fixed number of simultaneous contacts / constraint rows, keep the deepest when a
+ * state needs more, and go on - that env-step ran physics the reference would not have run.  info_dev is int32[B][4], 16-byte
+ * aligned:
+ *   0 step_bits              what went wrong in the launch that produced the current timestep (0 = nothing).  flight: bit 0 a
+ *                            position stage of the launch met more contacts than the handle's contact_capacity (exactly int 7 bits
+ *                            8-15 != 0 of the task state), bit 1 the constraint solve left its active-set loop on the iteration
+ *                            cap (8) with a changed set that got no re-solve.  walk_on_ball: this launch's overflow bits 0-2 as
+ *                            documented for int 7 of the task state
+ *   1 episode_flagged_steps  control steps of the current episode with step_bits != 0
+ *   2 episode_bits           OR of step_bits over those steps (walk_on_ball: the sticky int 7)
+ *   3 episode_steps          control steps of the current episode so far (the task state's step_counter)
+ * The call that returns FIRST (auto-reset, ffe_reset, a masked row of ffe_reset_envs) sets fields 1-3 to 0; its step_bits describe
+ * the start state's position stage and are not counted, so the values read after a LAST timestep are that episode's totals.
+ * ffe_physics_step updates step_bits only (walk_on_ball: and ORs into the sticky int 7, as before); ffe_set_state touches none.
+ * One small launch on `stream`; the step kernels maintain the fields in the state record they write anyway. */
+int ffe_get_validity(ffe_handle h, int32_t *info_dev, void *stream);
+
 /* name and duration helper for bench.py's roofline: launches `iters` steps bracketed by HIP events on `stream`
  * and returns the mean milliseconds per ffe_step launch (synchronises the stream). */
 int ffe_time_steps(ffe_handle h, const float *act_dev, float *obs_dev, float *reward_dev, float *discount_dev,
@@ -196,6 +215,19 @@ int ffe_nstep_observe(ffe_nstep_handle h, const float *action_dev, const int32_t
  * next_obs[capacity][O], and the running count of transitions written */
 int ffe_nstep_buffers(ffe_nstep_handle h, float **obs, float **act, float **ret, float **disc, float **next_obs, unsigned long long **written_dev);
 int ffe_nstep_destroy(ffe_nstep_handle h);
+/* Validity tracking of the writer - no counterpart in acme's adder, which sees MuJoCo's unbounded contact list: the replay ring
+ * gains a taint column so that a learner can drop or down-weight transitions that span truncated physics.  A writer made by the
+ * _tracked constructor (same arguments as the plain one) is fed step_bits with every call: element i at step_bits_dev[i * stride_ints],
+ * so that column 0 of the ffe_get_validity buffer is passed as it lies with stride_ints = 4.  The position stage a launch ends with
+ * is carried into the first substep of the next launch, so a flag raised at step t can reach the physics of step t + 1: the entry
+ * appended at step t is marked when bits_t | bits_(t-1) != 0 (the bits passed with a FIRST row count as bits_(t-1) of the episode's
+ * first entry), and a transition is tainted (taint[slot] = 1, written with the row) when any entry it spans is marked.  Fed through
+ * the plain observe call, a tracked writer takes the bits as zero; the flagged call on an untracked writer, and the taint buffer of
+ * one, fail with a text. */
+int ffe_nstep_create_tracked(int batch, int obs_dim, int act_dim, int n_step, float discount, long long capacity, int device, ffe_nstep_handle *out);
+int ffe_nstep_observe_flagged(ffe_nstep_handle h, const float *action_dev, const int32_t *step_type_dev, const float *reward_dev,
+                              const float *discount_dev, const float *obs_dev, const int32_t *step_bits_dev, int stride_ints, void *stream);
+int ffe_nstep_taint_buffer(ffe_nstep_handle h, uint8_t **taint /* [capacity] */);
 /* The unit the per-step gather to a central learner moves (the reference has no collective - its actors
  * push transitions through Reverb, agents/ray_distributed_dmpo.py:106-115): one fused launch packs (obs, reward, discount,
  * step_type) of the current device into packed_dev[B][obs_dim + 3] (flybody_amd/distributed.py:TimestepGather). */
@@ -208,6 +240,12 @@ int ffe_pack_timestep(const float *obs_dev, const float *reward_dev, const float
  * the finished env's counters restart.  One launch per step, nothing read back. */
 int ffe_episode_stats(const int32_t *step_type_dev, const float *reward_dev, float *episode_return_dev, long long *episode_length_dev,
                       long long *totals_i64_dev, double *total_return_dev, int batch, void *stream);
+/* batch totals of the validity records, accumulated on the device like the episode statistics above (the reference logs nothing of
+ * the kind: MuJoCo's warning counters stay inside each actor process): totals_dev int64[3] += {env-steps with step_bits != 0 on
+ * MID / LAST rows, episodes finished in this call (LAST rows) with episode_flagged_steps > 0, sum of their episode_flagged_steps}.
+ * info_dev is the int32[B][4] buffer of ffe_get_validity for the same timestep as step_type_dev; no per-env running state is needed,
+ * the step kernels keep it. */
+int ffe_validity_stats(const int32_t *step_type_dev, const int32_t *info_dev, long long *totals_dev, int batch, void *stream);
 const char *ffe_nstep_last_error(ffe_nstep_handle h);
 
 #ifdef __cplusplus

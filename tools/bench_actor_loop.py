@@ -1,7 +1,8 @@
 """End-to-end actor throughput on one GPU: env.step + policy network + n-step transition writer, all device-resident
 (`flybody_amd/actor_loop.py`; what the reference does with one OS process per env: agents/ray_distributed_dmpo.py:401-440,514-521).
 The policy is the reference's DMPO policy shape (LayerNormMLP 512-512-256 + a diagonal Gaussian head, train_dmpo_ray.py),
-random weights, sampled actions in the canonical [-1, 1] spec (clipped).    python tools/bench_actor_loop.py [steps]"""
+random weights, sampled actions in the canonical [-1, 1] spec (clipped).  The last case is the writer case with validity
+tracking on (env.validity() + taint column + flagged totals every step).    python tools/bench_actor_loop.py [steps]"""
 import json, os, sys
 sys.path.insert(0, os.path.join(os.path.dirname(__file__), ".."))
 import torch
@@ -32,7 +33,9 @@ class Policy(torch.nn.Module):
 
 torch.manual_seed(0)
 out = {}
-for name in ("env_only_fixed_action", "env_plus_policy", "env_plus_policy_plus_nstep_writer", "env_plus_bf16_policy_plus_nstep_writer"):
+
+
+def single_loop(name):
     env = BatchedFlyEnv(tables, rq, rv, batch_size=B, seed=0, canonical_actions=True, clip_actions=True)
     pol = Policy(env.spec.obs_dim, env.spec.action_dim).cuda()
     fixed = (torch.rand(B, env.spec.action_dim, device="cuda") * 2 - 1).contiguous()
@@ -44,18 +47,25 @@ for name in ("env_only_fixed_action", "env_plus_policy", "env_plus_policy_plus_n
                 return pol(o).float()
     else:
         policy = pol
-    adder = NStepTransitionWriter(B, env.spec.obs_dim, env.spec.action_dim, n_step=50, discount=0.99, capacity=1 << 20) if name.endswith("writer") else None
-    loop = BatchedActorLoop(env, policy, adder)
+    track = name.endswith("validity")
+    adder = NStepTransitionWriter(B, env.spec.obs_dim, env.spec.action_dim, n_step=50, discount=0.99, capacity=1 << 20, track_validity=track) if "writer" in name else None
+    loop = BatchedActorLoop(env, policy, adder, track_validity=track)
     loop.run(30)
     r = loop.run(steps)
     out[name] = {"env_steps_per_s": round(r["steps_per_second"], 1), "ms_per_step": round(1e3 * B / r["steps_per_second"], 4), "episodes": r["episodes"],
                  "mean_episode_length": round(r["episode_length"], 1)}
+    if track:
+        out[name].update({k: r[k] for k in ("flagged_env_steps", "flagged_episodes", "flagged_steps_per_flagged_episode")})
     rg = loop.run(steps, graph=True)  # the same iteration captured once into a HIP graph and replayed
     out[name]["hip_graph"] = {"env_steps_per_s": round(rg["steps_per_second"], 1), "ms_per_step": round(1e3 * B / rg["steps_per_second"], 4),
                               "episodes": rg["episodes"]}
     if adder is not None:
         out[name]["transitions_written"] = adder.num_written(); adder.close()
     env.close()
+
+
+for name in ("env_only_fixed_action", "env_plus_policy", "env_plus_policy_plus_nstep_writer", "env_plus_bf16_policy_plus_nstep_writer"):
+    single_loop(name)
 # the same actor as two asynchronous groups of B / 2 envs (flybody_amd/groups.py, GroupedActorLoop): policy, env step and writer of a group
 # on that group's stream, nobody waits for the other group
 from flybody_amd import fly_envs
@@ -76,4 +86,6 @@ for G in (2,):
     out[f"env_plus_policy_plus_nstep_writer_{G}_async_groups"]["hip_graph"] = {"env_steps_per_s": round(rg["steps_per_second"], 1), "ms_per_step": round(1e3 * B / rg["steps_per_second"], 4), "episodes": rg["episodes"]}
     for a in adders: a.close()
     grp.close()
+# last, so that the cases above see the random streams they always saw: the writer case with validity tracking on
+single_loop("env_plus_policy_plus_nstep_writer_tracking_validity")
 print(json.dumps(out))

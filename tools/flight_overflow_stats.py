@@ -1,6 +1,7 @@
 """flight_imitation at the benchmark's workload (B = 8192, actions uniform over the raw action spec) with contact_capacity 6 and 12:
 env-steps in which a position stage met more contacts than the solver carries (ffe_get_task_state int 7 bits 8-15), envs flagged at
-the end of the run, the largest number of contacts a substep used, and env-steps/s of both capacities through ffe_time_steps, measured
+the end of the run, the largest number of contacts a substep used, per finished episode (env.validity(), read on LAST rows) the share
+with at least one flagged control step and the mean number of flagged steps in those, and env-steps/s of both capacities through ffe_time_steps, measured
 alternately in one process (median of `rounds` blocks each).
     python tools/flight_overflow_stats.py [batch] [steps] [rounds] [timed launches per block]"""
 import json
@@ -26,13 +27,24 @@ for cap, env in envs.items():
     env.reset()
     g = torch.Generator(device="cuda").manual_seed(1234)
     flagged_steps, most = 0, 0
+    episodes, flagged_eps, flagged_in_eps, cap_exits = 0, 0, 0, 0
     for k in range(steps):
-        env.step((lo + (hi - lo) * torch.rand(B, len(spec.minimum), device="cuda", generator=g)).contiguous())
+        ts = env.step((lo + (hi - lo) * torch.rand(B, len(spec.minimum), device="cuda", generator=g)).contiguous())
         w = env.get_task_state()[0][:, 7]
         flagged_steps += int((((w >> 8) & 255) != 0).sum())
         most = max(most, int(torch.stack([(w >> (16 + 4 * q)) & 15 for q in range(4)]).max()))
+        v = env.validity()
+        last = ts.step_type == 2
+        episodes += int(last.sum())
+        flagged_eps += int((last & (v.episode_flagged_steps > 0)).sum())
+        flagged_in_eps += int(v.episode_flagged_steps[last].sum())
+        cap_exits += int(((v.step_bits & 2) != 0).sum())
     out[f"capacity_{cap}"] = {"env_steps_flagged": flagged_steps, "flagged_fraction": flagged_steps / (B * steps),
-                              "envs_flagged_at_the_end": int((((w >> 8) & 255) != 0).sum()), "most_contacts_in_a_substep": most}
+                              "envs_flagged_at_the_end": int((((w >> 8) & 255) != 0).sum()), "most_contacts_in_a_substep": most,
+                              "finished_episodes": episodes, "episodes_with_a_flagged_step": flagged_eps,
+                              "share_of_episodes_flagged": flagged_eps / episodes if episodes else float("nan"),
+                              "mean_flagged_steps_in_flagged_episodes": flagged_in_eps / flagged_eps if flagged_eps else float("nan"),
+                              "launches_that_left_the_solver_on_its_iteration_cap": cap_exits}
 g = torch.Generator(device="cuda").manual_seed(99)
 a = (lo + (hi - lo) * torch.rand(B, len(spec.minimum), device="cuda", generator=g)).contiguous()
 rate = {6: [], 12: []}
