@@ -55,6 +55,9 @@ class NStepTransitionWriter:
         for name, v in (("batch_size", batch_size), ("obs_dim", obs_dim), ("act_dim", act_dim), ("n_step", n_step), ("capacity", capacity)):
             if isinstance(v, bool) or int(v) != v or v <= 0:
                 raise ValueError(f"{name} must be a positive integer, got {v!r}")
+        if capacity < batch_size * n_step:
+            raise ValueError(f"capacity {capacity} is below batch_size * n_step = {batch_size * n_step}, the rows one observe() can write "
+                             "(every env on LAST with a full ring): they would share slots of the replay ring")
         import torch
 
         self.track_validity = track_validity

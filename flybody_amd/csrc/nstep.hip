@@ -18,7 +18,9 @@
 // count as bits_{t-1} of the episode's first entry), and a transition is tainted when any entry it spans is marked.  For the
 // transitions that start at held entries 0 .. len - 1 and end at the newest that is a suffix OR of the marks: one ballot per env.
 // One wavefront per env: lanes move the observation / action rows (coalesced), lane-parallel products give R and D.
-// Transitions land in a device-resident replay ring (slot = running counter mod capacity); nothing touches the host.
+// Transitions land in a device-resident replay ring (slot = running counter mod capacity); nothing touches the host.  capacity >=
+// batch x n_step (refused otherwise), so the rows of one launch never share a slot; launches are stream-ordered, so after W rows the
+// ring holds exactly the last min(W, capacity) claimed ones, each of them whole.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -289,6 +291,13 @@ static int nstep_create(int batch, int obs_dim, int act_dim, int n_step, float d
   if (!out) return -1;
   *out = nullptr;
   if (batch <= 0 || obs_dim <= 0 || act_dim <= 0 || n_step <= 0 || capacity <= 0) { g_nerr = "ffe_nstep_create: bad arguments"; return -1; }
+  // one call can write batch x n_step rows (every env on LAST with a full ring); in a smaller ring two transitions of the same launch
+  // would share a slot, and a row's five arrays are stored by different waves: a torn row
+  if (capacity < (long long)batch * n_step) {
+    g_nerr = "ffe_nstep_create: capacity " + std::to_string(capacity) + " is below batch x n_step = " + std::to_string((long long)batch * n_step) +
+             ", the rows one call can write: they would share slots of the ring";
+    return -1;
+  }
   int ndev = 0, prev = -1;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || device < 0 || device >= ndev) { g_nerr = "no such HIP device: the MI355X path has no CPU fallback"; return -1; }
   (void)hipGetDevice(&prev);

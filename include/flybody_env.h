@@ -205,8 +205,13 @@ const char *ffe_version(void);
  * new observation, (o_s, a_s, R, D, o_t+1) with R = r_0 + g d_0 r_1 + g^2 d_0 d_1 r_2 + ... and D = g^(m-1) d_0 ... d_(m-1) over the
  * m <= n entries spanned - like acme's adder it does not wait for n entries, so an episode's first n - 1 steps yield the short
  * transitions (o_0 -> o_1), (o_0 -> o_2), ...; LAST also flushes the shorter tails (an episode of T steps leaves T + min(T, n) - 1).
- * Transitions go to a device replay ring of `capacity` slots (slot = count mod capacity).  acme is not in the reference tree:
- * these semantics restate its published behaviour (parity unpinned, tests/test_nstep.py). */
+ * Transitions go to a device replay ring of `capacity` slots (slot = count mod capacity).  capacity >= batch * n_step, the rows one
+ * call can write (every env on LAST with a full ring): both constructors refuse a smaller ring with a text in
+ * ffe_nstep_last_error(NULL), because two transitions of one launch would then share a slot and a row's arrays are stored by
+ * different wavefronts.  Calls are stream-ordered, the envs of one call are not: after W rows the ring holds the last
+ * min(W, capacity) claimed rows, each of them whole, in no particular order inside a call.  acme is not in the reference tree:
+ * these semantics restate its published behaviour (parity unpinned; the kernel is pinned to a numpy restatement of them at the
+ * deployed shapes, tests/test_gpu_nstep_shapes.py). */
 typedef struct ffe_nstep *ffe_nstep_handle;
 int ffe_nstep_create(int batch, int obs_dim, int act_dim, int n_step, float discount, long long capacity, int device, ffe_nstep_handle *out);
 int ffe_nstep_observe(ffe_nstep_handle h, const float *action_dev, const int32_t *step_type_dev, const float *reward_dev,

@@ -4,34 +4,15 @@ include/flybody_env.h) on scripted reward / discount / step_type sequences with 
 import numpy as np
 import pytest
 
+from nstep_restatement import writer_restatement
+
 pytestmark = pytest.mark.gpu
 
 
 def _reference(obs, act, rew, disc, st, n, gamma):
-    """One env.  obs[t], rew[t], disc[t], st[t] = timestep t (t = 0 is FIRST); act[t] = action applied to reach timestep t.
-    Returns the transitions in the order the adder writes them."""
-    out, hist = [], []   # hist entries: (o_s, a_s, r_{s+1}, d_{s+1})
-    last = None
-    for t in range(len(st)):
-        if st[t] == 0:
-            hist, last = [], obs[t]
-            continue
-        hist.append((last, act[t], np.float32(rew[t]), np.float32(disc[t])))
-        hist = hist[-n:]
-        # acme's NStepTransitionAdder._write runs on every add() and does not wait for n entries: during an episode's first n - 1
-        # steps it writes the short transitions (o_0 -> o_1), (o_0 -> o_2), ...; _write_last then flushes the tails
-        starts = [0]
-        if st[t] == 2:
-            starts += list(range(1, len(hist)))
-        for s in starts:
-            ret, td = hist[s][2], hist[s][3]
-            for i in range(s + 1, len(hist)):
-                td = np.float32(td * np.float32(gamma))
-                ret = np.float32(ret + np.float32(hist[i][2] * td))
-                td = np.float32(td * hist[i][3])
-            out.append((hist[s][0], hist[s][1], ret, td, obs[t]))
-        last = obs[t]
-    return out
+    """One env: the transitions in the order the adder writes them (tests/nstep_restatement.py, pinned without a device by
+    tests/test_nstep_restatement_cpu.py)."""
+    return writer_restatement(obs, act, rew, disc, st, n, gamma)
 
 
 @pytest.mark.parametrize("n_step", [1, 5, 50])

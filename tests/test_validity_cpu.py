@@ -7,27 +7,9 @@ import re
 import pytest
 
 from conftest import ROOT
+from nstep_restatement import taint_restatement  # noqa: F401  (tests/test_gpu_validity.py imports it from here)
 
 NEW_SYMBOLS = ("ffe_get_validity", "ffe_validity_stats", "ffe_nstep_create_tracked", "ffe_nstep_observe_flagged", "ffe_nstep_taint_buffer")
-
-
-def taint_restatement(step_type, bits, n_step):
-    """One env.  step_type[t] / bits[t] = what call t passed (t = 0 is FIRST).  The entry appended at step t is marked when
-    bits[t] | bits[t - 1] != 0 (a FIRST call appends nothing, but its bits count as the previous bits of the episode's first entry);
-    a transition is tainted when any of the at most n_step entries it spans is marked.  Returns the taint of every transition in the
-    order the adder writes them (tests/test_nstep.py:_reference: one from the oldest held entry per step, on LAST also the tails)."""
-    out, marks, prev = [], [], 0
-    for t in range(len(step_type)):
-        b = int(bits[t])
-        if step_type[t] == 0:
-            marks, prev = [], b
-            continue
-        marks.append(int((b | prev) != 0))
-        marks = marks[-n_step:]
-        prev = b
-        starts = [0] + (list(range(1, len(marks))) if step_type[t] == 2 else [])
-        out += [int(any(marks[s:])) for s in starts]
-    return out
 
 
 def test_header_declares_and_library_exports_the_validity_entry_points():
