@@ -16,6 +16,7 @@ SYMBOLS = [
     "ffe_nstep_create", "ffe_nstep_observe", "ffe_nstep_buffers", "ffe_nstep_destroy", "ffe_nstep_last_error",
     "ffe_pack_timestep", "ffe_episode_stats",
     "ffe_get_validity", "ffe_validity_stats", "ffe_nstep_create_tracked", "ffe_nstep_observe_flagged", "ffe_nstep_taint_buffer",
+    "ffe_sampler_create", "ffe_sampler_sample", "ffe_sampler_info", "ffe_sampler_destroy", "ffe_sampler_last_error",
 ]
 
 
@@ -106,6 +107,14 @@ def lib():
     L.ffe_nstep_taint_buffer.argtypes = [vp, C.POINTER(C.c_void_p)]
     for s in ("ffe_get_validity", "ffe_validity_stats", "ffe_nstep_create_tracked", "ffe_nstep_observe_flagged", "ffe_nstep_taint_buffer"):
         getattr(L, s).restype = C.c_int
+    L.ffe_sampler_create.argtypes = [C.POINTER(vp), C.c_int, C.c_int, C.c_uint64, C.c_longlong, C.c_int, C.c_int, C.POINTER(vp)]
+    L.ffe_sampler_sample.argtypes = [vp, fp, fp, fp, fp, fp, vp, ip, vp]
+    L.ffe_sampler_info.argtypes = [vp, C.POINTER(C.c_void_p)]
+    L.ffe_sampler_destroy.argtypes = [vp]
+    for s in ("ffe_sampler_create", "ffe_sampler_sample", "ffe_sampler_info", "ffe_sampler_destroy"):
+        getattr(L, s).restype = C.c_int
+    L.ffe_sampler_last_error.restype = C.c_char_p
+    L.ffe_sampler_last_error.argtypes = [vp]
     L.ffe_nstep_last_error.restype = C.c_char_p
     L.ffe_nstep_last_error.argtypes = [vp]
     for s in ("ffe_nstep_create", "ffe_nstep_observe", "ffe_nstep_buffers", "ffe_nstep_destroy"):

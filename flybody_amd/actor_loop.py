@@ -8,7 +8,9 @@ are accumulated with the same keys the reference logs (`episode_length`, `episod
 
 from __future__ import annotations
 
+import collections
 import ctypes as C
+import numbers
 import time
 
 from . import _capi
@@ -150,6 +152,119 @@ class NStepTransitionWriter:
     def close(self):
         if getattr(self, "_h", None):
             self._L.ffe_nstep_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+ReplaySample = collections.namedtuple("ReplaySample", ["obs", "action", "n_step_return", "discount", "next_obs", "taint", "index"])
+
+
+class ReplaySampler:
+    """Uniform minibatches from one or several writers' replay rings, drawn and gathered on the device (`ffe_sampler_*`,
+    flybody_amd/csrc/replay.hip): the read side of the table the reference builds at `agents/ray_distributed_dmpo.py:85-113`,
+    `reverb.Table(sampler=Uniform(), remover=Fifo(), max_size=..., rate_limiter=MinSize(min_replay_size) | SampleToInsertRatio(...))`,
+    read by the learner in batches of 256.  The writers' rings are the `Fifo` remover and `max_size`; this is the `Uniform` sampler
+    (with replacement), the `MinSize` gate (`min_size`) and the batching.  Reverb is not in the reference tree: its behaviour is
+    restated, parity with it is unpinned.
+
+    `writers`: one `NStepTransitionWriter` or a sequence of up to eight (one per env group), on one device, with equal `obs_dim`
+    and `act_dim`.  The sampler keeps references to them (it reads their rings through raw pointers), so they cannot be collected
+    first; closing a writer by hand before its sampler is an error of the caller.
+
+    `sample()` is two launches on torch's current stream with no host synchronisation: it can be captured into a HIP graph (the
+    call counter lives on the device, so every replay draws a fresh batch).  It must be stream-ordered after every `observe()` whose
+    rows it may see - the same stream, or `sample(after=streams)` - or a row that is being overwritten can be read torn.  While fewer
+    than `min_size` rows are in the rings the call writes nothing (see `info()["ready"]`).
+    The `sample()` calls of one sampler must be stream-ordered among themselves too (its control block, counters and outputs are one
+    per sampler): consumers on unordered streams each take a sampler of their own.
+
+    `skip_tainted` (tracked writers only): a draw that hits a tainted row is redrawn, up to eight tries; the eighth is kept and
+    counted in `info()["tainted_kept"]`."""
+
+    def __init__(self, writers, batch_size: int = 256, *, seed: int = 0, min_size: int = 1, skip_tainted: bool = False):
+        if isinstance(writers, NStepTransitionWriter):
+            writers = [writers]
+        if not isinstance(writers, (list, tuple)):
+            raise TypeError(f"writers must be an NStepTransitionWriter or a list / tuple of them, got {type(writers).__name__}")
+        if not 1 <= len(writers) <= 8:
+            raise ValueError(f"a sampler reads 1 to 8 writers, got {len(writers)}")
+        for i, w in enumerate(writers):
+            if not isinstance(w, NStepTransitionWriter):
+                raise TypeError(f"writers[{i}] is no NStepTransitionWriter: {type(w).__name__}")
+            if not getattr(w, "_h", None):
+                raise ValueError(f"writers[{i}] is closed")
+        if not isinstance(skip_tainted, bool):
+            raise TypeError(f"skip_tainted must be a bool, got {skip_tainted!r}")
+        for name, v, lo, hi in (("batch_size", batch_size, 1, 1 << 20), ("min_size", min_size, 1, (1 << 63) - 1), ("seed", seed, 0, (1 << 64) - 1)):
+            if isinstance(v, bool) or not isinstance(v, numbers.Integral) or not lo <= v <= hi:
+                raise ValueError(f"{name} must be an integer in {lo} .. {hi}, got {v!r}")
+        w0 = writers[0]
+        for i, w in enumerate(writers):
+            if (w.obs_dim, w.act_dim) != (w0.obs_dim, w0.act_dim):
+                raise ValueError(f"writers[{i}] has rows of (obs_dim, act_dim) = ({w.obs_dim}, {w.act_dim}), writers[0] of ({w0.obs_dim}, {w0.act_dim}): "
+                                 "they must be equal")
+            if w.device != w0.device:
+                raise ValueError(f"writers[{i}] is on {w.device}, writers[0] on {w0.device}: one sampler reads one device")
+            if w.capacity >= 1 << 40:
+                raise ValueError(f"writers[{i}] has a capacity of 2^40 or more: index packs the slot into 40 bits")
+        self.tracked = all(w.track_validity for w in writers)
+        if skip_tainted and not self.tracked:
+            raise ValueError("skip_tainted needs every writer created with track_validity=True")
+        import torch
+
+        self._t, self._L = torch, _capi.lib()
+        self._writers = tuple(writers)
+        self.batch_size, self.seed, self.min_size, self.skip_tainted = int(batch_size), int(seed), int(min_size), skip_tainted
+        self.obs_dim, self.act_dim, self.device = w0.obs_dim, w0.act_dim, w0.device
+        handles = (C.c_void_p * len(writers))(*[w._h.value for w in writers])
+        h = C.c_void_p()
+        if self._L.ffe_sampler_create(handles, len(writers), self.batch_size, self.seed, self.min_size, 1 if skip_tainted else 0, self.device.index,
+                                      C.byref(h)) != 0:
+            raise RuntimeError(self._L.ffe_sampler_last_error(None).decode())
+        self._h = h
+        K, dev = self.batch_size, self.device
+        self._out = ReplaySample(torch.zeros(K, self.obs_dim, device=dev), torch.zeros(K, self.act_dim, device=dev), torch.zeros(K, device=dev),
+                                 torch.zeros(K, device=dev), torch.zeros(K, self.obs_dim, device=dev),
+                                 torch.zeros(K, dtype=torch.uint8, device=dev) if self.tracked else None, torch.zeros(K, dtype=torch.int64, device=dev))
+        p = C.c_void_p()
+        assert self._L.ffe_sampler_info(self._h, C.byref(p)) == 0
+        self._info = w0._view(p.value, (8,), torch.int64)
+
+    def sample(self, after=()):
+        """One minibatch as `ReplaySample(obs [K,O], action [K,A], n_step_return [K], discount [K], next_obs [K,O], taint [K] uint8 or
+        None for untracked writers, index [K] int64 = (ring << 40) | slot)`.  The tensors are owned by the sampler, the same ones on
+        every call, and are OVERWRITTEN by the next call (fixed addresses are what make graph capture possible): clone what must
+        last.  `after`: streams the current stream is made to wait on first, e.g. `EnvGroups.streams` the writers are fed on."""
+        t = self._t
+        if not self._h:
+            raise RuntimeError("the sampler is closed")
+        cur = t.cuda.current_stream(self.device)
+        for s in after:
+            cur.wait_stream(s)
+        o = self._out
+        rc = self._L.ffe_sampler_sample(self._h, o.obs.data_ptr(), o.action.data_ptr(), o.n_step_return.data_ptr(), o.discount.data_ptr(), o.next_obs.data_ptr(),
+                                        o.taint.data_ptr() if o.taint is not None else None, o.index.data_ptr(), C.c_void_p(cur.cuda_stream))
+        if rc != 0:
+            raise RuntimeError(self._L.ffe_sampler_last_error(self._h).decode())
+        return o
+
+    def info(self) -> dict:
+        """What the last `sample()` found (synchronises the device): `ready`, `total` (rows eligible), `call` (the index the call used),
+        `tainted_kept` (draws that stayed tainted after eight tries) and the cumulative `samples_drawn` - with the writers'
+        `num_written()` the sample-to-insert ratio the reference's `SampleToInsertRatio` limiter enforces; the host can throttle on
+        it, the device never blocks."""
+        self._t.cuda.synchronize(self.device)
+        v = self._info.tolist()
+        return {"ready": bool(v[0]), "total": v[1], "call": v[2], "tainted_kept": v[3], "samples_drawn": v[4]}
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.ffe_sampler_destroy(self._h)
             self._h = None
 
     def __del__(self):

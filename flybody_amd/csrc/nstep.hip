@@ -30,25 +30,9 @@
 #include <string>
 
 #include "../../include/flybody_env.h"
+#include "nstep_ring.hpp"
 
 namespace ffn {
-
-struct Dev {
-  int batch, obs_dim, act_dim, n_step;
-  float gamma;
-  long long capacity;
-  // per-env rings
-  float *r_obs, *r_act, *r_rew, *r_disc;  // [B][n][O], [B][n][A], [B][n], [B][n]
-  float *last_obs;                        // [B][O] observation the next action will be taken from
-  int *head, *count;                      // ring write position / entries held
-  // replay ring
-  float *t_obs, *t_act, *t_ret, *t_disc, *t_next;
-  unsigned long long *written;            // transitions written so far (monotone)
-  // validity tracking (null on a writer created without it)
-  unsigned char *r_mark;                  // [B][n] mark e of each held entry
-  int *prev_bits;                         // [B] step_bits passed with the previous call
-  unsigned char *t_taint;                 // [capacity] taint of each replay slot
-};
 
 // Writes the `total` transitions that start at ring entries 0 .. total - 1 (0 = oldest of `len` held entries) and all end in
 // `next_obs`: total = 1 on an ordinary step, = len on LAST (the shorter tails).  `rew_l` / `disc_l`: lane i holds the reward /
@@ -267,21 +251,9 @@ __global__ void validity_stats_kernel(const int *__restrict__ st, const int *__r
   }
 }
 
-struct Handle {
-  Dev d{};
-  int device = 0;
-  void *allocs[20] = {nullptr};
-  int nalloc = 0;
-  std::string err;
-};
-
 }  // namespace ffn
 
 using ffn::Handle;
-
-struct ffe_nstep {
-  Handle h;
-};
 
 static thread_local std::string g_nerr;
 

@@ -253,6 +253,46 @@ int ffe_episode_stats(const int32_t *step_type_dev, const float *reward_dev, flo
 int ffe_validity_stats(const int32_t *step_type_dev, const int32_t *info_dev, long long *totals_dev, int batch, void *stream);
 const char *ffe_nstep_last_error(ffe_nstep_handle h);
 
+/* ---- device replay sampler: uniform minibatches from the writers' replay rings, the read side of the table the writers feed.
+ * Replaces the reverb.Table(sampler=reverb.selectors.Uniform(), remover=reverb.selectors.Fifo(), max_size=max_replay_size,
+ * rate_limiter=MinSize(min_replay_size) | SampleToInsertRatio(...)) of agents/ray_distributed_dmpo.py:85-113 and the batching of the
+ * dataset the learner iterates (batch_size = 256).  The ring is already the Fifo remover and max_size; this adds the Uniform
+ * sampler (with replacement), the MinSize gate and the batch, over 1 .. 8 rings (one per env group).  Reverb is not in the reference
+ * tree: these semantics restate its published behaviour (parity unpinned; the kernel is pinned to a numpy restatement of the draw
+ * below, tests/test_gpu_replay_sampler.py).
+ * Lifetime and ordering: the sampler keeps raw pointers into the writers' rings, so every writer must outlive it (destroy the
+ * sampler first); and a sample must be stream-ordered after every ffe_nstep_observe / ffe_nstep_observe_flagged whose rows it may
+ * see - the same stream, or an event wait - because a writer claims a slot before it stores the row: a row that is being
+ * overwritten would otherwise be read torn.  The sample calls on one handle must be stream-ordered among themselves as well (one
+ * stream, or event waits between them): the control block the prologue writes and the gather reads, the counters and info are one
+ * per handle, so two calls in flight at once on unordered streams would race on them.  Use one sampler per consumer stream. */
+typedef struct ffe_sampler *ffe_sampler_handle;
+enum { FFE_SAMPLE_SKIP_TAINTED = 1 };
+/* reverb.Table(...) + the learner's batch: n_writers 1 .. 8, all on `device` with equal obs_dim and act_dim and a capacity below
+ * 2^40; batch (K) 1 .. 2^20; min_size >= 1 (MinSize(min_replay_size)); flags 0 or FFE_SAMPLE_SKIP_TAINTED, which needs every writer
+ * tracked.  Anything else fails with rc < 0 and a text in ffe_sampler_last_error(NULL). */
+int ffe_sampler_create(const ffe_nstep_handle *writers, int n_writers, int batch, uint64_t seed, long long min_size, int flags, int device,
+                       ffe_sampler_handle *out);
+/* one item of the learner's iterator (next(dataset) on reverb.TrajectoryDataset batched to K, sampler Uniform): two launches on
+ * `stream`, no host synchronisation and no host read, so the call can be captured into a HIP graph and replayed.  With
+ * N_r = min(written_r, capacity_r), total = sum N_r: when total < min_size nothing is written (the outputs keep what they held);
+ * otherwise row k of obs_dev[K][O], act_dev[K][A], ret_dev[K], disc_dev[K], next_obs_dev[K][O], taint_dev[K], index_dev[K] is the
+ * ring row g (rings concatenated in the order given, index = (ring << 40) | slot), drawn exactly as
+ *   key = splitmix64(splitmix64(seed ^ 0x5A3B1E) + call), u(k,t) = splitmix64(key + (k << 3) + t), g(k,t) = (u(k,t) * total) >> 64
+ * with call = the number of earlier sample calls on this handle, ready or not (kept on the device).  Without
+ * FFE_SAMPLE_SKIP_TAINTED row k is g(k,0); with it the first try t = 0 .. 7 whose row has taint 0, the eighth when all are tainted
+ * (counted in info[3]).  A non-NULL taint_dev needs every writer tracked. */
+int ffe_sampler_sample(ffe_sampler_handle s, float *obs_dev, float *act_dev, float *ret_dev, float *disc_dev, float *next_obs_dev,
+                       uint8_t *taint_dev /* may be NULL */, int64_t *index_dev /* may be NULL */, void *stream);
+/* reverb.Table.info / the rate limiter's counters: *info_dev = library-owned device int64[8], rewritten by every sample call:
+ * 0 ready, 1 total (rows eligible at this call), 2 call (the index this call used), 3 draws of this call that stayed tainted,
+ * 4 samples_drawn (cumulative rows of ready calls: with the writers' counts the sample-to-insert ratio SampleToInsertRatio
+ * enforces - the host can throttle on it, the device never blocks), 5-7 zero. */
+int ffe_sampler_info(ffe_sampler_handle s, long long **info_dev);
+/* reverb.Client / Table teardown; the writers are left as they are */
+int ffe_sampler_destroy(ffe_sampler_handle s);
+const char *ffe_sampler_last_error(ffe_sampler_handle s);
+
 #ifdef __cplusplus
 }
 #endif
