@@ -17,6 +17,7 @@ SYMBOLS = [
     "ffe_pack_timestep", "ffe_episode_stats",
     "ffe_get_validity", "ffe_validity_stats", "ffe_nstep_create_tracked", "ffe_nstep_observe_flagged", "ffe_nstep_taint_buffer",
     "ffe_sampler_create", "ffe_sampler_sample", "ffe_sampler_info", "ffe_sampler_destroy", "ffe_sampler_last_error",
+    "ffe_eplog_create", "ffe_eplog_arm", "ffe_eplog_observe", "ffe_eplog_buffers", "ffe_eplog_destroy", "ffe_eplog_last_error",
 ]
 
 
@@ -115,6 +116,15 @@ def lib():
         getattr(L, s).restype = C.c_int
     L.ffe_sampler_last_error.restype = C.c_char_p
     L.ffe_sampler_last_error.argtypes = [vp]
+    L.ffe_eplog_create.argtypes = [C.c_int, C.c_longlong, C.c_int, C.c_int, C.POINTER(vp)]
+    L.ffe_eplog_arm.argtypes = [vp, vp, vp]
+    L.ffe_eplog_observe.argtypes = [vp, ip, fp, fp, ip, ip, C.c_int, vp]
+    L.ffe_eplog_buffers.argtypes = [vp, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]
+    L.ffe_eplog_destroy.argtypes = [vp]
+    for s in ("ffe_eplog_create", "ffe_eplog_arm", "ffe_eplog_observe", "ffe_eplog_buffers", "ffe_eplog_destroy"):
+        getattr(L, s).restype = C.c_int
+    L.ffe_eplog_last_error.restype = C.c_char_p
+    L.ffe_eplog_last_error.argtypes = [vp]
     L.ffe_nstep_last_error.restype = C.c_char_p
     L.ffe_nstep_last_error.argtypes = [vp]
     for s in ("ffe_nstep_create", "ffe_nstep_observe", "ffe_nstep_buffers", "ffe_nstep_destroy"):

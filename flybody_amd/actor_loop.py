@@ -274,6 +274,284 @@ class ReplaySampler:
             pass
 
 
+def _device_view(torch, device, ptr, shape, typestr):
+    """torch tensor over library-owned device memory (no copy), via the CUDA array interface"""
+
+    class _Mem:
+        __cuda_array_interface__ = {"shape": tuple(shape), "typestr": typestr, "data": (int(ptr), False), "version": 2, "strides": None}
+
+    return torch.as_tensor(_Mem(), device=device)
+
+
+def record_dtype():
+    """numpy dtype of one episode record (32 bytes; include/flybody_env.h, ffe_eplog_*)"""
+    import numpy as np
+
+    return np.dtype([("env", "<i4"), ("tag", "<i4"), ("length", "<i4"), ("ret", "<f4"), ("call", "<i8"), ("flagged_steps", "<i4"), ("bits", "<i4")])
+
+
+TERMINATED_BIT = 256  # record["bits"] bit 8: the LAST row's discount was 0
+
+_SUMMARY_STATS = ("avg", "var", "max", "min")
+
+
+def canonical_order(records):
+    """The records sorted by (call, env): the order `EpisodeLog.records()` returns and `summarize` counts `last` in (stable, so the
+    concatenation of several logs keeps the logs' order among equal keys)."""
+    import numpy as np
+
+    records = np.asarray(records)
+    if records.dtype != record_dtype():
+        raise TypeError(f"records must be a structured array of dtype {record_dtype()}, got {records.dtype}")
+    return records[np.lexsort((records["env"], records["call"]))]
+
+
+def summarize(records, last=None, by_tag=False, num_tags=None):
+    """The evaluator's aggregate of the reference, `_eval_agg_stat` (`agents/ray_distributed_dmpo.py:417-440`), over the last `last`
+    records of the canonical (call, env) order (None = all; a `last` beyond the record count takes all; the reference's window is
+    `eval_average_over`): `avg_` / `var_` / `max_` / `min_` of `episode_return` and `episode_length` - `np.var`, the population
+    variance, as there - plus `episodes`, `terminated_fraction` (episodes whose LAST row had discount 0, as opposed to the time limit),
+    `flagged_episodes` (with at least one control step of truncated physics) and `flagged_steps` (their sum).  float64 numpy on the
+    host, on purpose: this is no hot path, a record is 32 bytes.  Without episodes the statistics are nan and the counts 0.
+
+    `by_tag=True`: every value is an array indexed by tag (flight imitation: the reference clip), of `num_tags` entries (default: the
+    largest tag present + 1); tags without episodes give nan and a count of 0.  `records` may be the concatenation of several logs'
+    records (one log per env group): counts and statistics are then those of the groups together.
+
+    The reference also logs a per-episode `steps_per_second` and its mean; it is not recorded here: in a batched loop an episode
+    has no wall time of its own (`run()` reports the loop's)."""
+    import numpy as np
+
+    rec = canonical_order(records)
+    if last is not None:
+        if isinstance(last, bool) or not isinstance(last, numbers.Integral) or last < 0:
+            raise ValueError(f"last must be a non-negative integer or None, got {last!r}")
+        rec = rec[len(rec) - min(int(last), len(rec)):]
+
+    def one(r):
+        out = {}
+        for key, field in (("episode_return", "ret"), ("episode_length", "length")):
+            x = r[field].astype(np.float64)
+            for stat, fn in zip(_SUMMARY_STATS, (np.mean, np.var, np.max, np.min)):
+                out[f"{stat}_{key}"] = float(fn(x)) if len(x) else float("nan")
+        out["episodes"] = int(len(r))
+        out["terminated_fraction"] = float(np.mean((r["bits"] & TERMINATED_BIT) != 0)) if len(r) else float("nan")
+        out["flagged_episodes"] = int((r["flagged_steps"] > 0).sum())
+        out["flagged_steps"] = int(r["flagged_steps"].astype(np.int64).sum())
+        return out
+
+    if not by_tag:
+        return one(rec)
+    if len(rec) and int(rec["tag"].min()) < 0:
+        raise ValueError("by_tag needs non-negative tags")
+    n = (int(rec["tag"].max()) + 1 if len(rec) else 0) if num_tags is None else int(num_tags)
+    if len(rec) and int(rec["tag"].max()) >= n:
+        raise ValueError(f"a record has tag {int(rec['tag'].max())}, num_tags is {n}")
+    rows = [one(rec[rec["tag"] == k]) for k in range(n)]
+    keys = list(one(rec[:0]))
+    ints = ("episodes", "flagged_episodes", "flagged_steps")
+    return {k: np.array([row[k] for row in rows], dtype=np.int64 if k in ints else np.float64) for k in keys}
+
+
+class EpisodeLog:
+    """One record per finished episode, written on the device (`ffe_eplog_*`, flybody_amd/csrc/episode_log.hip): what the reference's
+    `EnvironmentLoop` logs per episode and its evaluator keeps in `self._stats` (`agents/ray_distributed_dmpo.py:401-440`), for B envs
+    per call.  `observe(timestep)` is one launch on torch's current stream with no host read (capturable into a HIP graph): per env a
+    FIRST row restarts the running return and length, MID adds reward and a step, LAST does the same and emits
+    (env, tag, length, ret, call, flagged_steps, bits) into a ring of `capacity >= batch_size` records (slot = count mod capacity).
+
+    `one_shot=True`: only envs armed by `arm(mask)` emit, and an env disarms on its LAST - every armed env contributes exactly its next
+    finished episode; `info()["armed_left"]` counts the ones still running (`BatchedEvaluator` polls it)."""
+
+    def __init__(self, batch_size: int, *, capacity: int = 1 << 16, device: int = 0, one_shot: bool = False):
+        if not isinstance(one_shot, bool):
+            raise TypeError(f"one_shot must be a bool, got {one_shot!r}")
+        for name, v in (("batch_size", batch_size), ("capacity", capacity)):
+            if isinstance(v, bool) or not isinstance(v, numbers.Integral) or v <= 0:
+                raise ValueError(f"{name} must be a positive integer, got {v!r}")
+        if isinstance(device, bool) or not isinstance(device, numbers.Integral) or device < 0:
+            raise ValueError(f"device must be a non-negative integer, got {device!r}")
+        if batch_size >= 1 << 31:
+            raise ValueError(f"batch_size {batch_size} does not fit the record's int32 env index")
+        if capacity < batch_size:
+            raise ValueError(f"capacity {capacity} is below batch_size = {batch_size}, the records one observe() can write (every env on LAST): "
+                             "they would share slots of the ring")
+        import torch
+
+        self._t, self._L = torch, _capi.lib()
+        self.batch_size, self.capacity, self.one_shot = int(batch_size), int(capacity), one_shot
+        self.device = torch.device("cuda", int(device))
+        h = C.c_void_p()
+        if self._L.ffe_eplog_create(self.batch_size, self.capacity, 1 if one_shot else 0, int(device), C.byref(h)) != 0:
+            raise RuntimeError(self._L.ffe_eplog_last_error(None).decode())
+        self._h = h
+        rec, info = C.c_void_p(), C.c_void_p()
+        assert self._L.ffe_eplog_buffers(self._h, C.byref(rec), C.byref(info)) == 0
+        self._records = _device_view(torch, self.device, rec.value, (self.capacity * 32,), "|u1")
+        self._info = _device_view(torch, self.device, info.value, (4,), "<i8")
+
+    def _check_open(self):
+        if not getattr(self, "_h", None):
+            raise RuntimeError("the episode log is closed")
+
+    def _stream(self):
+        return C.c_void_p(self._t.cuda.current_stream(self.device).cuda_stream)
+
+    def observe(self, timestep, *, validity=None, tags=None):
+        """`timestep`: the `TimeStep` of `env.reset()` / `env.step()` (step_type int32 [B], reward / discount float32 [B]).
+        `validity`: the env's int32 [B, 4] validity buffer for the same timestep (`env.validity_buffer` after `env.validity()`) or None
+        (records then carry flagged_steps 0 and no episode bits).  `tags`: int32 [B] tensor, or a column of a contiguous int32 [B, k]
+        tensor (its stride is passed through), read on LAST rows; None = tag 0."""
+        t, B = self._t, self.batch_size
+        self._check_open()
+
+        # the C ABI takes raw device pointers: everything it will read is checked here
+        def ok(x, dtype, shape):
+            return isinstance(x, t.Tensor) and x.is_cuda and x.device == self.device and x.dtype == dtype and x.is_contiguous() and tuple(x.shape) == shape
+
+        st, rew, disc = timestep.step_type, timestep.reward, timestep.discount
+        if not (ok(st, t.int32, (B,)) and ok(rew, t.float32, (B,)) and ok(disc, t.float32, (B,))):
+            raise ValueError(f"step_type int32 [{B}], reward / discount float32 [{B}], contiguous on the log's device {self.device}")
+        if validity is not None and not ok(validity, t.int32, (B, 4)):
+            raise ValueError(f"validity must be the contiguous int32 [{B}, 4] validity buffer on the log's device {self.device}")
+        tag_ptr, stride = None, 1
+        if tags is not None:
+            if not isinstance(tags, t.Tensor) or tags.dtype != t.int32:
+                raise TypeError("tags must be an int32 tensor")
+            if not tags.is_cuda or tags.device != self.device:
+                raise ValueError(f"tags must live on the log's device {self.device}")
+            if tags.dim() != 1 or tags.shape[0] != B or (B > 1 and tags.stride(0) < 1):
+                raise ValueError(f"tags must have shape ({B},): an int32 [{B}] tensor or a column of a contiguous int32 [{B}, k] tensor")
+            tag_ptr, stride = tags.data_ptr(), max(1, int(tags.stride(0)))
+        rc = self._L.ffe_eplog_observe(self._h, st.data_ptr(), rew.data_ptr(), disc.data_ptr(), validity.data_ptr() if validity is not None else None,
+                                       tag_ptr, stride, self._stream())
+        if rc != 0:
+            raise RuntimeError(self._L.ffe_eplog_last_error(self._h).decode())
+
+    def arm(self, mask=None):
+        """One-shot logs: envs with `mask[i] != 0` (bool / uint8 [B] on the log's device; None = all) emit their next finished episode.
+        One launch on the current stream, nothing read back."""
+        t = self._t
+        self._check_open()
+        if not self.one_shot:
+            raise ValueError("arm() needs a log created with one_shot=True: a plain log records every episode")
+        m = None
+        if mask is not None:
+            if not isinstance(mask, t.Tensor) or mask.dtype not in (t.bool, t.uint8):
+                raise TypeError("mask must be a bool or uint8 tensor")
+            if not mask.is_cuda or mask.device != self.device or tuple(mask.shape) != (self.batch_size,) or not mask.is_contiguous():
+                raise ValueError(f"mask must be contiguous, of shape ({self.batch_size},), on the log's device {self.device}")
+            m = mask.view(t.uint8) if mask.dtype == t.bool else mask
+        if self._L.ffe_eplog_arm(self._h, m.data_ptr() if m is not None else None, self._stream()) != 0:
+            raise RuntimeError(self._L.ffe_eplog_last_error(self._h).decode())
+
+    def info(self) -> dict:
+        """`written` (records since creation), `calls` (observe calls), `armed_left` (one-shot: armed envs still in their episode).
+        Synchronises the device."""
+        self._check_open()
+        self._t.cuda.synchronize(self.device)
+        v = self._info.tolist()
+        return {"written": v[0], "calls": v[1], "armed_left": v[2]}
+
+    def records(self):
+        """The min(written, capacity) records in the ring as a numpy structured array (`record_dtype()`), sorted by (call, env) - the
+        canonical order; slots inside one call are claimed in no particular order.  Synchronises and copies to the host."""
+        n = min(self.info()["written"], self.capacity)
+        raw = self._records[:n * 32].cpu().numpy()
+        return canonical_order(raw.view(record_dtype()))
+
+    def summary(self, last=None, by_tag=False, num_tags=None):
+        """`summarize(self.records(), ...)`"""
+        return summarize(self.records(), last=last, by_tag=by_tag, num_tags=num_tags)
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.ffe_eplog_destroy(self._h)
+            self._h = None
+            self._records = self._info = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class BatchedEvaluator:
+    """The reference's evaluator loop for a batch: `EnvironmentLoop(actor_or_evaluator="evaluator")`
+    (`agents/ray_distributed_dmpo.py:342-352, 401-440`), which runs the deterministic policy episode after episode and reports
+    `_eval_agg_stat`.  `env` is a handle of the evaluator's own, not the one the actors step; `policy` is whatever callable gives the
+    deterministic action for `flat_obs [B, O]` (the reference uses `StochasticMeanHead`).
+
+    `run()` works in rounds, `ceil(episodes_per_clip * ntraj / B)` of them: env i of round r gets clip `(r * B + i) mod ntraj` and a wing
+    phase from `np.random.RandomState(seed)`, both through `set_next_trajectory_index`; the assignment is the tag tensor.  Each round
+    arms a one-shot `EpisodeLog`, resets, and steps until `armed_left` is 0 - one value read on the host every `poll_every` steps, so
+    envs that finished go on stepping (auto-reset) unrecorded meanwhile.  Every env contributes exactly its first episode of every
+    round: long and short episodes weigh equally, where a "first N finished" rule would favour the short ones.  Envs without clips
+    (`walk_on_ball`) run as one clip with tag 0.  More than the env's time-limit control steps + 2 in one round raises."""
+
+    def __init__(self, env, policy, *, episodes_per_clip: int = 1, seed: int = 0, poll_every: int = 64):
+        for name, v in (("episodes_per_clip", episodes_per_clip), ("poll_every", poll_every)):
+            if isinstance(v, bool) or not isinstance(v, numbers.Integral) or v <= 0:
+                raise ValueError(f"{name} must be a positive integer, got {v!r}")
+        if isinstance(seed, bool) or not isinstance(seed, numbers.Integral) or not 0 <= seed < 1 << 32:
+            raise ValueError(f"seed must be an integer in 0 .. 2^32 - 1, got {seed!r}")
+        self.env, self.policy = env, policy
+        self.episodes_per_clip, self.seed, self.poll_every = int(episodes_per_clip), int(seed), int(poll_every)
+        self.has_clips = getattr(env, "task_kind", None) == "flight_imitation"
+        self.ntraj = int(env.refs.ntraj) if self.has_clips else 1
+        B = env.batch_size
+        self.rounds = -(-self.episodes_per_clip * self.ntraj // B)
+        self.max_steps = int(env.time_limit_steps) + 2
+
+    def run(self) -> dict:
+        """`summarize` of the rounds' records, plus `"per_clip"` (its `by_tag` tables over the `ntraj` clips), `"records"` (the raw
+        records, canonical order), `"rounds"` ((first, one past the last) observe-call index of every round) and `"wall_seconds"`."""
+        import numpy as np
+        import torch
+
+        env, B = self.env, self.env.batch_size
+        rng = np.random.RandomState(self.seed)
+        log = EpisodeLog(B, capacity=max(B, self.rounds * B), device=env.device.index, one_shot=True)
+        track = hasattr(env, "validity")
+        spans, call = [], 0
+        start = time.perf_counter()
+        try:
+            with torch.cuda.device(env.device):
+                for r in range(self.rounds):
+                    tags = None
+                    if self.has_clips:
+                        clips = ((r * B + np.arange(B)) % self.ntraj).astype(np.int32)
+                        env.set_next_trajectory_index(clips, rng.uniform(size=B))
+                        tags = torch.tensor(clips, device=env.device)
+                    log.arm()
+                    ts = env.reset()
+                    log.observe(ts, tags=tags)
+                    first, steps, left = call, 0, B
+                    while left:
+                        if steps >= self.max_steps:
+                            raise RuntimeError(f"round {r}: {left} envs still in their first episode after {steps} steps, the time limit is {self.max_steps - 2}")
+                        for _ in range(min(self.poll_every, self.max_steps - steps)):
+                            with torch.no_grad():
+                                action = self.policy(env.flat_observation)
+                            ts = env.step(action.contiguous())
+                            if track:
+                                env.validity()
+                            log.observe(ts, validity=env.validity_buffer if track else None, tags=tags)
+                            steps += 1
+                        left = log.info()["armed_left"]
+                    call = first + 1 + steps  # one observe for the reset, one per step
+                    spans.append((first, call))
+                records = log.records()
+        finally:
+            log.close()
+        wall = time.perf_counter() - start
+        assert len(records) == self.rounds * B, (len(records), self.rounds, B)
+        out = summarize(records)
+        out.update({"per_clip": summarize(records, by_tag=True, num_tags=self.ntraj), "records": records, "rounds": spans, "wall_seconds": wall})
+        return out
+
+
 class BatchedActorLoop:
     def __init__(self, env, policy, adder: NStepTransitionWriter | None = None, track_validity: bool = False):
         """`adder`: optional `NStepTransitionWriter`; fed as the reference's actor feeds its adder (`observe_first` on FIRST,
@@ -282,7 +560,9 @@ class BatchedActorLoop:
         `track_validity`: every iteration also reads `env.validity()`, hands its `step_bits` to the adder (which must then have
         been created with `track_validity=True` as well) and accumulates batch totals on the device; `run()` then also reports
         `flagged_env_steps` (MID / LAST env-steps whose physics was truncated), `flagged_episodes` (finished episodes with at least
-        one) and `flagged_steps_per_flagged_episode`.  Off (the default): the launches and result keys are those without it."""
+        one) and `flagged_steps_per_flagged_episode`.  Off (the default): the launches and result keys are those without it.
+
+        `log_episodes(log)` attaches an `EpisodeLog`; the constructor keeps the parameter list its callers know."""
         import torch
 
         if not isinstance(track_validity, bool):
@@ -301,6 +581,27 @@ class BatchedActorLoop:
         self._sum_ret = torch.zeros(1, dtype=torch.float64, device=dev)
         self._vtot = torch.zeros(3, dtype=torch.int64, device=dev) if track_validity else None  # ffe_validity_stats totals
         self._L = _capi.lib()
+        self.episode_log = self._task_ints = self._task_reals = None
+
+    def log_episodes(self, episode_log: EpisodeLog | None):
+        """Attaches an `EpisodeLog` of the env's batch size (None detaches it) and returns the loop, so that
+        `BatchedActorLoop(env, policy, ...).log_episodes(log).run(n)` reads in one line.  Every iteration then also calls the log's
+        `observe` (one launch) - with the validity buffer when `track_validity` is on, and for `flight_imitation` with the episode's clip
+        as the tag: column 3 (`traj_idx`) of a task-state buffer the loop owns and refills each step (`ffe_get_task_state`, one more
+        launch, logged loops only) - and `run()` adds `"episode_log": log`.  Without a log the launches and result keys are those of a
+        loop that never had one."""
+        t, B, dev = self._t, self.env.batch_size, self.env.device
+        if episode_log is not None:
+            if not isinstance(episode_log, EpisodeLog):
+                raise TypeError(f"episode_log must be an EpisodeLog, got {type(episode_log).__name__}")
+            if episode_log.batch_size != B or episode_log.device != dev:
+                raise ValueError(f"episode_log is for {episode_log.batch_size} envs on {episode_log.device}, the env has {B} on {dev}")
+        self.episode_log = episode_log
+        self._task_ints = self._task_reals = None
+        if episode_log is not None and getattr(self.env, "task_kind", None) == "flight_imitation":
+            self._task_ints = t.zeros(B, 8, dtype=t.int32, device=dev)
+            self._task_reals = t.zeros(B, 8, dtype=t.float64, device=dev)
+        return self
 
     @property
     def episodes(self) -> int:
@@ -322,6 +623,18 @@ class BatchedActorLoop:
                                            self._sum_ret.data_ptr(), self.env.batch_size, C.c_void_p(t.cuda.current_stream(self.env.device).cuda_stream))
         if rc != 0:
             raise RuntimeError("ffe_episode_stats failed")
+        if self.episode_log is not None:
+            self._observe_log(ts, self.env.validity_buffer if self.track_validity else None)
+
+    def _observe_log(self, ts, validity):
+        """the timestep just produced -> the episode log (flight: the task state is refilled first, its traj_idx column is the tag)"""
+        t, tags = self._t, None
+        if self._task_ints is not None:
+            if self._L.ffe_get_task_state(self.env._h, self._task_ints.data_ptr(), self._task_reals.data_ptr(),
+                                          C.c_void_p(t.cuda.current_stream(self.env.device).cuda_stream)) != 0:
+                raise RuntimeError("ffe_get_task_state failed")
+            tags = self._task_ints[:, 3]
+        self.episode_log.observe(ts, validity=validity, tags=tags)
 
     def _observe_validity(self, action, ts):
         """validity of the timestep just produced -> the adder's taint column and the batch totals (two or three small launches)"""
@@ -334,6 +647,9 @@ class BatchedActorLoop:
                                             C.c_void_p(t.cuda.current_stream(self.env.device).cuda_stream))
         if rc != 0:
             raise RuntimeError("ffe_validity_stats failed")
+
+    def _log_result(self) -> dict:
+        return {} if self.episode_log is None else {"episode_log": self.episode_log}
 
     def _validity_result(self) -> dict:
         if not self.track_validity:
@@ -368,7 +684,8 @@ class BatchedActorLoop:
             n = int(self._tot[0].item())
             return {"episodes": n, "episode_return": float(self._sum_ret.item()) / n if n else float("nan"),
                     "episode_length": float(self._tot[1].item()) / n if n else float("nan"),
-                    "steps_per_second": num_steps * self.env.batch_size / wall, "capacity_flagged_envs": self._flagged(), **self._validity_result()}
+                    "steps_per_second": num_steps * self.env.batch_size / wall, "capacity_flagged_envs": self._flagged(), **self._validity_result(),
+                    **self._log_result()}
         start = time.perf_counter()
         for _ in range(num_steps):
             self._iteration()
@@ -377,7 +694,8 @@ class BatchedActorLoop:
         n = int(self._tot[0].item())
         return {"episodes": n, "episode_return": float(self._sum_ret.item()) / n if n else float("nan"),
                 "episode_length": float(self._tot[1].item()) / n if n else float("nan"),
-                "steps_per_second": num_steps * self.env.batch_size / wall, "capacity_flagged_envs": self._flagged(), **self._validity_result()}
+                "steps_per_second": num_steps * self.env.batch_size / wall, "capacity_flagged_envs": self._flagged(), **self._validity_result(),
+                    **self._log_result()}
 
     def _begin(self):
         """reset + `observe_first`, statistics zeroed (on torch's current stream)"""
@@ -389,6 +707,8 @@ class BatchedActorLoop:
         if self.adder is not None:
             kw = {"step_bits": self.env.validity().step_bits} if self.track_validity else {}
             self.adder.observe(t.zeros(self.env.batch_size, self.adder.act_dim, device=self.env.device), ts, self.env.flat_observation, **kw)
+        if self.episode_log is not None:  # the FIRST rows: whatever episode the log was following is abandoned
+            self._observe_log(ts, None)
 
     def _flagged(self) -> int:
         """Envs whose step met more simultaneous contacts / constraint rows than the kernel carries (`ffe_get_task_state` int 7: the
@@ -400,16 +720,23 @@ class BatchedActorLoop:
         return int((((w >> 8) & 255) != 0).sum()) if is_flight else int((w != 0).sum())
 
 
-
 class GroupedActorLoop:
     """The actor loop over asynchronous env groups (`flybody_amd.groups.EnvGroups`): one `BatchedActorLoop` per group, everything a group
     does - policy, env step, adder, statistics - on that group's stream, the host enqueueing the groups round-robin.  No group waits for
     another, as the reference's actor processes do not (`train_dmpo_ray.py:432-452`); one group's launch drains while the next group's
     fills the device.  The policy is shared (its weights are read-only here)."""
 
-    def __init__(self, groups, policy, adders=None, track_validity: bool = False):
+    def __init__(self, groups, policy, adders=None, track_validity: bool = False, episode_logs=None):
+        """`episode_logs`: optional sequence of one `EpisodeLog` per group (of the group's batch size); group g's loop feeds logs[g] on
+        the group's stream, `run()` then adds `"episode_logs": logs`; `summarize` takes the concatenation of their `records()`."""
         self.groups = groups
+        if episode_logs is not None and len(episode_logs) != len(groups.envs):
+            raise ValueError(f"episode_logs has {len(episode_logs)} logs for {len(groups.envs)} groups")
+        self.episode_logs = list(episode_logs) if episode_logs is not None else None
         self.loops = [BatchedActorLoop(e, policy, adders[g] if adders is not None else None, track_validity) for g, e in enumerate(groups.envs)]
+        if self.episode_logs is not None:
+            for lp, log in zip(self.loops, self.episode_logs):
+                lp.log_episodes(log)
 
     def run(self, num_steps: int, graph: bool = False) -> dict:
         """`graph`: every group's iteration is captured once into a HIP graph on the group's stream and replayed (two dozen launches per
@@ -448,7 +775,7 @@ class GroupedActorLoop:
         length = sum(int(lp._tot[1].item()) for lp in self.loops)
         return {"episodes": n, "episode_return": ret / n if n else float("nan"), "episode_length": length / n if n else float("nan"),
                 "steps_per_second": num_steps * self.groups.batch_size / wall, "capacity_flagged_envs": sum(lp._flagged() for lp in self.loops),
-                **self._validity_result()}
+                **self._validity_result(), **({"episode_logs": self.episode_logs} if self.episode_logs is not None else {})}
 
     def _validity_result(self) -> dict:
         if not self.loops or not self.loops[0].track_validity:

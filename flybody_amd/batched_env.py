@@ -122,6 +122,7 @@ class BatchedFlyEnv:
             terminal_com_dist=float(terminal_com_dist), ghost_accel_z=ghost_accel_z, pad_first_obs=int(pad_first_obs),
             physics_flags=int(physics_flags), canonical_actions=int(canonical_actions), clip_actions=int(clip_actions),
             contact_capacity=self.contact_capacity)
+        self.time_limit_steps = int(task.episode_limit_steps)  # control steps after which the time limit ends an episode
         h = C.c_void_p()
         rc = self._L.ffe_create_flight(blob, len(blob), C.byref(task), self.batch_size, device, seed, env_id_base, C.byref(h))
         if rc != 0:
@@ -353,6 +354,7 @@ class BatchedBallEnv(BatchedFlyEnv):
         task = _capi.BallTask(control_timestep=float(control_timestep), time_limit_steps=time_limit_control_steps(time_limit, h_phys, nsub),
                               pad_first_obs=int(pad_first_obs), physics_flags=int(physics_flags),
                               canonical_actions=int(canonical_actions), clip_actions=int(clip_actions))
+        self.time_limit_steps = int(task.time_limit_steps)
         h = C.c_void_p()
         rc = self._L.ffe_create_walk_on_ball(blob, len(blob), C.byref(task), self.batch_size, device, C.byref(h))
         if rc != 0:

@@ -293,6 +293,51 @@ int ffe_sampler_info(ffe_sampler_handle s, long long **info_dev);
 int ffe_sampler_destroy(ffe_sampler_handle s);
 const char *ffe_sampler_last_error(ffe_sampler_handle s);
 
+/* ---- per-episode log on the device: one 32-byte record per finished episode, in a ring in HBM.  Replaces what the reference's
+ * EnvironmentLoop keeps per episode - the row `run_episode` returns to its logger after every episode (episode_length,
+ * episode_return: agents/ray_distributed_dmpo.py:401-440) and the list `self._stats` of the last eval_average_over of them that
+ * the evaluator's `_eval_agg_stat` aggregates into avg_ / var_ / max_ / min_ (:408-440; eval_average_over: :81) - for B envs per
+ * call.  The aggregation itself stays on the host (flybody_amd.actor_loop.summarize).  acme's loop is not in the reference tree:
+ * the per-episode rule restates its published behaviour (parity unpinned; the kernel is pinned to a numpy restatement of the rule,
+ * tests/test_gpu_episode_log.py).
+ * Record (32 bytes, 32-byte aligned):
+ *   int32 env            env index in the handle
+ *   int32 tag            the caller's tag of the env, read on the LAST row (flight imitation: the clip, task-state int 3)
+ *   int32 length         control steps of the episode
+ *   float ret            running float32 sum of the rewards in step order, exactly as ffe_episode_stats accumulates it
+ *   int64 call           index of the observe call that closed the episode (the first call on the handle is 0)
+ *   int32 flagged_steps  info[i][1] on the LAST row (ffe_get_validity: episode_flagged_steps); 0 without info_dev
+ *   int32 bits           bits 0-7 info[i][2] & 255 (episode_bits); bit 8 set when the LAST row's discount is 0: the episode
+ *                        terminated and was not cut by the time limit
+ * Per env: a FIRST row restarts the running return and length and adds nothing, so an episode abandoned by an explicit reset leaves
+ * no record (as in the reference's loop, which only logs at the end of run_episode); a MID row adds its reward and one step; a LAST
+ * row does the same, then emits the record and restarts the counters.
+ * Ring: the slot of a record is count mod capacity; count, the call counter and armed_left live on the device in the info block
+ * int64[4] = {records written, calls, armed_left, reserved}.  capacity >= batch, the records one call can emit: the constructor
+ * refuses a smaller ring with a text in the last-error string of the NULL handle.  Calls are stream-ordered; the records of one call are
+ * in no particular order among themselves but occupy one contiguous range of count. */
+typedef struct ffe_eplog *ffe_eplog_handle;
+enum { FFE_EPLOG_ONE_SHOT = 1 };
+/* the evaluator's / actor's per-episode bookkeeping (EnvironmentLoop.__init__, agents/ray_distributed_dmpo.py:342-352, where
+ * `self._stats = []` is set up): flags 0 or FFE_EPLOG_ONE_SHOT - only armed envs emit, and an env disarms on its LAST: the "first
+ * episode of every env" an evaluation round wants */
+int ffe_eplog_create(int batch, long long capacity, int flags /* bit 0: one-shot */, int device, ffe_eplog_handle *out);
+/* starting an evaluation round (the evaluator's run_episode entered once per env, :401-404): armed[i] = mask_dev[i] != 0, or every env
+ * when mask_dev is NULL, and armed_left = their number.  One launch on `stream`, nothing read back.  Fails with a text on a plain log */
+int ffe_eplog_arm(ffe_eplog_handle h, const uint8_t *mask_dev /* [B] or NULL = all */, void *stream);
+/* the loop body's bookkeeping of one timestep (episode_return += reward, episode_steps += 1, and at the end of the episode the
+ * logged row: agents/ray_distributed_dmpo.py:401-415) for every env: one launch on `stream`, no host read, capturable into a HIP
+ * graph (the call index lives on the device, so every replay is its own call).  The pointers are read on the handle's device */
+int ffe_eplog_observe(ffe_eplog_handle h, const int32_t *step_type_dev, const float *reward_dev, const float *discount_dev,
+                      const int32_t *info_dev   /* ffe_get_validity buffer int32[B][4], or NULL */,
+                      const int32_t *tag_dev, int tag_stride_ints /* element i at tag_dev[i*stride]; NULL = tag 0 */,
+                      void *stream);
+/* `self._stats` itself (:408-412): *records_dev = the library-owned ring of `capacity` records, *info_dev = the int64[4] info block */
+int ffe_eplog_buffers(ffe_eplog_handle h, void **records_dev, long long **info_dev /* int64[4] */);
+/* the loop's teardown */
+int ffe_eplog_destroy(ffe_eplog_handle h);
+const char *ffe_eplog_last_error(ffe_eplog_handle h);
+
 #ifdef __cplusplus
 }
 #endif
