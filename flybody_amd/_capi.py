@@ -18,6 +18,8 @@ SYMBOLS = [
     "ffe_get_validity", "ffe_validity_stats", "ffe_nstep_create_tracked", "ffe_nstep_observe_flagged", "ffe_nstep_taint_buffer",
     "ffe_sampler_create", "ffe_sampler_sample", "ffe_sampler_info", "ffe_sampler_destroy", "ffe_sampler_last_error",
     "ffe_eplog_create", "ffe_eplog_arm", "ffe_eplog_observe", "ffe_eplog_buffers", "ffe_eplog_destroy", "ffe_eplog_last_error",
+    "ffe_walktask_create", "ffe_walktask_features", "ffe_walktask_evaluate", "ffe_walktask_reference_pose", "ffe_walktask_info",
+    "ffe_walktask_destroy", "ffe_walktask_last_error",
 ]
 
 
@@ -38,6 +40,18 @@ class FlightTask(C.Structure):
 class BallTask(C.Structure):
     _fields_ = [("control_timestep", C.c_double), ("time_limit_steps", C.c_int32), ("pad_first_obs", C.c_int32),
                 ("physics_flags", C.c_int32), ("canonical_actions", C.c_int32), ("clip_actions", C.c_int32)]
+
+
+class WalkTask(C.Structure):
+    _fields_ = [
+        ("n_joints", C.c_int32), ("joints", C.POINTER(C.c_int32)), ("n_sites", C.c_int32), ("sites", C.POINTER(C.c_int32)),
+        ("ntraj", C.c_int32), ("traj_off", C.POINTER(C.c_int32)), ("ref_qpos", C.POINTER(C.c_double)), ("ref_qvel", C.POINTER(C.c_double)),
+        ("ref_root2site", C.POINTER(C.c_double)), ("ref_joint_quat", C.POINTER(C.c_double)),
+        ("future_steps", C.c_int32), ("control_timestep", C.c_double), ("time_limit", C.c_double), ("terminal_com_dist", C.c_double),
+        ("std", C.c_double * 4), ("weights", C.c_double * 4),
+        ("n_overrides", C.c_int32), ("override_qadr", C.POINTER(C.c_int32)), ("override_val", C.POINTER(C.c_double)),
+        ("inference_mode", C.c_int32),
+    ]
 
 
 class Spec(C.Structure):
@@ -125,6 +139,17 @@ def lib():
         getattr(L, s).restype = C.c_int
     L.ffe_eplog_last_error.restype = C.c_char_p
     L.ffe_eplog_last_error.argtypes = [vp]
+    L.ffe_walktask_create.argtypes = [C.c_void_p, C.c_size_t, C.POINTER(WalkTask), C.c_int, C.c_int, C.POINTER(vp)]
+    L.ffe_walktask_features.argtypes = [vp, dp, dp, C.c_int, dp, vp, vp, vp, vp]
+    L.ffe_walktask_evaluate.argtypes = [vp, dp, dp, ip, ip, C.c_int, vp, vp, ip, vp, C.c_int, vp]
+    L.ffe_walktask_reference_pose.argtypes = [vp, ip, ip, C.c_int, dp, dp, vp]
+    L.ffe_walktask_info.argtypes = [vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+    L.ffe_walktask_destroy.argtypes = [vp]
+    for s in ("ffe_walktask_create", "ffe_walktask_features", "ffe_walktask_evaluate", "ffe_walktask_reference_pose", "ffe_walktask_info",
+              "ffe_walktask_destroy"):
+        getattr(L, s).restype = C.c_int
+    L.ffe_walktask_last_error.restype = C.c_char_p
+    L.ffe_walktask_last_error.argtypes = [vp]
     L.ffe_nstep_last_error.restype = C.c_char_p
     L.ffe_nstep_last_error.argtypes = [vp]
     for s in ("ffe_nstep_create", "ffe_nstep_observe", "ffe_nstep_buffers", "ffe_nstep_destroy"):

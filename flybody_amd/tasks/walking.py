@@ -149,6 +149,36 @@ def synthetic_snippets(view: WalkModelView, n: int = 4, length: int = 200, dt: f
     return out
 
 
+def featurize(view: WalkModelView, qpos_rows, qvel_rows, off, device: int = 0) -> WalkRefSet:
+    """Raw pose rows (IK output: qpos [rows, 7 + J] root pose + tracked joint angles, qvel [rows, 6 + J], clips concatenated with
+    `off` [n + 1] their first rows) -> the four reference tables, the tracked features computed on the device by the float64
+    task-layer handle (`tasks/walk_tracker.py`) on the pose `full_qpos` builds from every row: what `synthetic_snippets` does
+    row by row in numpy.  Needs a HIP device."""
+    import torch
+
+    from .walk_tracker import WalkTracker
+
+    qpos_rows, qvel_rows = np.asarray(qpos_rows, dtype=np.float64), np.asarray(qvel_rows, dtype=np.float64)
+    off = np.asarray(off, dtype=np.int64)
+    J = len(view.mocap_jnt)
+    if qpos_rows.ndim != 2 or qpos_rows.shape[1] != 7 + J or qvel_rows.shape != (len(qpos_rows), 6 + J):
+        raise ValueError(f"featurize: qpos rows {qpos_rows.shape} / qvel rows {qvel_rows.shape}, expected [rows, {7 + J}] and [rows, {6 + J}]")
+    if off[0] != 0 or off[-1] != len(qpos_rows) or (np.diff(off) <= 0).any():
+        raise ValueError("featurize: off must rise from 0 to the number of rows")
+    full = np.tile(view.m.qpos0.astype(np.float64), (len(qpos_rows), 1))
+    full[:, :7] = qpos_rows[:, :7]
+    full[:, view.mocap_qadr] = qpos_rows[:, 7:]
+    full[:, view.retract_qadr] = view.retract_val
+    tr = WalkTracker(None, view, dtype="float64", device=device)
+    try:
+        ft = tr.features(torch.from_numpy(full), torch.zeros((len(full), view.nv), dtype=torch.float64))
+        r2s, jq = ft.root2site.cpu().numpy(), ft.joint_quat[:, 1:].cpu().numpy()
+    finally:
+        tr.close()
+    return WalkRefSet([{"qpos": qpos_rows[a:b], "qvel": qvel_rows[a:b], "root2site": r2s[a:b], "joint_quat": jq[a:b]}
+                       for a, b in zip(off[:-1], off[1:])])
+
+
 def save_npz(path: str, snippets, joint_names, site_names, timestep_seconds: float = 2e-3):
     """Ragged walking snippets in one file: rows concatenated + `traj_off`; names of the tracked joints / sites as the dataset
     gives them (`trajectory_loaders.py:217-223`)."""

@@ -338,6 +338,65 @@ int ffe_eplog_buffers(ffe_eplog_handle h, void **records_dev, long long **info_d
 int ffe_eplog_destroy(ffe_eplog_handle h);
 const char *ffe_eplog_last_error(ffe_eplog_handle h);
 
+/* ---- walk_imitation task layer: features, reward factors, termination bits and the kinematic observation columns of
+ * fly_envs.walk_imitation (vnl_ray/fly_envs.py:75-122, tasks/walk_imitation.py:24-191, tasks/rewards.py:9-111, tasks/base.py:237-261)
+ * as a pure function of (qpos, qvel, clip, step) - no physics.  Stands in for get_walker_features / reward_factors_deep_mimic, for
+ * the task observables ref_displacement / ref_root_quat and the walker observables appendages_pos / joints_pos / joints_vel /
+ * world_zaxis, and for the pose initialize_episode writes at reset.  The reference's walking dataset is not in its repository: which
+ * joints and sites are tracked comes from the caller (parity unpinned on that choice).  One wavefront per state row; no call
+ * allocates, reads back or synchronises, so every call can be captured into a HIP graph.  States come in the ffe_get_state layout:
+ * qpos double [N][nq], qvel double [N][nv]. */
+typedef struct ffe_walktask *ffe_walktask_handle;
+enum { FFE_WALKTASK_FLOAT64 = 1 };
+/* all host pointers, copied during create */
+typedef struct {
+  int32_t n_joints; const int32_t *joints;   /* tracked hinge joints (model joint indices); may be 0 */
+  int32_t n_sites; const int32_t *sites;     /* tracked sites (model site indices); may be 0 */
+  /* reference clips of individual lengths, rows concatenated (HDF5WalkingTrajectoryLoader.get_trajectory, trajectory_loaders.py:163-215);
+   * ntraj = 0: no reference, only ffe_walktask_features works */
+  int32_t ntraj; const int32_t *traj_off;    /* [ntraj + 1], traj_off[0] = 0 */
+  const double *ref_qpos;                    /* [rows][7 + n_joints] */
+  const double *ref_qvel;                    /* [rows][6 + n_joints] */
+  const double *ref_root2site;               /* [rows][n_sites][3] */
+  const double *ref_joint_quat;              /* [rows][n_joints][4] */
+  int32_t future_steps;                      /* fly_envs.py (64): preview rows after the current one */
+  double control_timestep, time_limit, terminal_com_dist;
+  double std[4], weights[4];                 /* com, qvel, root2site, joint_quat (rewards.py:96-102; walk_imitation.py: 20,1,1,1) */
+  int32_t n_overrides; const int32_t *override_qadr; const double *override_val; /* qpos written after the reference pose at reset
+                                                                                    (retract_wings, task_utils.py:117-122) */
+  int32_t inference_mode;                    /* walk_imitation.py:148-151: the reward is the constant 1 */
+} ffe_walk_task;
+/* flags: 0 = float32 kinematics and outputs, FFE_WALKTASK_FLOAT64 = the float64 instantiation (dataset featurisation).  The root
+ * position and every difference against it are float64 in both.  Refused with rc < 0 and a text in ffe_walktask_last_error(NULL):
+ * a null required pointer, a tracked joint that is not a hinge, a joint / site / override index out of range, a clip shorter than
+ * future_steps + 2 rows, a non-positive std or control_timestep, unknown flags, no such device. */
+int ffe_walktask_create(const void *model_blob, size_t blob_size, const ffe_walk_task *task, int flags, int device, ffe_walktask_handle *out);
+/* get_walker_features (rewards.py:36-61) of n states: com double [n][3], qvel [n][6 + J], root2site [n][S][3], joint_quat [n][1 + J][4]
+ * (the root quaternion heads it); the three typed outputs are float or double as the handle was created.  Any output may be NULL
+ * (skipped); qvel_dev may be NULL when qvel_out_dev is */
+int ffe_walktask_features(ffe_walktask_handle h, const double *qpos_dev, const double *qvel_dev, int n, double *com_dev, void *qvel_out_dev,
+                          void *root2site_dev, void *joint_quat_dev, void *stream);
+/* reward_factors_deep_mimic against get_reference_features(clip, step) and check_termination's task rules, for n states with their
+ * clip[n] and step[n] (int32): factors [n][4], reward [n] (their product, NaN -> 0; 1 in inference mode), term_bits int32 [n]
+ * (bit 0: |ref_root[step] - root| > terminal_com_dist; bit 1: step == episode_steps; bit 2: step outside [0, episode_steps] or clip
+ * outside [0, ntraj)), and the kinematic columns of the observation row written into obs_dev[n][obs_stride] at the offsets
+ * ffe_walktask_info reports (appendages_pos, joints_pos, joints_vel, ref_displacement, ref_root_quat, world_zaxis); the other columns
+ * of the row (sensors, activations) are left untouched.  Every reference row index is clamped to the clip's own rows.  Typed
+ * outputs are float or double as the handle; any output may be NULL.  obs_stride (elements) must be at least obs_dim */
+int ffe_walktask_evaluate(ffe_walktask_handle h, const double *qpos_dev, const double *qvel_dev, const int32_t *clip_dev, const int32_t *step_dev,
+                          int n, void *factors_dev, void *reward_dev, int32_t *term_bits_dev, void *obs_dev, int obs_stride, void *stream);
+/* the state initialize_episode builds (walk_imitation.py:112-121): qpos0, the root pose and the tracked joints of row `step` of the
+ * clip, then the overrides; zero velocity.  qpos double [n][nq], qvel double [n][nv]: exact copies, the root quaternion q / |q| as the
+ * position stage leaves it in qpos (mj_kinematics normalises it in place), rounded as that code rounds it; either may be NULL */
+int ffe_walktask_reference_pose(ffe_walktask_handle h, const int32_t *clip_dev, const int32_t *step_dev, int n, double *qpos_dev, double *qvel_dev,
+                                void *stream);
+/* dims int32[16]: 0 nq, 1 nv, 2 J, 3 S, 4 ntraj, 5 future_steps, 6 obs_dim, 7 off appendages_pos, 8 off joints_pos, 9 off joints_vel,
+ * 10 off ref_displacement, 11 off ref_root_quat, 12 off world_zaxis, 13 appendages, 14 observed joints, 15 float64 handle.
+ * episode_steps int32[ntraj] (host; may be NULL): min(len - future_steps - 1, round(time_limit / control_timestep) + 1) */
+int ffe_walktask_info(ffe_walktask_handle h, int32_t *dims, int32_t *episode_steps);
+int ffe_walktask_destroy(ffe_walktask_handle h);
+const char *ffe_walktask_last_error(ffe_walktask_handle h);
+
 #ifdef __cplusplus
 }
 #endif
