@@ -20,6 +20,7 @@ SYMBOLS = [
     "ffe_eplog_create", "ffe_eplog_arm", "ffe_eplog_observe", "ffe_eplog_buffers", "ffe_eplog_destroy", "ffe_eplog_last_error",
     "ffe_walktask_create", "ffe_walktask_features", "ffe_walktask_evaluate", "ffe_walktask_reference_pose", "ffe_walktask_info",
     "ffe_walktask_destroy", "ffe_walktask_last_error",
+    "ffe_create_walk_physics",
 ]
 
 
@@ -40,6 +41,10 @@ class FlightTask(C.Structure):
 class BallTask(C.Structure):
     _fields_ = [("control_timestep", C.c_double), ("time_limit_steps", C.c_int32), ("pad_first_obs", C.c_int32),
                 ("physics_flags", C.c_int32), ("canonical_actions", C.c_int32), ("clip_actions", C.c_int32)]
+
+
+class WalkPhysicsTask(C.Structure):
+    _fields_ = [("physics_flags", C.c_int32)]
 
 
 class WalkTask(C.Structure):
@@ -89,6 +94,8 @@ def lib():
     L.ffe_create_flight.argtypes = [C.c_void_p, C.c_size_t, C.POINTER(FlightTask), C.c_int, C.c_int, C.c_uint64, C.c_uint64, C.POINTER(vp)]
     L.ffe_create_walk_on_ball.restype = C.c_int
     L.ffe_create_walk_on_ball.argtypes = [C.c_void_p, C.c_size_t, C.POINTER(BallTask), C.c_int, C.c_int, C.POINTER(vp)]
+    L.ffe_create_walk_physics.restype = C.c_int
+    L.ffe_create_walk_physics.argtypes = [C.c_void_p, C.c_size_t, C.POINTER(WalkPhysicsTask), C.c_int, C.c_int, C.POINTER(vp)]
     L.ffe_get_act.argtypes = [vp, dp, vp]
     L.ffe_set_act.argtypes = [vp, dp, vp]
     L.ffe_get_act.restype = L.ffe_set_act.restype = C.c_int

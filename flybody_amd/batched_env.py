@@ -22,6 +22,8 @@ from .tasks.constants import _WING_PARAMS
 _ASSETS = os.path.join(os.path.dirname(os.path.abspath(__file__)), "assets")
 FLIGHT_BLOB = os.path.join(_ASSETS, "fly_flight.ffmb")
 BALL_BLOB = os.path.join(_ASSETS, "fly_ball.ffmb")
+WALK_BLOB = os.path.join(_ASSETS, "fly_walk.ffmb")
+FFE_NO_LIMIT, FFE_NO_CONTACT = 2, 64  # include/flybody_env.h
 
 
 # `env.validity()`: four int32 [B] views of one [B, 4] device buffer (include/flybody_env.h, ffe_get_validity)
@@ -392,3 +394,52 @@ class BatchedBallEnv(BatchedFlyEnv):
         assert tuple(act.shape) == (self.batch_size, self.spec.nu)
         self._check(self._L.ffe_set_act(self._h, act.data_ptr(), self._stream()))
         t.cuda.current_stream(self.device).synchronize()
+
+
+class BatchedWalkPhysics:
+    """B walking flies (`assets/fly_walk.ffmb`: free thorax, 6 + 102 dofs, 59 filtered actuators) advanced on one MI355X by
+    `ffe_physics_step` with constraints off: the smooth dynamics of `walk_imitation`.  Not an
+    environment: there is no reset, step, observation or reward - joint limits, floor contacts, sensors and the episode protocol are
+    not built yet, and `physics_flags` must contain FFE_NO_CONTACT | FFE_NO_LIMIT.  The handle starts at the model's `qpos0` at rest.
+
+    Tensor conventions are `BatchedBallEnv`'s: `get_state` returns float64 cuda tensors qpos[B, 109] = root position (float64 on the
+    device too), root quaternion, 102 hinges and qvel[B, 108] = root linear velocity (world frame), root angular velocity (body
+    frame), hinges; `set_state` takes the same and normalises the quaternion; `physics_step` takes float32 ctrl[B, 59]."""
+
+    task_kind = "walk_physics"
+
+    def __init__(self, *, batch_size: int, device: int = 0, physics_flags: int = FFE_NO_CONTACT | FFE_NO_LIMIT, blob_path: str = WALK_BLOB):
+        import torch
+
+        if not torch.cuda.is_available():
+            raise RuntimeError("BatchedWalkPhysics needs a HIP device (MI355X); there is no CPU fallback")
+        self._torch = torch
+        self._L = _capi.lib()
+        self.batch_size = int(batch_size)
+        self.device = torch.device("cuda", device)
+        with open(blob_path, "rb") as f:
+            blob = f.read()
+        task = _capi.WalkPhysicsTask(physics_flags=int(physics_flags))
+        h = C.c_void_p()
+        rc = self._L.ffe_create_walk_physics(blob, len(blob), C.byref(task), self.batch_size, device, C.byref(h))
+        if rc != 0:
+            raise RuntimeError("ffe_create_walk_physics: " + self._L.ffe_last_error(None).decode())
+        self._h = h
+        self.physics_flags = int(physics_flags)
+        self.spec = _capi.Spec()
+        self._check(self._L.ffe_spec(self._h, C.byref(self.spec)))
+        amin, amax = (C.c_float * self.spec.action_dim)(), (C.c_float * self.spec.action_dim)()
+        self._check(self._L.ffe_action_bounds(self._h, amin, amax))
+        self._action_min, self._action_max = np.array(amin[:], dtype=np.float32), np.array(amax[:], dtype=np.float32)
+
+    _check = BatchedFlyEnv._check
+    _stream = BatchedFlyEnv._stream
+    close = BatchedFlyEnv.close
+    __del__ = BatchedFlyEnv.__del__
+    raw_action_bounds = BatchedFlyEnv.raw_action_bounds
+    get_state = BatchedFlyEnv.get_state
+    set_state = BatchedFlyEnv.set_state
+    physics_step = BatchedFlyEnv.physics_step
+    get_task_state = BatchedFlyEnv.get_task_state
+    get_act = BatchedBallEnv.get_act
+    set_act = BatchedBallEnv.set_act

@@ -29,15 +29,6 @@
 namespace ffb {
 using namespace dm;
 
-enum { BF_NO_FLUID = 1, BF_NO_LIMIT = 2, BF_NO_DAMPER = 4, BF_NO_SPRING = 8, BF_NO_GRAVITY = 16, BF_NO_ACTUATION = 32,
-       BF_NO_CONTACT = 64, BF_NO_NOSLIP = 128, BF_NO_ADHESION = 256 };
-// Keeps the fully unrolled per-entry loops from being interleaved into one huge basic block of loads: without it the
-// scheduler hoists every entry's LDS reads to the top and the kernel needs > 500 VGPRs.
-#define ENTRY_FENCE() __builtin_amdgcn_sched_barrier(0)
-// Loop-invariant code motion otherwise precomputes every LDS address derived from the per-lane entry / slot words once per
-// launch and keeps ~150 of them alive across the substep loop; an opaque copy forces the (cheap) address math to stay local.
-__device__ __forceinline__ unsigned opq(unsigned x) { asm volatile("" : "+v"(x)); return x; }
-__device__ __forceinline__ int opq(int x) { asm volatile("" : "+v"(x)); return x; }
 #ifdef FFB_STAMPS
 __device__ unsigned long long g_bstamps[24];
 #define BSTAMP(k) do { const unsigned long long t_ = __builtin_amdgcn_s_memtime(); c.st_acc[k] += t_ - c.st_t0; c.st_t0 = t_; } while (0)
@@ -153,223 +144,13 @@ struct Ctx {
 #endif
 };
 
-__device__ __forceinline__ bool slot_on(const Ctx &c, int s) { return c.sdof[s] >= 0; }
-__device__ __forceinline__ int l_parent(const Ctx &c) { return (int)(c.lpack & 0xffu) - 1; }
-__device__ __forceinline__ int l_ndof(const Ctx &c) { return (int)((c.lpack >> 12) & 0x3u); }
-// The tables are read through an address-space-1 pointer: a generic pointer makes every table read a FLAT load, which
-// counts against the LDS wait counter as well, so each LDS wait would also wait for the schedule prefetch.
-typedef const BallModel FFE_GLOBAL *ModelPtr;
-__device__ __forceinline__ const BallModel FFE_GLOBAL &model(const Ctx &c) {
-  ModelPtr m = (ModelPtr)c.M;
-  asm volatile("" : "+s"(m));
-  return *m;
-}
 
-// ------------------------------------------------------------------------------------------------ block factorisation
-// mj: mj_factorI on M's 12 independent blocks, all blocks in lock step (step s eliminates every block's s-th pivot from the
-// leaf end).  The matrix lives in LDS, so any lane can apply any update: the host lays the ~2300 updates
-//   L[e] -= L[ki] * L[kj] / L[kk]        (e = (i, j), i a proper ancestor of the pivot k; values stay unscaled until the end)
-// out in step order as `nfs` slots of 64 independent updates (ball_model.hpp), read coalesced and one slot ahead.
-// LDS operations of a wave complete in issue order, which is all the ordering the steps need.
-__device__ __forceinline__ void factor2(Ctx &c) {
-  // factorises M into T.Lm and M + diag(T.dadd) into T.Lh in one pass over the schedule (same elimination order, so the
-  // schedule words, address arithmetic and control flow are shared)
-  BTile &T = *c.T;
-  const BallModel FFE_GLOBAL &M = model(c);
-  const int lane = c.lane;
-#pragma unroll
-  for (int t = 0; t < ECAP; t++) {
-    const unsigned ea = M.ent_a[t][lane];
-    if (ea >> 31) {
-      const unsigned i = ea & 0xffu, j = (ea >> 8) & 0xffu, adr = (ea >> 16) & 0x3ffu;
-      const float vv = T.Mq[adr];
-      T.Lm[adr] = vv;
-      T.Lh[adr] = i == j ? vv + T.dadd[i] : vv;
-    }
-  }
-  DM_SYNC();
-  // Schedule words are fetched one group of four slots ahead (tables are zero padded past nfs).  No fence inside the loop:
-  // the LDS accesses of consecutive slots may alias, so the compiler keeps their order, and the hardware executes a
-  // wave's LDS operations in issue order.
-  const int nfs = M.nfs;
-  unsigned wa[4], wb[4];
-#pragma unroll
-  for (int q = 0; q < 4; q++) { wa[q] = M.fac_a[q][lane]; wb[q] = M.fac_b[q][lane]; }
-#pragma unroll 1
-  for (int base = 0; base < nfs; base += 4) {
-    unsigned ca[4], cb[4];
-#pragma unroll
-    for (int q = 0; q < 4; q++) { ca[q] = wa[q]; cb[q] = wb[q]; }
-#pragma unroll
-    for (int q = 0; q < 4; q++) { wa[q] = M.fac_a[base + 4 + q][lane]; wb[q] = M.fac_b[base + 4 + q][lane]; }
-#pragma unroll
-    for (int q = 0; q < 4; q++) {
-      const unsigned a = ca[q], b = cb[q];
-      if (a >> 31) {
-        const unsigned akk = (a >> 10) & 0x3ffu, aki = (a >> 20) & 0x3ffu, akj = b & 0x3ffu, ae = a & 0x3ffu;
-        const float mkk = T.Lm[akk], mki = T.Lm[aki], mkj = T.Lm[akj], hkk = T.Lh[akk], hki = T.Lh[aki], hkj = T.Lh[akj];
-        T.Lm[ae] -= mki * mkj * frcp(mkk);
-        T.Lh[ae] -= hki * hkj * frcp(hkk);
-      }
-    }
-  }
-  DM_SYNC();
-#pragma unroll
-  for (int t = 0; t < ECAP; t++) {
-    const unsigned ea = M.ent_a[t][lane];
-    if ((ea >> 31) && (ea & 0xffu) == ((ea >> 8) & 0xffu)) {
-      T.dinv_m[ea & 0xffu] = frcp(T.Lm[(ea >> 16) & 0x3ffu]);
-      T.dinv_h[ea & 0xffu] = frcp(T.Lh[(ea >> 16) & 0x3ffu]);
-    }
-  }
-  DM_SYNC();
-#pragma unroll
-  for (int t = 0; t < ECAP; t++) {
-    const unsigned ea = M.ent_a[t][lane];
-    if ((ea >> 31) && (ea & 0xffu) != ((ea >> 8) & 0xffu)) {
-      T.Lm[(ea >> 16) & 0x3ffu] *= T.dinv_m[ea & 0xffu];
-      T.Lh[(ea >> 16) & 0x3ffu] *= T.dinv_h[ea & 0xffu];
-    }
-  }
-  DM_SYNC();
-}
+}  // namespace ffb
 
-// mj: mj_solveLD on T.X4 (four right-hand sides at once): rows leaf -> root, D^-1, columns root -> leaf, from the two
-// schedules p1 / p2 (slots of 64 independent updates in step order)
-__device__ __forceinline__ void solve4(Ctx &c, const float *L, const float *dinv) {
-  BTile &T = *c.T;
-  const BallModel FFE_GLOBAL &M = model(c);
-  const int lane = c.lane;
-  {
-    const int n = M.np1;
-    unsigned wq[4];
-#pragma unroll
-    for (int q = 0; q < 4; q++) wq[q] = M.p1[q][lane];
-#pragma unroll 1
-    for (int base = 0; base < n; base += 4) {
-      unsigned cw[4];
-#pragma unroll
-      for (int q = 0; q < 4; q++) cw[q] = wq[q];
-#pragma unroll
-      for (int q = 0; q < 4; q++) wq[q] = M.p1[base + 4 + q][lane];
-#pragma unroll
-      for (int q = 0; q < 4; q++) {
-        const unsigned w = cw[q];
-        if (w >> 31) {
-          const unsigned i = (w >> 10) & 0x7fu, j = (w >> 17) & 0x7fu;
-          const float l = L[w & 0x3ffu];
-          const float4 xi = T.X4[i];
-          float4 xj = T.X4[j];
-          xj.x -= l * xi.x; xj.y -= l * xi.y; xj.z -= l * xi.z; xj.w -= l * xi.w;
-          T.X4[j] = xj;
-        }
-      }
-    }
-    DM_SYNC();
-  }
-  for (int f = lane; f < ND; f += 64) {
-    const float dv = dinv[f];
-    float4 x = T.X4[f];
-    x.x *= dv; x.y *= dv; x.z *= dv; x.w *= dv;
-    T.X4[f] = x;
-  }
-  DM_SYNC();
-  {
-    const int n = M.np2;
-    unsigned wq[4];
-#pragma unroll
-    for (int q = 0; q < 4; q++) wq[q] = M.p2[q][lane];
-#pragma unroll 1
-    for (int base = 0; base < n; base += 4) {
-      unsigned cw[4];
-#pragma unroll
-      for (int q = 0; q < 4; q++) cw[q] = wq[q];
-#pragma unroll
-      for (int q = 0; q < 4; q++) wq[q] = M.p2[base + 4 + q][lane];
-#pragma unroll
-      for (int q = 0; q < 4; q++) {
-        const unsigned w = cw[q];
-        if (w >> 31) {
-          const unsigned i = (w >> 10) & 0x7fu, j = (w >> 17) & 0x7fu;
-          const float l = L[w & 0x3ffu];
-          const float4 xj = T.X4[j];
-          float4 xi = T.X4[i];
-          xi.x -= l * xj.x; xi.y -= l * xj.y; xi.z -= l * xj.z; xi.w -= l * xj.w;
-          T.X4[i] = xi;
-        }
-      }
-    }
-    DM_SYNC();
-  }
-}
+#include "leg_dyn.hpp"  // BF_* flags, slot_on / l_parent / l_ndof / model, factor2 / solve4 / solve_dual
 
-// Two single-right-hand-side solves with two factors of the same structure in one pass over the schedules:
-// T.X4[.].x <- (L_A D_A L_A')^-1 x, T.X4[.].y <- (L_B D_B L_B')^-1 y   (final acceleration with M, Euler with M + h B)
-__device__ __forceinline__ void solve_dual(Ctx &c, const float *LA, const float *dinvA, const float *LB, const float *dinvB) {
-  BTile &T = *c.T;
-  const BallModel FFE_GLOBAL &M = model(c);
-  const int lane = c.lane;
-  {
-    const int n = M.np1;
-    unsigned wq[4];
-#pragma unroll
-    for (int q = 0; q < 4; q++) wq[q] = M.p1[q][lane];
-#pragma unroll 1
-    for (int base = 0; base < n; base += 4) {
-      unsigned cw[4];
-#pragma unroll
-      for (int q = 0; q < 4; q++) cw[q] = wq[q];
-#pragma unroll
-      for (int q = 0; q < 4; q++) wq[q] = M.p1[base + 4 + q][lane];
-#pragma unroll
-      for (int q = 0; q < 4; q++) {
-        const unsigned w = cw[q];
-        if (w >> 31) {
-          const unsigned i = (w >> 10) & 0x7fu, j = (w >> 17) & 0x7fu;
-          const float la = LA[w & 0x3ffu], lb = LB[w & 0x3ffu];
-          const float4 xi = T.X4[i];
-          float4 xj = T.X4[j];
-          xj.x -= la * xi.x; xj.y -= lb * xi.y;
-          T.X4[j] = xj;
-        }
-      }
-    }
-    DM_SYNC();
-  }
-  for (int f = lane; f < ND; f += 64) {
-    float4 x = T.X4[f];
-    x.x *= dinvA[f]; x.y *= dinvB[f];
-    T.X4[f] = x;
-  }
-  DM_SYNC();
-  {
-    const int n = M.np2;
-    unsigned wq[4];
-#pragma unroll
-    for (int q = 0; q < 4; q++) wq[q] = M.p2[q][lane];
-#pragma unroll 1
-    for (int base = 0; base < n; base += 4) {
-      unsigned cw[4];
-#pragma unroll
-      for (int q = 0; q < 4; q++) cw[q] = wq[q];
-#pragma unroll
-      for (int q = 0; q < 4; q++) wq[q] = M.p2[base + 4 + q][lane];
-#pragma unroll
-      for (int q = 0; q < 4; q++) {
-        const unsigned w = cw[q];
-        if (w >> 31) {
-          const unsigned i = (w >> 10) & 0x7fu, j = (w >> 17) & 0x7fu;
-          const float la = LA[w & 0x3ffu], lb = LB[w & 0x3ffu];
-          const float4 xj = T.X4[j];
-          float4 xi = T.X4[i];
-          xi.x -= la * xj.x; xi.y -= lb * xj.y;
-          T.X4[i] = xi;
-        }
-      }
-    }
-    DM_SYNC();
-  }
-}
+namespace ffb {
+
 
 // ------------------------------------------------------------------------------------------------ impedance
 // mj: getimpedance (margin folded into `x` by the caller: x = |pos - margin|)
@@ -885,203 +666,12 @@ __device__ __forceinline__ float self_gather(const Ctx &c, unsigned sbl, int f, 
 }
 
 // ------------------------------------------------------------------------------------------------ stage 1
-__device__ __forceinline__ void stage1(Ctx &c) {
+template <class C>  // (a template so that the fragment's free-root branches are discarded, not compiled)
+__device__ __forceinline__ void stage1(C &c) {
+  constexpr bool FREE_ROOT = false;
   BTile &T = *c.T;
   const BallModel FFE_GLOBAL &M = model(c);
-  const int lane = c.lane, parent = l_parent(c), ndof = l_ndof(c);
-  const V3 c0 = {M.thorax_pos[0], M.thorax_pos[1], M.thorax_pos[2]};
-  const V3 pos = {M.l_pos[0][lane], M.l_pos[1][lane], M.l_pos[2][lane]};
-  const Q4 quat = {M.l_quat[0][lane], M.l_quat[1][lane], M.l_quat[2][lane], M.l_quat[3][lane]};
-  V3 axis[3];
-#pragma unroll
-  for (int s = 0; s < 3; s++) axis[s] = {M.s_axis[0][s][lane], M.s_axis[1][s][lane], M.s_axis[2][s][lane]};
-  // Every joint of this model sits at its body's origin (checked on the host), so a link's origin does not depend on
-  // its own joint angles and everything that does not involve the parent is done once, before the tree pass:
-  // the link's orientation relative to its parent after 0, 1, 2, 3 of its joints and the joint axes in the parent frame.
-  Q4 qrel = quat;
-  V3 axp[3];
-#pragma unroll
-  for (int s = 0; s < 3; s++) {
-    axp[s] = qrot(qrel, axis[s]);
-    if (s < ndof) {
-      float sn, cs;
-      fsincos(0.5f * c.q[s], &sn, &cs);
-      qrel = qmul(qrel, Q4{cs, axis[s].x * sn, axis[s].y * sn, axis[s].z * sn});
-    }
-  }
-  // ---- mj: mj_kinematics by pointer jumping instead of one sweep per tree level: after round r the pose (xp, xq) is
-  //      relative to the frame above the link's 2^(r+1)-th ancestor; three rounds cover the deepest chain (8 links) with every
-  //      lane at work in every round (a level sweep runs its body once per level with one level's lanes active).
-  const unsigned tree = M.l_tree[lane];
-  const int sub = (int)(tree & 0xffu), anc2 = (int)((tree >> 8) & 0xffu) - 1, anc4 = (int)((tree >> 16) & 0xffu) - 1;
-  V3 axw[3], anc[3];
-  {
-    V3 xp = pos;
-    Q4 xq = qrel;
-#pragma unroll
-    for (int r = 0; r < 3; r++) {
-      const int a = r == 0 ? parent : (r == 1 ? anc2 : anc4);
-      float *o = T.lk[lane];
-      o[0] = xp.x; o[1] = xp.y; o[2] = xp.z; o[3] = xq.w; o[4] = xq.x; o[5] = xq.y; o[6] = xq.z;
-      DM_SYNC();
-      if (a >= 0) {
-        const float *p = T.lk[a];
-        const V3 pp = {p[0], p[1], p[2]};
-        const Q4 pq = {p[3], p[4], p[5], p[6]};
-        xp = pp + mv(q2m(pq), xp);
-        xq = qmul(pq, xq);
-      }
-      DM_SYNC();
-    }
-    xq = qnormalize(xq);
-    c.xp = xp; c.xq = xq;
-    float *o = T.lk[lane];
-    o[3] = xq.w; o[4] = xq.x; o[5] = xq.y; o[6] = xq.z;
-    DM_SYNC();
-    Q4 pq = {1.f, 0.f, 0.f, 0.f};
-    if (parent >= 0) { const float *p = T.lk[parent]; pq = {p[3], p[4], p[5], p[6]}; }
-    const M3 Rp = q2m(pq);
-#pragma unroll
-    for (int s = 0; s < 3; s++) { axw[s] = mv(Rp, axp[s]); anc[s] = xp; }
-    DM_SYNC();
-  }
-  BSTAMP(0);  // kinematics
-  const M3 xmat = q2m(c.xq);
-  c.xip = c.xp + mv(xmat, V3{M.l_ipos[0][lane], M.l_ipos[1][lane], M.l_ipos[2][lane]});
-  const M3 ximat = q2m(qmul(c.xq, Q4{M.l_iquat[0][lane], M.l_iquat[1][lane], M.l_iquat[2][lane], M.l_iquat[3][lane]}));
-  c.mass = M.l_mass[lane];
-  // ---- mj: mj_comPos with the fixed thorax origin as the reference point
-  const I10 cinert = inert_com(V3{M.l_inertia[0][lane], M.l_inertia[1][lane], M.l_inertia[2][lane]}, ximat, c.xip - c0, c.mass);
-  S6 cdof[3];
-#pragma unroll
-  for (int s = 0; s < 3; s++) cdof[s] = s < ndof ? mk6(axw[s], cross(axw[s], c0 - anc[s])) : zero6();
-  // ---- mj: mj_comVel + the acceleration half of mj_rne.  All motion vectors refer to the fixed thorax origin, so a link's
-  //      velocity is the plain sum of v * cdof over its ancestor path: path sums by pointer jumping (published inclusive,
-  //      the exclusive one - the parent's velocity - kept privately), the velocity products locally, then the same path
-  //      sum for the bias accelerations.
-  {
-    S6 dv = zero6();
-#pragma unroll
-    for (int s = 0; s < 3; s++) if (s < ndof) dv = dv + c.v[s] * cdof[s];
-    S6 sv = dv, pv = zero6();
-#pragma unroll
-    for (int r = 0; r < 3; r++) {
-      const int a = r == 0 ? parent : (r == 1 ? anc2 : anc4);
-      st6(T.lk[lane], sv);
-      DM_SYNC();
-      if (a >= 0) { const S6 t = ld6(T.lk[a]); sv = sv + t; pv = pv + t; }
-      DM_SYNC();
-    }
-    S6 da = zero6();
-#pragma unroll
-    for (int s = 0; s < 3; s++) {
-      if (s < ndof) {
-        const S6 cdd = cross_motion(pv, cdof[s]);
-        pv = pv + c.v[s] * cdof[s];
-        da = da + c.v[s] * cdd;
-      }
-    }
-    c.cvel = pv;
-#pragma unroll
-    for (int r = 0; r < 3; r++) {
-      const int a = r == 0 ? parent : (r == 1 ? anc2 : anc4);
-      st6(T.lk[lane], da);
-      DM_SYNC();
-      if (a >= 0) da = da + ld6(T.lk[a]);
-      DM_SYNC();
-    }
-    da.l2 += (c.flags & BF_NO_GRAVITY) ? 0.f : -M.gz;
-    c.caccb = da;
-  }
-  BSTAMP(1);  // velocities + bias accelerations
-  // ---- body forces: rigid-body bias (mj_rne) minus inertia-box drag (mj_inertiaBoxFluidModel), about c0
-  S6 ftot;
-  {
-    const S6 t1 = mul_inert(cinert, c.caccb), t2 = mul_inert(cinert, c.cvel);
-    ftot = t1 + cross_force(c.cvel, t2);
-    if (!(c.flags & BF_NO_FLUID)) {
-      float fl[8];
-#pragma unroll
-      for (int k = 0; k < 8; k++) fl[k] = M.l_fl[k][lane];
-      const V3 r = c.xip - c0;
-      const V3 wl = mtv(ximat, ang(c.cvel)), vl = mtv(ximat, lin(c.cvel) + cross(ang(c.cvel), r));
-      const V3 Tl = {-fl[0] * wl.x - fl[5] * fabsf(wl.x) * wl.x, -fl[0] * wl.y - fl[6] * fabsf(wl.y) * wl.y, -fl[0] * wl.z - fl[7] * fabsf(wl.z) * wl.z};
-      const V3 Fl = {-fl[1] * vl.x - fl[2] * fabsf(vl.x) * vl.x, -fl[1] * vl.y - fl[3] * fabsf(vl.y) * vl.y, -fl[1] * vl.z - fl[4] * fabsf(vl.z) * vl.z};
-      const V3 Tw = mv(ximat, Tl), Fw = mv(ximat, Fl);
-      ftot = ftot - mk6(Tw + cross(r, Fw), Fw);
-    }
-  }
-  // ---- subtree sums (mj_crb's composite inertia, then mj_rne's backward pass), leaves first
-  //      Links are numbered depth first, so the subtree of link l is lanes l .. l + sub - 1: every lane gathers its own
-  //      range from one publication of the per-link values (no level order, no barrier inside the loop).
-  I10 crb = cinert;
-  const int maxsub = M.maxsub;
-  st10(T.lk[lane], cinert);
-  DM_SYNC();
-#pragma unroll 1
-  for (int t = 1; t < maxsub; t++) if (t < sub) crb = add10(crb, ld10(T.lk[lane + t]));
-  DM_SYNC();
-  st6(T.lk[lane], ftot);
-  DM_SYNC();
-#pragma unroll 1
-  for (int t = 1; t < maxsub; t++) if (t < sub) ftot = ftot + ld6(T.lk[lane + t]);
-  DM_SYNC();
-  BSTAMP(2);  // body forces + subtree sums
-  // ---- smooth joint forces without actuation: springs, dampers, -(bias - drag)
-#pragma unroll
-  for (int s = 0; s < 3; s++) {
-    float f = 0.f;
-    if (s < ndof) {
-      if (!(c.flags & BF_NO_SPRING)) f -= M.s_stiff[s][lane] * (c.q[s] - M.s_sref[s][lane]);
-      if (!(c.flags & BF_NO_DAMPER)) f -= M.s_damp[s][lane] * c.v[s];
-      f -= dot6(cdof[s], ftot);
-    }
-    c.fnb[s] = f;
-  }
-  if (c.xh) {  // halteres: closed form (see ball_model.hpp)
-    float sn, cs;
-    fsincos(c.q[2], &sn, &cs);
-    float f = 0.f;
-    if (!(c.flags & BF_NO_SPRING)) f -= M.s_stiff[2][lane] * (c.q[2] - M.s_sref[2][lane]);
-    if (!(c.flags & BF_NO_DAMPER)) f -= M.s_damp[2][lane] * c.v[2];
-    if (!(c.flags & BF_NO_GRAVITY)) f += M.x_Gc[lane] * cs + M.x_Gs[lane] * sn;
-    if (!(c.flags & BF_NO_FLUID)) f -= M.x_cv[lane] * c.v[2] + M.x_cq[lane] * fabsf(c.v[2]) * c.v[2];
-    c.fnb[2] = f;
-  }
-  // ball: isotropic sphere about its centre, only the box drag acts (mj_inertiaBoxFluidModel in the inertial frame)
-  {
-    V3 tau = {0.f, 0.f, 0.f};
-    if (!(c.flags & BF_NO_FLUID)) {
-      const M3 Ri = q2m(Q4{M.b_iquat[0], M.b_iquat[1], M.b_iquat[2], M.b_iquat[3]});
-      const V3 wl = mtv(Ri, c.bw);
-      const V3 Tl = {-M.b_fl[0] * wl.x - M.b_fl[5] * fabsf(wl.x) * wl.x, -M.b_fl[0] * wl.y - M.b_fl[6] * fabsf(wl.y) * wl.y, -M.b_fl[0] * wl.z - M.b_fl[7] * fabsf(wl.z) * wl.z};
-      tau = mv(Ri, Tl);
-    }
-    c.btau = tau;
-  }
-  // ---- mj: mj_crb joint-space inertia, one entry per (lane, slot t)
-#pragma unroll
-  for (int s = 0; s < 3; s++) {
-    if (s < ndof) { st6(T.F[opq(c.sdof[s])], mul_inert(crb, cdof[s])); st6(T.C[opq(c.sdof[s])], cdof[s]); }
-  }
-  if (c.xh) { st6(T.F[c.sdof[2]], S6{M.x_M[lane], 0.f, 0.f, 0.f, 0.f, 0.f}); st6(T.C[c.sdof[2]], S6{1.f, 0.f, 0.f, 0.f, 0.f, 0.f}); }
-#pragma unroll
-  for (int s = 0; s < 3; s++) if (slot_on(c, s)) T.dadd[opq(c.sdof[s])] = (c.flags & BF_NO_DAMPER) ? 0.f : M.h * M.s_damp[s][lane];
-  DM_SYNC();
-#pragma unroll
-  for (int t = 0; t < ECAP; t++) {
-    const unsigned ea = M.ent_a[t][lane];
-    if (ea >> 31) {
-      const unsigned i = ea & 0xffu, j = (ea >> 8) & 0xffu;
-      float mij = dot6(ld6(T.C[j]), ld6(T.F[i]));
-      if (i == j) mij += M.d_arm[i];
-      T.Mq[(ea >> 16) & 0x3ffu] = mij;
-    }
-  }
-  DM_SYNC();
-  BSTAMP(3);  // joint forces + inertia assembly
-  factor2(c);
-  BSTAMP(4);  // factor M and M + h B
+#include "leg_stage1.inc"
   // ---- mj: mj_collision, ball (geom1, sphere) against this link's capsule: mjc_SphereCapsule
   bool hit = false;
   float dist = 0.f, margin = 0.f, gap = 0.f;

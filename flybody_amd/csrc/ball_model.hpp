@@ -176,8 +176,12 @@ struct BallHost {
   int nq = 106, nv = 105;
 };
 
-inline BallHost build_ball_model(const Blob &b) {
-  using namespace detail;
+// One builder for both fly models: `walk` = false is the tethered fly on the ball (fly_ball.ffmb), `walk` = true the fly whose thorax
+// hangs on a free joint (fly_walk.ffmb, walk_model.hpp): the same 64 links + 2 halteres in the same hinge order, dof offset 6
+// instead of 3, link frames relative to the thorax frame instead of the world, no ball and (in this build) no collision tables.
+namespace detail {
+inline BallHost build_fly_model(const Blob &b, const bool walk) {
+  const int off = walk ? 6 : 3;  // oracle dofs ahead of the hinges: free joint / ball joint
   BallHost H;
   BallModel &M = H.m;
   std::memset(&M, 0, sizeof(M));
@@ -194,12 +198,19 @@ inline BallHost build_ball_model(const Blob &b) {
   const Tensor &dpar = b.get("dof_parentid"), &ddamp = b.get("dof_damping"), &darm = b.get("dof_armature"), &dinvw = b.get("dof_invweight0"),
                &dM0 = b.get("dof_M0"), &djnt = b.get("dof_jntid"), &dbody = b.get("dof_bodyid");
   const int nb = (int)bpar.count, nv = (int)dpar.count, njnt = (int)jtype.count;
-  if (nv != ND + 3) throw std::runtime_error("ball model: expected 105 dofs");
+  if (nv != ND + off) throw std::runtime_error(walk ? "walk model: expected 108 dofs" : "ball model: expected 105 dofs");
   // ---- identify ball, thorax, halteres
   int ball = -1, thorax = (int)b.get("site").f(0);
   for (int j = 0; j < njnt; j++) if (jtype.i(j) == 1) ball = b.get("jnt_bodyid").i(j);
+  if (walk) {
+    if (ball >= 0) throw std::runtime_error("walk model: unexpected ball joint");
+    if (thorax != 1 || bpar.i(thorax) != 0 || bjnum.i(thorax) != 1 || jtype.i(bjadr.i(thorax)) != 0 || jdadr.i(bjadr.i(thorax)) != 0 ||
+        jqadr.i(bjadr.i(thorax)) != 0)
+      throw std::runtime_error("walk model: the thorax must be the first body and hang on the model's first joint, a free joint");
+  } else {
   if (ball != 1 || jdadr.i(bjadr.i(ball)) != 0) throw std::runtime_error("ball model: the ball joint must come first");
   if (bjnum.i(thorax) != 0 || bpar.i(thorax) != 0) throw std::runtime_error("ball model: thorax must be fixed to the world");
+  }
   std::vector<int> nchild(nb, 0);
   for (int i = 1; i < nb; i++) nchild[bpar.i(i)]++;
   std::vector<int> lane_of(nb, -1), halt;
@@ -215,8 +226,8 @@ inline BallHost build_ball_model(const Blob &b) {
   }
   if (nl != NL || halt.size() != 2) throw std::runtime_error("ball model: expected 64 links + 2 halteres");
   double tpos[3], tquat[4];
-  for (int k = 0; k < 3; k++) tpos[k] = bpos.f(3 * thorax + k);
-  for (int k = 0; k < 4; k++) tquat[k] = bquat.f(4 * thorax + k);
+  for (int k = 0; k < 3; k++) tpos[k] = walk ? 0.0 : bpos.f(3 * thorax + k);  // (walk: everything is expressed in the thorax frame)
+  for (int k = 0; k < 4; k++) tquat[k] = walk ? (k == 0 ? 1.0 : 0.0) : bquat.f(4 * thorax + k);
   for (int k = 0; k < 3; k++) M.thorax_pos[k] = (float)tpos[k];
   for (int k = 0; k < 4; k++) M.thorax_quat[k] = (float)tquat[k];
   {
@@ -232,6 +243,7 @@ inline BallHost build_ball_model(const Blob &b) {
   const Tensor &binvw = b.get("body_invweight0");
   int ball_geom = -1;
   for (int g = 0; g < (int)gbody.count; g++) if (gbody.i(g) == ball) ball_geom = g;
+  if (!walk) {
   if (ball_geom < 0 || gtype.i(ball_geom) != 2) throw std::runtime_error("ball model: ball sphere geom missing");
   M.b_radius = (float)gsize.f(3 * ball_geom);
   for (int k = 0; k < 3; k++) M.b_center[k] = (float)bpos.f(3 * ball + k);
@@ -241,6 +253,7 @@ inline BallHost build_ball_model(const Blob &b) {
     double box[3] = {bbox.f(3 * ball), bbox.f(3 * ball + 1), bbox.f(3 * ball + 2)};
     ffe::BoxCoef c = ffe::box_coefs(box, rho, beta);
     for (int k = 0; k < 8; k++) M.b_fl[k] = c.c[k];
+  }
   }
   // ---- links
   int maxdepth = 0;
@@ -281,7 +294,7 @@ inline BallHost build_ball_model(const Blob &b) {
   M.maxdepth = maxdepth;
   // ---- dof slots
   auto fill_slot = [&](int s, int l, int j) {
-    int od = jdadr.i(j), f = od - 3, qa = jqadr.i(j);
+    int od = jdadr.i(j), f = od - off, qa = jqadr.i(j);
     M.s_dof[s][l] = f;
     M.s_stiff[s][l] = (float)jstiff.f(j); M.s_sref[s][l] = (float)qspring.f(qa); M.s_damp[s][l] = (float)ddamp.f(od);
     M.s_arm[s][l] = (float)darm.f(od); M.s_lo[s][l] = (float)jrange.f(2 * j); M.s_hi[s][l] = (float)jrange.f(2 * j + 1);
@@ -356,9 +369,9 @@ inline BallHost build_ball_model(const Blob &b) {
   int adr = 0, nblk = 0;
   std::vector<int> blk_start;
   for (int f = 0; f < ND; f++) {
-    int p = dpar.i(f + 3);
-    par[f] = p < 0 ? -1 : p - 3;
-    if (p >= 0 && p < 3) throw std::runtime_error("ball model: fly dof parented to the ball");
+    int p = dpar.i(f + off);
+    par[f] = (p < 0 || (walk && p < off)) ? -1 : p - off;  // (walk: the six root dofs are handled apart, the blocks stay the tethered fly's)
+    if (!walk && p >= 0 && p < 3) throw std::runtime_error("ball model: fly dof parented to the ball");
     madr[f] = adr;
     depth[f] = par[f] < 0 ? 1 : depth[par[f]] + 1;
     adr += depth[f];
@@ -369,10 +382,10 @@ inline BallHost build_ball_model(const Blob &b) {
     amask[f] = (1u << li[f]) | (par[f] < 0 ? 0u : amask[par[f]]);
     if (li[f] >= NSTEP) throw std::runtime_error("ball model: block larger than 14 dofs");
     M.d_parent[f] = (short)par[f]; M.d_madr[f] = (short)madr[f]; M.d_blk[f] = (short)blk[f]; M.d_li[f] = (short)li[f];
-    M.d_amask[f] = (unsigned short)amask[f]; M.d_arm[f] = (float)darm.f(f + 3);
+    M.d_amask[f] = (unsigned short)amask[f]; M.d_arm[f] = (float)darm.f(f + off);
   }
   if (nblk > NBLK || adr > NMMAX) throw std::runtime_error("ball model: inertia structure exceeds capacities");
-  for (int l = 0; l < NL; l++) if (M.x_on[l]) M.d_arm[M.s_dof[2][l]] = 0.f;  // x_M already holds the haltere armature
+  for (int l = 0; l < NL; l++) if (M.x_on[l] && !walk) M.d_arm[M.s_dof[2][l]] = 0.f;  // x_M already holds the haltere armature
   M.nM = adr; M.nblk = nblk;
   blk_start.push_back(ND);
   // entries of M with the elimination steps that touch them
@@ -456,8 +469,8 @@ inline BallHost build_ball_model(const Blob &b) {
     M.l_nchain[l] = (int)ch.size();
     for (int k = 0; k < NCH; k++) M.l_chain[k][l] = k < (int)ch.size() ? ch[k] : -1;
   }
-  const double bfric = gfric.f(3 * ball_geom), bmix = gsolmix.f(ball_geom);
-  for (int g = 0; g < (int)gbody.count; g++) {
+  const double bfric = walk ? 0.0 : gfric.f(3 * ball_geom), bmix = walk ? 0.0 : gsolmix.f(ball_geom);
+  for (int g = 0; !walk && g < (int)gbody.count; g++) {
     int l = lane_of[gbody.i(g)];
     if (l < 0) continue;
     int ty = gtype.i(g);
@@ -513,7 +526,7 @@ inline BallHost build_ball_model(const Blob &b) {
     M.a_flimited[a] = afl.i(a); M.a_flo[a] = (float)afr.f(2 * a); M.a_fhi[a] = (float)afr.f(2 * a + 1);
     M.a_tau[a] = (float)std::max(1e-15, adp.f(a)); M.a_action[a] = aact.i(a); M.a_link[a] = -1;
     auto bind = [&](int od, double coef, int which) {
-      int f = od - 3, l = slot_lane[f], s = slot_idx[f];
+      int f = od - off, l = f < 0 ? -1 : slot_lane[f], s = f < 0 ? -1 : slot_idx[f];
       if (f < 0 || l < 0) throw std::runtime_error("ball model: actuator on an unknown dof");
       if (M.s_act[which][s][l] >= 0) throw std::runtime_error("ball model: two actuators of a kind on one dof");
       M.s_act[which][s][l] = a; M.s_actcoef[which][s][l] = (float)coef;
@@ -529,10 +542,10 @@ inline BallHost build_ball_model(const Blob &b) {
   for (size_t k = 0; k < amin.count; k++) { H.action_min[k] = (float)amin.f(k); H.action_max[k] = (float)amax.f(k); M.act_lo[k] = H.action_min[k]; M.act_hi[k] = H.action_max[k]; }
   const Tensor &oj = b.get("obs_jnt");
   if ((int)oj.count != NOBSJ) throw std::runtime_error("ball model: expected 85 observable joints");
-  for (int k = 0; k < NOBSJ; k++) M.obs_dof[k] = jdadr.i(oj.i(k)) - 3;
+  for (int k = 0; k < NOBSJ; k++) M.obs_dof[k] = jdadr.i(oj.i(k)) - off;
   const Tensor &wj = b.get("wing_jnt");
   M.nwing = (int)wj.count;
-  for (int k = 0; k < M.nwing && k < 8; k++) M.wing_dof[k] = jdadr.i(wj.i(k)) - 3;
+  for (int k = 0; k < M.nwing && k < 8; k++) M.wing_dof[k] = jdadr.i(wj.i(k)) - off;
   double mi = 0;
   for (int k = 0; k < nv; k++) mi += dM0.f(k) / nv;
   M.meaninertia = (float)mi;
@@ -567,7 +580,7 @@ inline BallHost build_ball_model(const Blob &b) {
     M.l_kids[l] = (unsigned)M.l_child[0][l] | ((unsigned)M.l_child[1][l] << 8) | ((unsigned)M.l_child[2][l] << 16) | ((unsigned)M.l_nchild[l] << 24);
   }
   // ---- fly-fly candidate pairs over the primitive geoms, filtered as mj_collision filters them
-  {
+  if (!walk) {
     const Tensor &gct = b.get("geom_contype"), &gca = b.get("geom_conaffinity"), &excl = b.get("exclude_pairs"), &weld = b.get("body_weldid");
     std::vector<int> slot_of((size_t)gbody.count, -1);
     for (int l = 0; l < NL; l++) M.g_slot[l] = -1;
@@ -641,7 +654,7 @@ inline BallHost build_ball_model(const Blob &b) {
     }
   }
   // ---- convex pairs: geom tables, the static candidate list, the ball's convex partners
-  {
+  if (!walk) {
     const Tensor &cg1 = b.get("cand_g1"), &cg2 = b.get("cand_g2");
     const int ng = (int)gbody.count;
     if (ng - 1 > NG) throw std::runtime_error("ball model: more collision geoms than the geom table holds");
@@ -714,5 +727,8 @@ inline BallHost build_ball_model(const Blob &b) {
   (void)dbody; (void)djnt; (void)gcondim;
   return H;
 }
+}  // namespace detail
+
+inline BallHost build_ball_model(const Blob &b) { return detail::build_fly_model(b, false); }
 
 }  // namespace ffb

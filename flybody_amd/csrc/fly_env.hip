@@ -22,6 +22,7 @@
 
 #include "../../include/flybody_env.h"
 #include "ball_env.hpp"
+#include "walk_env.hpp"
 #include "dev_model.hpp"
 #include "launch_order.hpp"
 #include "dev_math.hpp"
@@ -2032,6 +2033,7 @@ using namespace ffe;
 
 struct ffe_env {
   ffb::BallEnv *ball = nullptr;  // walk_on_ball handles dispatch to ball_env.hip; everything below is the flight env
+  ffw::WalkEnv *walk = nullptr;  // free-root walking-fly physics handles dispatch to walk_env.hip
   int device = 0, batch = 0;
   DevModel dm{};
   TaskDev task{};
@@ -2088,7 +2090,37 @@ static T *upload(ffe_env *h, const T *src, size_t n) {
     return 0;                                                         \
   }
 
+// free-root walking-fly handles (ffe_create_walk_physics): the same for walk_env.hip
+#define FFE_WALK_DISPATCH(h, body)                                    \
+  if ((h) && (h)->walk) {                                             \
+    try { body; } catch (const std::exception &e_) { (h)->err = e_.what(); return -2; } \
+    return 0;                                                         \
+  }
+// ... and the calls such a handle refuses: bare physics is all that is built
+#define FFE_WALK_REFUSE(h, what)                                      \
+  if ((h) && (h)->walk) {                                             \
+    (h)->err = what ": not available on a walk physics handle (bare physics only: limits, floor contacts, sensors and the episode protocol are not built yet)"; \
+    return -1;                                                        \
+  }
+
 extern "C" {
+
+int ffe_create_walk_physics(const void *model_blob, size_t blob_size, const ffe_walk_physics_task *task, int batch, int device, ffe_handle *out) {
+  if (!out) return -1;
+  *out = nullptr;
+  std::unique_ptr<ffe_env> h(new ffe_env());
+  try {
+    if (!task) throw std::runtime_error("ffe_create_walk_physics: bad arguments");
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) throw std::runtime_error("no HIP device: the MI355X path has no CPU fallback");
+    if (device < 0 || device >= ndev) throw std::runtime_error("ffe_create_walk_physics: no such device");
+    DeviceGuard guard(device);
+    h->walk = ffw::walk_create(model_blob, blob_size, task->physics_flags, batch, device);
+    h->device = device; h->batch = batch;
+  } catch (const std::exception &e) { g_err = e.what(); return -1; }
+  *out = h.release();
+  return 0;
+}
 
 int ffe_create_walk_on_ball(const void *model_blob, size_t blob_size, const ffe_ball_task *task, int batch, int device, ffe_handle *out) {
   if (!out) return -1;
@@ -2109,14 +2141,16 @@ int ffe_create_walk_on_ball(const void *model_blob, size_t blob_size, const ffe_
   return 0;
 }
 int ffe_get_act(ffe_handle h, double *act_dev, void *stream) {
-  if (!h || !act_dev || !h->ball) return -1;
+  if (!h || !act_dev || (!h->ball && !h->walk)) return -1;
   DeviceGuard guard(h->device);
+  FFE_WALK_DISPATCH(h, ffw::walk_get_act(h->walk, act_dev, stream));
   FFE_BALL_DISPATCH(h, ffb::ball_get_act(h->ball, act_dev, stream));
   return -1;
 }
 int ffe_set_act(ffe_handle h, const double *act_dev, void *stream) {
-  if (!h || !act_dev || !h->ball) return -1;
+  if (!h || !act_dev || (!h->ball && !h->walk)) return -1;
   DeviceGuard guard(h->device);
+  FFE_WALK_DISPATCH(h, ffw::walk_set_act(h->walk, act_dev, stream));
   FFE_BALL_DISPATCH(h, ffb::ball_set_act(h->ball, act_dev, stream));
   return -1;
 }
@@ -2217,6 +2251,7 @@ int ffe_destroy(ffe_handle h) {
   if (!h) return -1;
   DeviceGuard guard(h->device);
   if (h->ball) { ffb::ball_destroy(h->ball); delete h; return 0; }
+  if (h->walk) { ffw::walk_destroy(h->walk); delete h; return 0; }
   for (void *p : h->allocs) (void)hipFree(p);
   if (h->ev0) (void)hipEventDestroy(h->ev0);
   if (h->ev1) (void)hipEventDestroy(h->ev1);
@@ -2226,6 +2261,14 @@ int ffe_destroy(ffe_handle h) {
 
 int ffe_spec(ffe_handle h, ffe_spec_t *s) {
   if (!h || !s) return -1;
+  if (h->walk) {  // no observation row: every offset is -1
+    std::memset(s, 0, sizeof(*s));
+    ffw::walk_spec(h->walk, &s->nq, &s->nv, &s->nu, &s->action_dim, &s->obs_dim, &s->nsub, &s->physics_timestep, &s->control_timestep);
+    s->batch = h->batch;
+    s->off_accelerometer = s->off_gyro = s->off_joints_pos = s->off_joints_vel = s->off_velocimeter = s->off_world_zaxis = -1;
+    s->off_ref_displacement = -1; s->off_ref_root_quat = -1;
+    return 0;
+  }
   if (h->ball) {
     std::memset(s, 0, sizeof(*s));
     ffb::ball_spec(h->ball, &s->nq, &s->nv, &s->nu, &s->action_dim, &s->obs_dim, &s->nsub, &s->physics_timestep, &s->control_timestep);
@@ -2248,6 +2291,7 @@ int ffe_spec(ffe_handle h, ffe_spec_t *s) {
 
 int ffe_action_bounds(ffe_handle h, float *mn, float *mx) {
   if (!h || !mn || !mx) return -1;
+  FFE_WALK_DISPATCH(h, ffw::walk_action_bounds(h->walk, mn, mx));
   FFE_BALL_DISPATCH(h, ffb::ball_action_bounds(h->ball, mn, mx));
   std::memcpy(mn, h->host.action_min.data(), h->host.action_min.size() * sizeof(float));
   std::memcpy(mx, h->host.action_max.data(), h->host.action_max.size() * sizeof(float));
@@ -2262,7 +2306,9 @@ int ffe_action_bounds(ffe_handle h, float *mn, float *mx) {
 static int launch_step(ffe_handle h, const float *act, float *obs, float *rew, float *disc, int32_t *st, void *stream, int mode, int nphys = 0,
                        const uint8_t *mask = nullptr) {
   if (!h) return -1;
+  if (h->walk && mode != 2) { FFE_WALK_REFUSE(h, "ffe_reset / ffe_reset_envs / ffe_step"); }
   DeviceGuard guard(h->device);
+  FFE_WALK_DISPATCH(h, ffw::walk_physics(h->walk, act, nphys, stream));
   FFE_BALL_DISPATCH(h, ffb::ball_launch(h->ball, act, obs, rew, disc, st, stream, mode, nphys, mask));
   if (mode != 2 && (!obs || !rew || !disc || !st || (mode == 0 && !act))) { h->err = "null device buffer"; return -1; }
   if (h->timing && hipEventRecord(h->ev0, static_cast<hipStream_t>(stream)) != hipSuccess) return -2;
@@ -2307,6 +2353,7 @@ int ffe_physics_step(ffe_handle h, const float *ctrl, int nsteps, void *stream) 
 
 int ffe_force_next_episode(ffe_handle h, const int32_t *traj, const double *phase, void *stream) {
   if (!h || !traj || !phase) return -1;
+  FFE_WALK_REFUSE(h, "ffe_force_next_episode");
   if (h->ball) { h->err = "walk_on_ball episodes have no per-episode randomness"; return -1; }
   DeviceGuard guard(h->device);
   try {
@@ -2333,6 +2380,7 @@ int ffe_force_next_episode(ffe_handle h, const int32_t *traj, const double *phas
 int ffe_get_state(ffe_handle h, double *qpos, double *qvel, void *stream) {
   if (!h || !qpos || !qvel) return -1;
   DeviceGuard guard(h->device);
+  FFE_WALK_DISPATCH(h, ffw::walk_get_state(h->walk, qpos, qvel, stream));
   FFE_BALL_DISPATCH(h, ffb::ball_get_state(h->ball, qpos, qvel, stream));
   hipLaunchKernelGGL(get_state_kernel, dim3(h->batch), dim3(kWave), 0, static_cast<hipStream_t>(stream), h->states, h->state_stride, qpos, qvel, h->batch, h->dm.nq, h->dm.nv);
   return hipGetLastError() == hipSuccess ? 0 : -2;
@@ -2340,6 +2388,7 @@ int ffe_get_state(ffe_handle h, double *qpos, double *qvel, void *stream) {
 int ffe_set_state(ffe_handle h, const double *qpos, const double *qvel, void *stream) {
   if (!h || !qpos || !qvel) return -1;
   DeviceGuard guard(h->device);
+  FFE_WALK_DISPATCH(h, ffw::walk_set_state(h->walk, qpos, qvel, stream));
   FFE_BALL_DISPATCH(h, ffb::ball_set_state(h->ball, qpos, qvel, stream));
   hipLaunchKernelGGL(set_state_kernel, dim3(h->batch), dim3(kWave), 0, static_cast<hipStream_t>(stream), h->states, h->state_stride, qpos, qvel, h->batch, h->dm.nq, h->dm.nv);
   return hipGetLastError() == hipSuccess ? 0 : -2;
@@ -2348,6 +2397,7 @@ int ffe_get_validity(ffe_handle h, int32_t *info, void *stream) {
   if (!h) return -1;
   if (!info || (reinterpret_cast<uintptr_t>(info) & 15)) { h->err = "ffe_get_validity: info_dev must be a 16-byte aligned device buffer"; return -1; }
   DeviceGuard guard(h->device);
+  FFE_WALK_DISPATCH(h, ffw::walk_get_validity(h->walk, info, stream));
   FFE_BALL_DISPATCH(h, ffb::ball_get_validity(h->ball, info, stream));
   hipLaunchKernelGGL(get_validity_kernel, dim3((h->batch + 255) / 256), dim3(256), 0, static_cast<hipStream_t>(stream), h->states, h->state_stride, info, h->batch);
   return hipGetLastError() == hipSuccess ? 0 : -2;
@@ -2355,6 +2405,7 @@ int ffe_get_validity(ffe_handle h, int32_t *info, void *stream) {
 int ffe_get_task_state(ffe_handle h, int32_t *ints, double *reals, void *stream) {
   if (!h || !ints || !reals) return -1;
   DeviceGuard guard(h->device);
+  FFE_WALK_DISPATCH(h, ffw::walk_get_task_state(h->walk, ints, reals, stream));
   FFE_BALL_DISPATCH(h, ffb::ball_get_task_state(h->ball, ints, reals, stream));
   hipLaunchKernelGGL(get_task_state_kernel, dim3((h->batch + 255) / 256), dim3(256), 0, static_cast<hipStream_t>(stream), h->states, h->state_stride, ints, reals, h->batch);
   return hipGetLastError() == hipSuccess ? 0 : -2;
@@ -2362,6 +2413,7 @@ int ffe_get_task_state(ffe_handle h, int32_t *ints, double *reals, void *stream)
 
 int ffe_time_steps(ffe_handle h, const float *act, float *obs, float *rew, float *disc, int32_t *st, int iters, void *stream, float *ms) {
   if (!h || !ms || iters <= 0) return -1;
+  FFE_WALK_REFUSE(h, "ffe_time_steps");
   DeviceGuard guard(h->device);
   FFE_BALL_DISPATCH(h, *ms = ffb::ball_time_steps(h->ball, act, obs, rew, disc, st, iters, stream));
   hipStream_t s = static_cast<hipStream_t>(stream);
@@ -2380,6 +2432,7 @@ int ffe_time_steps(ffe_handle h, const float *act, float *obs, float *rew, float
 
 int ffe_time_kernel(ffe_handle h, const float *act, float *obs, float *rew, float *disc, int32_t *st, int iters, void *stream, float *ms) {
   if (!h || !ms || iters <= 0) return -1;
+  FFE_WALK_REFUSE(h, "ffe_time_kernel");
   DeviceGuard guard(h->device);
   FFE_BALL_DISPATCH(h, *ms = ffb::ball_time_kernel(h->ball, act, obs, rew, disc, st, iters, stream));
   h->timing = true; h->timing_ms = 0.0;

@@ -63,12 +63,16 @@ def walk_on_ball(random_state=None, *, batch_size: int = 1, device: int = 0, **e
 def walk_imitation(ref_path=None, random_state=None, terminal_com_dist: float = 0.3, **env_kwargs):
     """Requires a fruitfly to track a reference walking fly (`fly_envs.py:75-122`).
 
-    Built so far (DESIGN.md section 2, row f3): the compiled model (`assets/fly_walk.ffmb`: free root, floor plane, Walking
-    configuration), the snippet layout and walker features (`tasks/walking.py`), the DeepMimic reward maths (`tasks/rewards.py`)
-    and the float64 CPU restatement of the whole task that the tests check against (test infrastructure, outside this package).  The free-root contact step kernel is
-    not written yet, and this package has no CPU path: the factory fails instead of returning a slow environment."""
-    raise NotImplementedError("walk_imitation: model, reference layout, reward maths and oracle exist; the HIP step kernel "
-                              "(free root + floor contacts) is not built yet - see DESIGN.md section 2 row f3")
+    Built so far (DESIGN.md section 2 row f3, section 12): the compiled model (`assets/fly_walk.ffmb`: free root, floor plane, Walking
+    configuration), the snippet layout and walker features (`tasks/walking.py`), the DeepMimic reward maths (`tasks/rewards.py`), the
+    task layer on the device (`tasks/walk_tracker.py`: features, reward, termination, observation columns), the free-root smooth
+    dynamics on the device (`batched_env.BatchedWalkPhysics`: `ffe_physics_step` with constraints off) and the float64 CPU restatement
+    of the whole task that the tests check against (test infrastructure, outside this package).  Missing: joint limits, floor
+    contacts, sensors and the episode protocol of the step kernel.  This package has no CPU path: the factory fails instead of
+    returning a slow environment."""
+    raise NotImplementedError("walk_imitation: model, reference layout, reward maths, oracle, the device task layer (WalkTracker) and the "
+                              "free-root smooth dynamics (BatchedWalkPhysics) exist; joint limits, floor contacts, sensors and the episode "
+                              "protocol of the HIP step kernel are not built yet - see DESIGN.md section 12")
 
 
 def vision_guided_flight(*args, **kwargs):

@@ -106,7 +106,23 @@ int ffe_create_flight(const void *model_blob, size_t blob_size, const ffe_flight
  * qvel[105] = ball angular velocity (body frame), then the hinges. */
 int ffe_create_walk_on_ball(const void *model_blob, size_t blob_size, const ffe_ball_task *task, int batch, int device,
                             ffe_handle *out);
-/* physics.data.act (actuator activations, [B][nu] float64 device buffers) of a walk_on_ball handle */
+/* The walking fly of fly_envs.walk_imitation (fly_envs.py:75-122; flybody_amd/assets/fly_walk.ffmb: free thorax, 6 + 102 dofs, 59
+ * filtered actuators) as bare physics: smooth dynamics on the device, constraints off ("dynamics only", as ffe_physics_step offers for
+ * the other two tasks).  Joint limits, floor contacts, sensors and the episode protocol are not built yet. */
+typedef struct {
+  int32_t physics_flags; /* FFE_NO_*; must contain FFE_NO_CONTACT | FFE_NO_LIMIT in this build */
+} ffe_walk_physics_task;
+/* The handle starts at the blob's qpos0 with zero velocity and zero activation and works with ffe_spec (nq 109, nv 108, nu 59,
+ * action_dim 59, obs_dim 0, nsub 10, every observation offset -1) / ffe_action_bounds / ffe_physics_step (ctrl[B][59], clamped to
+ * ctrlrange) / ffe_get_state / ffe_set_state / ffe_get_act / ffe_set_act / ffe_get_task_state (zeros) / ffe_get_validity (zeros) /
+ * ffe_last_error / ffe_destroy.  State layout (MuJoCo's): qpos[109] = root position 3 (float64 on the device too), root quaternion
+ * 4, the 102 hinges; qvel[108] = root linear velocity in the world frame 3, root angular velocity in the body frame 3, the hinges.
+ * ffe_set_state normalises the quaternion as the position stage does.  Refused with rc < 0 and a text (ffe_last_error): flags
+ * lacking FFE_NO_CONTACT | FFE_NO_LIMIT, a blob that is not the walk model; on such a handle ffe_reset, ffe_reset_envs, ffe_step,
+ * ffe_time_steps, ffe_time_kernel and ffe_force_next_episode. */
+int ffe_create_walk_physics(const void *model_blob, size_t blob_size, const ffe_walk_physics_task *task, int batch, int device,
+                            ffe_handle *out);
+/* physics.data.act (actuator activations, [B][nu] float64 device buffers) of a walk_on_ball or walk physics handle */
 int ffe_get_act(ffe_handle h, double *act_dev, void *stream);
 int ffe_set_act(ffe_handle h, const double *act_dev, void *stream);
 int ffe_destroy(ffe_handle h);
