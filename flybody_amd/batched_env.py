@@ -54,7 +54,97 @@ def time_limit_control_steps(time_limit: float, physics_timestep: float, nsub: i
     return n
 
 
-class BatchedFlyEnv:
+class EnvHandle:
+    """One handle of the C ABI (include/flybody_env.h) and what every kind of handle shares: `_h`, `_L`, `device`, error checking, the
+    stream, the spec and the raw state accessors.  `get_act` / `set_act` exist on every kind; the library refuses them on a flight handle."""
+
+    def _open(self, batch_size: int, device: int):
+        """Binds the library and the device; the subclass then creates its handle and passes it to `_adopt`."""
+        import torch
+
+        if not torch.cuda.is_available():
+            raise RuntimeError(f"{type(self).__name__} needs a HIP device (MI355X); there is no CPU fallback")
+        self._torch = torch
+        self._L = _capi.lib()
+        self.batch_size = int(batch_size)
+        self.device = torch.device("cuda", device)
+
+    def _adopt(self, what: str, rc: int, h):
+        """Takes the handle a create function returned and reads its spec and action bounds."""
+        if rc != 0:
+            raise RuntimeError(what + ": " + self._L.ffe_last_error(None).decode())
+        self._h = h
+        self.spec = _capi.Spec()
+        self._check(self._L.ffe_spec(self._h, C.byref(self.spec)))
+        amin, amax = (C.c_float * self.spec.action_dim)(), (C.c_float * self.spec.action_dim)()
+        self._check(self._L.ffe_action_bounds(self._h, amin, amax))
+        self._action_min, self._action_max = np.array(amin[:], dtype=np.float32), np.array(amax[:], dtype=np.float32)
+
+    def _check(self, rc):
+        if rc != 0:
+            raise RuntimeError("flybody_env: " + self._L.ffe_last_error(self._h).decode())
+
+    def _stream(self):
+        return C.c_void_p(self._torch.cuda.current_stream(self.device).cuda_stream)
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.ffe_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def raw_action_bounds(self):
+        """(minimum, maximum) of the un-wrapped action spec (`fruitfly.py:496-526`)."""
+        return self._action_min.copy(), self._action_max.copy()
+
+    def get_state(self):
+        t = self._torch
+        qpos = t.empty(self.batch_size, self.spec.nq, dtype=t.float64, device=self.device)
+        qvel = t.empty(self.batch_size, self.spec.nv, dtype=t.float64, device=self.device)
+        self._check(self._L.ffe_get_state(self._h, qpos.data_ptr(), qvel.data_ptr(), self._stream()))
+        return qpos, qvel
+
+    def set_state(self, qpos, qvel):
+        t = self._torch
+        qpos = qpos.to(device=self.device, dtype=t.float64).contiguous()
+        qvel = qvel.to(device=self.device, dtype=t.float64).contiguous()
+        assert tuple(qpos.shape) == (self.batch_size, self.spec.nq) and tuple(qvel.shape) == (self.batch_size, self.spec.nv)
+        self._check(self._L.ffe_set_state(self._h, qpos.data_ptr(), qvel.data_ptr(), self._stream()))
+        t.cuda.current_stream(self.device).synchronize()
+
+    def physics_step(self, ctrl, nsteps: int = 1):
+        """`physics.set_control(ctrl)` then `nsteps` x `physics.step()` for every env, no task layer (BASELINE config 2).
+        `ctrl`: float32 [B, nu] cuda tensor."""
+        assert ctrl.is_cuda and ctrl.device == self.device and ctrl.dtype == self._torch.float32 and ctrl.is_contiguous() and tuple(ctrl.shape) == (self.batch_size, self.spec.nu)
+        self._check(self._L.ffe_physics_step(self._h, ctrl.data_ptr(), int(nsteps), self._stream()))
+
+    def get_task_state(self):
+        t = self._torch
+        ints = t.empty(self.batch_size, 8, dtype=t.int32, device=self.device)
+        reals = t.empty(self.batch_size, 8, dtype=t.float64, device=self.device)
+        self._check(self._L.ffe_get_task_state(self._h, ints.data_ptr(), reals.data_ptr(), self._stream()))
+        return ints, reals
+
+    def get_act(self):
+        t = self._torch
+        act = t.empty(self.batch_size, self.spec.nu, dtype=t.float64, device=self.device)
+        self._check(self._L.ffe_get_act(self._h, act.data_ptr(), self._stream()))
+        return act
+
+    def set_act(self, act):
+        t = self._torch
+        act = act.to(device=self.device, dtype=t.float64).contiguous()
+        assert tuple(act.shape) == (self.batch_size, self.spec.nu)
+        self._check(self._L.ffe_set_act(self._h, act.data_ptr(), self._stream()))
+        t.cuda.current_stream(self.device).synchronize()
+
+
+class BatchedFlyEnv(EnvHandle):
     """B independent flight-imitation environments stepping in lock-step on one MI355X.
 
     One `step()` = one kernel launch = one control step (4 physics substeps + task) of every env.
@@ -80,17 +170,10 @@ class BatchedFlyEnv:
         library rejects every other value."""
         import json
 
-        import torch
-
-        if not torch.cuda.is_available():
-            raise RuntimeError("BatchedFlyEnv needs a HIP device (MI355X); there is no CPU fallback")
+        self._open(batch_size, device)
         if isinstance(contact_capacity, bool) or int(contact_capacity) != contact_capacity:
             raise TypeError(f"contact_capacity must be an integer (6 or 12), got {contact_capacity!r}")
         self.contact_capacity = int(contact_capacity)
-        self._torch = torch
-        self._L = _capi.lib()
-        self.batch_size = int(batch_size)
-        self.device = torch.device("cuda", device)
         with open(blob_path, "rb") as f:
             blob = f.read()
         with open(os.path.splitext(blob_path)[0] + ".json") as f:
@@ -127,17 +210,10 @@ class BatchedFlyEnv:
         self.time_limit_steps = int(task.episode_limit_steps)  # control steps after which the time limit ends an episode
         h = C.c_void_p()
         rc = self._L.ffe_create_flight(blob, len(blob), C.byref(task), self.batch_size, device, seed, env_id_base, C.byref(h))
-        if rc != 0:
-            raise RuntimeError("ffe_create_flight: " + self._L.ffe_last_error(None).decode())
-        self._h = h
+        self._adopt("ffe_create_flight", rc, h)
         self.ghost_accel_z = ghost_accel_z
         self.canonical_actions = bool(canonical_actions)
-        self.spec = _capi.Spec()
-        self._check(self._L.ffe_spec(self._h, C.byref(self.spec)))
         s = self.spec
-        amin, amax = (C.c_float * s.action_dim)(), (C.c_float * s.action_dim)()
-        self._check(self._L.ffe_action_bounds(self._h, amin, amax))
-        self._action_min, self._action_max = np.array(amin[:], dtype=np.float32), np.array(amax[:], dtype=np.float32)
         self._alloc_outputs(double_buffer)
         j, r = s.n_obs_joints, s.n_ref
         # key order: enabled walker observables alphabetically, then the task's additions (dm_control Observables)
@@ -166,30 +242,12 @@ class BatchedFlyEnv:
         self._cur = (self._cur + 1) % len(self._sets)
         self._obs, self._reward, self._discount, self._step_type = self._sets[self._cur]
 
-    def _check(self, rc):
-        if rc != 0:
-            raise RuntimeError("flybody_env: " + self._L.ffe_last_error(self._h).decode())
-
-    def _stream(self):
-        return C.c_void_p(self._torch.cuda.current_stream(self.device).cuda_stream)
-
     def _timestep(self):
         obs = collections.OrderedDict()
         for key, (off, shape) in self._layout.items():
             n = int(np.prod(shape))
             obs[key] = self._obs[:, off:off + n].view(self.batch_size, *shape)
         return TimeStep(self._step_type, self._reward, self._discount, obs)
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._L.ffe_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     # ------------------------------------------------------------------------------------------ dm_env surface
     def reset(self) -> TimeStep:
@@ -232,10 +290,6 @@ class BatchedFlyEnv:
         return BoundedArray((self.spec.action_dim,), np.float32, self._action_min, self._action_max,
                             name="\t".join(self._meta["action_names"]))
 
-    def raw_action_bounds(self):
-        """(minimum, maximum) of the un-wrapped action spec (`fruitfly.py:496-526`)."""
-        return self._action_min.copy(), self._action_max.copy()
-
     def observation_spec(self):
         return collections.OrderedDict((k, Array(shape, np.float32, name=k)) for k, (_, shape) in self._layout.items())
 
@@ -260,34 +314,6 @@ class BatchedFlyEnv:
         phase = np.ascontiguousarray(np.broadcast_to(phase, (self.batch_size,)), dtype=np.float64)
         self._check(self._L.ffe_force_next_episode(self._h, idx.ctypes.data_as(C.POINTER(C.c_int32)), phase.ctypes.data_as(C.POINTER(C.c_double)),
                                                    self._stream()))
-
-    def get_state(self):
-        t = self._torch
-        qpos = t.empty(self.batch_size, self.spec.nq, dtype=t.float64, device=self.device)
-        qvel = t.empty(self.batch_size, self.spec.nv, dtype=t.float64, device=self.device)
-        self._check(self._L.ffe_get_state(self._h, qpos.data_ptr(), qvel.data_ptr(), self._stream()))
-        return qpos, qvel
-
-    def set_state(self, qpos, qvel):
-        t = self._torch
-        qpos = qpos.to(device=self.device, dtype=t.float64).contiguous()
-        qvel = qvel.to(device=self.device, dtype=t.float64).contiguous()
-        assert tuple(qpos.shape) == (self.batch_size, self.spec.nq) and tuple(qvel.shape) == (self.batch_size, self.spec.nv)
-        self._check(self._L.ffe_set_state(self._h, qpos.data_ptr(), qvel.data_ptr(), self._stream()))
-        t.cuda.current_stream(self.device).synchronize()
-
-    def physics_step(self, ctrl, nsteps: int = 1):
-        """`physics.set_control(ctrl)` then `nsteps` x `physics.step()` for every env, no task layer (BASELINE config 2).
-        `ctrl`: float32 [B, nu] cuda tensor."""
-        assert ctrl.is_cuda and ctrl.device == self.device and ctrl.dtype == self._torch.float32 and ctrl.is_contiguous() and tuple(ctrl.shape) == (self.batch_size, self.spec.nu)
-        self._check(self._L.ffe_physics_step(self._h, ctrl.data_ptr(), int(nsteps), self._stream()))
-
-    def get_task_state(self):
-        t = self._torch
-        ints = t.empty(self.batch_size, 8, dtype=t.int32, device=self.device)
-        reals = t.empty(self.batch_size, 8, dtype=t.float64, device=self.device)
-        self._check(self._L.ffe_get_task_state(self._h, ints.data_ptr(), reals.data_ptr(), self._stream()))
-        return ints, reals
 
     def validity(self) -> Validity:
         """Whether the physics behind the current timestep was truncated (`ffe_get_validity`): `step_bits` of the launch that produced
@@ -337,14 +363,7 @@ class BatchedBallEnv(BatchedFlyEnv):
                  double_buffer: bool = False, blob_path: str = BALL_BLOB):
         import json
 
-        import torch
-
-        if not torch.cuda.is_available():
-            raise RuntimeError("BatchedBallEnv needs a HIP device (MI355X); there is no CPU fallback")
-        self._torch = torch
-        self._L = _capi.lib()
-        self.batch_size = int(batch_size)
-        self.device = torch.device("cuda", device)
+        self._open(batch_size, device)
         with open(blob_path, "rb") as f:
             blob = f.read()
         with open(os.path.splitext(blob_path)[0] + ".json") as f:
@@ -359,16 +378,9 @@ class BatchedBallEnv(BatchedFlyEnv):
         self.time_limit_steps = int(task.time_limit_steps)
         h = C.c_void_p()
         rc = self._L.ffe_create_walk_on_ball(blob, len(blob), C.byref(task), self.batch_size, device, C.byref(h))
-        if rc != 0:
-            raise RuntimeError("ffe_create_walk_on_ball: " + self._L.ffe_last_error(None).decode())
-        self._h = h
+        self._adopt("ffe_create_walk_on_ball", rc, h)
         self.canonical_actions = bool(canonical_actions)
-        self.spec = _capi.Spec()
-        self._check(self._L.ffe_spec(self._h, C.byref(self.spec)))
         s = self.spec
-        amin, amax = (C.c_float * s.action_dim)(), (C.c_float * s.action_dim)()
-        self._check(self._L.ffe_action_bounds(self._h, amin, amax))
-        self._action_min, self._action_max = np.array(amin[:], dtype=np.float32), np.array(amax[:], dtype=np.float32)
         self._alloc_outputs(double_buffer)
         self._layout = collections.OrderedDict()
         off = 0
@@ -382,21 +394,8 @@ class BatchedBallEnv(BatchedFlyEnv):
     def set_next_trajectory_index(self, idx, phase):
         raise NotImplementedError("walk_on_ball has no reference trajectories")
 
-    def get_act(self):
-        t = self._torch
-        act = t.empty(self.batch_size, self.spec.nu, dtype=t.float64, device=self.device)
-        self._check(self._L.ffe_get_act(self._h, act.data_ptr(), self._stream()))
-        return act
 
-    def set_act(self, act):
-        t = self._torch
-        act = act.to(device=self.device, dtype=t.float64).contiguous()
-        assert tuple(act.shape) == (self.batch_size, self.spec.nu)
-        self._check(self._L.ffe_set_act(self._h, act.data_ptr(), self._stream()))
-        t.cuda.current_stream(self.device).synchronize()
-
-
-class BatchedWalkPhysics:
+class BatchedWalkPhysics(EnvHandle):
     """B walking flies (`assets/fly_walk.ffmb`: free thorax, 6 + 102 dofs, 59 filtered actuators) advanced on one MI355X by
     `ffe_physics_step` with constraints off: the smooth dynamics of `walk_imitation`.  Not an
     environment: there is no reset, step, observation or reward - joint limits, floor contacts, sensors and the episode protocol are
@@ -409,37 +408,11 @@ class BatchedWalkPhysics:
     task_kind = "walk_physics"
 
     def __init__(self, *, batch_size: int, device: int = 0, physics_flags: int = FFE_NO_CONTACT | FFE_NO_LIMIT, blob_path: str = WALK_BLOB):
-        import torch
-
-        if not torch.cuda.is_available():
-            raise RuntimeError("BatchedWalkPhysics needs a HIP device (MI355X); there is no CPU fallback")
-        self._torch = torch
-        self._L = _capi.lib()
-        self.batch_size = int(batch_size)
-        self.device = torch.device("cuda", device)
+        self._open(batch_size, device)
         with open(blob_path, "rb") as f:
             blob = f.read()
         task = _capi.WalkPhysicsTask(physics_flags=int(physics_flags))
         h = C.c_void_p()
         rc = self._L.ffe_create_walk_physics(blob, len(blob), C.byref(task), self.batch_size, device, C.byref(h))
-        if rc != 0:
-            raise RuntimeError("ffe_create_walk_physics: " + self._L.ffe_last_error(None).decode())
-        self._h = h
+        self._adopt("ffe_create_walk_physics", rc, h)
         self.physics_flags = int(physics_flags)
-        self.spec = _capi.Spec()
-        self._check(self._L.ffe_spec(self._h, C.byref(self.spec)))
-        amin, amax = (C.c_float * self.spec.action_dim)(), (C.c_float * self.spec.action_dim)()
-        self._check(self._L.ffe_action_bounds(self._h, amin, amax))
-        self._action_min, self._action_max = np.array(amin[:], dtype=np.float32), np.array(amax[:], dtype=np.float32)
-
-    _check = BatchedFlyEnv._check
-    _stream = BatchedFlyEnv._stream
-    close = BatchedFlyEnv.close
-    __del__ = BatchedFlyEnv.__del__
-    raw_action_bounds = BatchedFlyEnv.raw_action_bounds
-    get_state = BatchedFlyEnv.get_state
-    set_state = BatchedFlyEnv.set_state
-    physics_step = BatchedFlyEnv.physics_step
-    get_task_state = BatchedFlyEnv.get_task_state
-    get_act = BatchedBallEnv.get_act
-    set_act = BatchedBallEnv.set_act

@@ -1740,30 +1740,79 @@ __global__ void ball_validity_kernel(const BState *states, int *info, int batch)
 }
 
 // ================================================================================================ host side
-#define HIPB_OK(expr)                                                                               \
-  do {                                                                                              \
-    hipError_t _e = (expr);                                                                         \
-    if (_e != hipSuccess) throw std::runtime_error(std::string(#expr) + ": " + hipGetErrorString(_e)); \
-  } while (0)
-
-struct BallEnv {
-  int device = 0, batch = 0;
+struct BallEnv final : ffe::EnvBackend {
   BallHost host;
   BTaskDev task{};
   BallModel *model_dev = nullptr;
   BState *states = nullptr;
   int *order = nullptr, *cost = nullptr;  // launch order of the envs and its sort keys (launch_order.hpp)
-  bool timing = false; double timing_ms = 0.0;  // ball_time_kernel: events around the step kernel alone
+  ffe::KernelTimer tm;
   double control_timestep = 0;
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
+
+  ~BallEnv() override {
+    (void)hipFree(model_dev); (void)hipFree(states); (void)hipFree(order); (void)hipFree(cost);
+  }
+
+  void spec(ffe_spec_t &s) const override {
+    s = ffe_spec_t{};
+    s.batch = batch; s.nq = 106; s.nv = 105; s.nu = NU; s.action_dim = NACT; s.obs_dim = NOBS; s.nsub = host.m.nsub;
+    s.physics_timestep = host.m.h; s.control_timestep = control_timestep;
+    // walk_on_ball row: accelerometer 3 | actuator_activation 59 | appendages_pos 21 | ball_qvel 3 | force 18 | gyro 3 |
+    //                   joints_pos 85 | joints_vel 85 | touch 6 | velocimeter 3 | world_zaxis 3
+    s.off_accelerometer = 0; s.off_gyro = 104; s.off_joints_pos = 107; s.off_joints_vel = 192; s.off_velocimeter = 283; s.off_world_zaxis = 286;
+    s.off_ref_displacement = -1; s.off_ref_root_quat = -1; s.n_obs_joints = NOBSJ; s.n_ref = 0;
+  }
+  void action_bounds(float *mn, float *mx) const override {
+    for (int k = 0; k < NACT; k++) { mn[k] = host.action_min[k]; mx[k] = host.action_max[k]; }
+  }
+  ffe::KernelTimer *timer() override { return &tm; }
+
+  void launch(const float *act, float *obs, float *rew, float *disc, int32_t *st, void *stream, int mode, int nphys, const uint8_t *mask) override {
+    // (not ffe::Refused: these two have always come out as -2, and the header's table says so)
+    if (mode != 1 && mode != 3 && !act) throw std::runtime_error("walk_on_ball: null action buffer");
+    if (mode != 2 && (!obs || !rew || !disc || !st)) throw std::runtime_error("walk_on_ball: null output buffer");
+    hipStream_t s = (hipStream_t)stream;
+    tm.start(s);
+    hipLaunchKernelGGL(ball_step_kernel, dim3(batch), dim3(64), 0, s, model_dev, task, states, act, obs, rew, disc, st, batch, mode, nphys, order, cost, mask);
+    HIP_OK(hipGetLastError());
+    tm.stop(s);
+    if (mode == 0 && batch > 1) {
+      hipLaunchKernelGGL(ffe_order::order_by_cost, dim3(1), dim3(1024), 0, s, cost, order, batch);
+      HIP_OK(hipGetLastError());
+    }
+    tm.collect();
+  }
+  void force_next_episode(const int32_t *, const double *, void *) override { throw ffe::Refused("walk_on_ball episodes have no per-episode randomness"); }
+
+  void get_state(double *qpos, double *qvel, void *stream) override {
+    hipLaunchKernelGGL(ball_get_state_kernel, dim3(batch), dim3(128), 0, (hipStream_t)stream, states, qpos, qvel, batch);
+    HIP_OK(hipGetLastError());
+  }
+  void set_state(const double *qpos, const double *qvel, void *stream) override {
+    hipLaunchKernelGGL(ball_set_state_kernel, dim3(batch), dim3(128), 0, (hipStream_t)stream, states, qpos, qvel, batch);
+    HIP_OK(hipGetLastError());
+  }
+  void get_act(double *act, void *stream) override {
+    hipLaunchKernelGGL(ball_act_kernel, dim3(batch), dim3(64), 0, (hipStream_t)stream, states, act, batch, 0);
+    HIP_OK(hipGetLastError());
+  }
+  void set_act(const double *act, void *stream) override {
+    hipLaunchKernelGGL(ball_act_kernel, dim3(batch), dim3(64), 0, (hipStream_t)stream, states, const_cast<double *>(act), batch, 1);
+    HIP_OK(hipGetLastError());
+  }
+  void get_task_state(int32_t *ints, double *reals, void *stream) override {
+    hipLaunchKernelGGL(ball_task_state_kernel, dim3((batch + 63) / 64), dim3(64), 0, (hipStream_t)stream, states, ints, reals, batch);
+    HIP_OK(hipGetLastError());
+  }
+  void get_validity(int32_t *info, void *stream) override {
+    hipLaunchKernelGGL(ball_validity_kernel, dim3((batch + 63) / 64), dim3(64), 0, (hipStream_t)stream, states, info, batch);
+    HIP_OK(hipGetLastError());
+  }
 };
 
-struct BallEnvDeleter { void operator()(BallEnv *e) const { ball_destroy(e); } };
-
-// the caller (fly_env.hip) has made `device` current
-BallEnv *ball_create(const void *blob, size_t blob_size, const BallTaskHost &task, int batch, int device) {
+std::unique_ptr<ffe::EnvBackend> ball_create(const void *blob, size_t blob_size, const BallTaskHost &task, int batch, int device) {
   if (!blob || batch <= 0) throw std::runtime_error("ffe_create_walk_on_ball: bad arguments");
-  std::unique_ptr<BallEnv, BallEnvDeleter> e(new BallEnv());  // frees the device allocations made so far if a later step throws
+  std::unique_ptr<BallEnv> e(new BallEnv());  // frees the device allocations made so far if a later step throws
   Blob b(blob, blob_size);
   e->host = build_ball_model(b);
   e->device = device; e->batch = batch;
@@ -1772,78 +1821,16 @@ BallEnv *ball_create(const void *blob, size_t blob_size, const BallTaskHost &tas
   if (e->host.m.nsub < 1 || e->host.m.nsub > 64) throw std::runtime_error("walk_on_ball: bad control timestep");
   e->task.time_limit_steps = task.time_limit_steps; e->task.pad_first_obs = task.pad_first_obs; e->task.flags = task.physics_flags;
   e->task.canonical = task.canonical_actions; e->task.clip = task.clip_actions;
-  HIPB_OK(hipMalloc((void **)&e->model_dev, sizeof(BallModel)));
-  HIPB_OK(hipMemcpy(e->model_dev, &e->host.m, sizeof(BallModel), hipMemcpyHostToDevice));
-  HIPB_OK(hipMalloc((void **)&e->states, sizeof(BState) * (size_t)batch));
-  HIPB_OK(hipMalloc((void **)&e->order, sizeof(int) * (size_t)batch));
-  HIPB_OK(hipMalloc((void **)&e->cost, sizeof(int) * (size_t)batch));
+  HIP_OK(hipMalloc((void **)&e->model_dev, sizeof(BallModel)));
+  HIP_OK(hipMemcpy(e->model_dev, &e->host.m, sizeof(BallModel), hipMemcpyHostToDevice));
+  HIP_OK(hipMalloc((void **)&e->states, sizeof(BState) * (size_t)batch));
+  HIP_OK(hipMalloc((void **)&e->order, sizeof(int) * (size_t)batch));
+  HIP_OK(hipMalloc((void **)&e->cost, sizeof(int) * (size_t)batch));
   hipLaunchKernelGGL(ball_init_states, dim3((batch + 63) / 64), dim3(64), 0, 0, e->states, e->order, e->cost, batch);
-  HIPB_OK(hipGetLastError());
-  HIPB_OK(hipDeviceSynchronize());
-  HIPB_OK(hipEventCreate(&e->ev0));
-  HIPB_OK(hipEventCreate(&e->ev1));
-  return e.release();
-}
-void ball_destroy(BallEnv *e) {
-  if (!e) return;
-  if (e->model_dev) (void)hipFree(e->model_dev);
-  if (e->states) (void)hipFree(e->states);
-  if (e->order) (void)hipFree(e->order);
-  if (e->cost) (void)hipFree(e->cost);
-  if (e->ev0) (void)hipEventDestroy(e->ev0);
-  if (e->ev1) (void)hipEventDestroy(e->ev1);
-  delete e;
-}
-void ball_spec(const BallEnv *e, int *nq, int *nv, int *nu, int *action_dim, int *obs_dim, int *nsub, double *h, double *ctrl_dt) {
-  *nq = 106; *nv = 105; *nu = NU; *action_dim = NACT; *obs_dim = NOBS; *nsub = e->host.m.nsub; *h = e->host.m.h; *ctrl_dt = e->control_timestep;
-}
-void ball_action_bounds(const BallEnv *e, float *mn, float *mx) {
-  for (int k = 0; k < NACT; k++) { mn[k] = e->host.action_min[k]; mx[k] = e->host.action_max[k]; }
-}
-void ball_launch(BallEnv *e, const float *act, float *obs, float *rew, float *disc, int32_t *st, void *stream, int mode, int nphys,
-                 const uint8_t *mask) {
-  if (mode != 1 && mode != 3 && !act) throw std::runtime_error("walk_on_ball: null action buffer");
-  if (mode != 2 && (!obs || !rew || !disc || !st)) throw std::runtime_error("walk_on_ball: null output buffer");
-  if (mode == 3 && !mask) throw std::runtime_error("walk_on_ball: null reset mask");
-  if (e->timing) HIPB_OK(hipEventRecord(e->ev0, (hipStream_t)stream));
-  hipLaunchKernelGGL(ball_step_kernel, dim3(e->batch), dim3(64), 0, (hipStream_t)stream, e->model_dev, e->task, e->states, act, obs, rew, disc, st,
-                     e->batch, mode, nphys, e->order, e->cost, mask);
-  HIPB_OK(hipGetLastError());
-  if (e->timing) HIPB_OK(hipEventRecord(e->ev1, (hipStream_t)stream));
-  if (mode == 0 && e->batch > 1) {
-    hipLaunchKernelGGL(ffe_order::order_by_cost, dim3(1), dim3(1024), 0, (hipStream_t)stream, e->cost, e->order, e->batch);
-    HIPB_OK(hipGetLastError());
-  }
-  if (e->timing) {
-    float t = 0.f;
-    HIPB_OK(hipEventSynchronize(e->ev1));
-    HIPB_OK(hipEventElapsedTime(&t, e->ev0, e->ev1));
-    e->timing_ms += t;
-  }
-}
-void ball_get_state(BallEnv *e, double *qpos, double *qvel, void *stream) {
-  hipLaunchKernelGGL(ball_get_state_kernel, dim3(e->batch), dim3(128), 0, (hipStream_t)stream, e->states, qpos, qvel, e->batch);
-  HIPB_OK(hipGetLastError());
-}
-void ball_set_state(BallEnv *e, const double *qpos, const double *qvel, void *stream) {
-  hipLaunchKernelGGL(ball_set_state_kernel, dim3(e->batch), dim3(128), 0, (hipStream_t)stream, e->states, qpos, qvel, e->batch);
-  HIPB_OK(hipGetLastError());
-}
-void ball_get_act(BallEnv *e, double *act, void *stream) {
-  hipLaunchKernelGGL(ball_act_kernel, dim3(e->batch), dim3(64), 0, (hipStream_t)stream, e->states, act, e->batch, 0);
-  HIPB_OK(hipGetLastError());
-}
-void ball_set_act(BallEnv *e, const double *act, void *stream) {
-  hipLaunchKernelGGL(ball_act_kernel, dim3(e->batch), dim3(64), 0, (hipStream_t)stream, e->states, const_cast<double *>(act), e->batch, 1);
-  HIPB_OK(hipGetLastError());
-}
-void ball_get_task_state(BallEnv *e, int32_t *ints, double *reals, void *stream) {
-  hipLaunchKernelGGL(ball_task_state_kernel, dim3((e->batch + 63) / 64), dim3(64), 0, (hipStream_t)stream, e->states, ints, reals, e->batch);
-  HIPB_OK(hipGetLastError());
-}
-void ball_get_validity(BallEnv *e, int32_t *info, void *stream) {
-  hipLaunchKernelGGL(ball_validity_kernel, dim3((e->batch + 63) / 64), dim3(64), 0, (hipStream_t)stream, e->states, info, e->batch);
-  HIPB_OK(hipGetLastError());
+  HIP_OK(hipGetLastError());
+  HIP_OK(hipDeviceSynchronize());
+  e->tm.create();
+  return e;
 }
 #ifdef FFE_TRACE
 extern "C" int ffb_debug_read_trace(unsigned long long *out, int nrows) {
@@ -1857,22 +1844,5 @@ extern "C" int ffb_debug_read_stamps(unsigned long long *out24, int reset) {
   return 0;
 }
 #endif
-float ball_time_steps(BallEnv *e, const float *act, float *obs, float *rew, float *disc, int32_t *st, int iters, void *stream) {
-  hipStream_t s = (hipStream_t)stream;
-  HIPB_OK(hipEventRecord(e->ev0, s));
-  for (int k = 0; k < iters; k++) ball_launch(e, act, obs, rew, disc, st, stream, 0, 0, nullptr);
-  HIPB_OK(hipEventRecord(e->ev1, s));
-  HIPB_OK(hipEventSynchronize(e->ev1));
-  float ms = 0.f;
-  HIPB_OK(hipEventElapsedTime(&ms, e->ev0, e->ev1));
-  return ms / (float)iters;
-}
-
-float ball_time_kernel(BallEnv *e, const float *act, float *obs, float *rew, float *disc, int32_t *st, int iters, void *stream) {
-  e->timing = true; e->timing_ms = 0.0;
-  for (int k = 0; k < iters; k++) ball_launch(e, act, obs, rew, disc, st, stream, 0, 0, nullptr);
-  e->timing = false;
-  return (float)(e->timing_ms / iters);
-}
 
 }  // namespace ffb

@@ -21,7 +21,7 @@
 #include <memory>
 #include <string>
 
-#include "../../include/flybody_env.h"
+#include "env_backend.hpp"
 
 namespace ffl {
 
@@ -136,11 +136,6 @@ struct ffe_eplog {
 static thread_local std::string g_lerr;
 
 namespace {
-struct DeviceScope {
-  int prev = -1, dev;
-  explicit DeviceScope(int d) : dev(d) { (void)hipGetDevice(&prev); if (prev != dev) (void)hipSetDevice(dev); }
-  ~DeviceScope() { if (prev >= 0 && prev != dev) (void)hipSetDevice(prev); }
-};
 void free_all(ffe_eplog *p) {
   (void)hipFree(p->ep_ret); (void)hipFree(p->ep_len); (void)hipFree(p->armed); (void)hipFree(p->records); (void)hipFree(p->info); (void)hipFree(p->ticket);
 }
@@ -159,7 +154,7 @@ int ffe_eplog_create(int batch, long long capacity, int flags, int device, ffe_e
     return fail("capacity " + std::to_string(capacity) + " is below batch = " + std::to_string(batch) + ", the records one call can write: they would share slots of the ring");
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || device < 0 || device >= ndev) return fail("no such HIP device: the MI355X path has no CPU fallback");
-  DeviceScope scope(device);
+  ffe::DeviceGuard guard(device);
   std::unique_ptr<ffe_eplog> p(new ffe_eplog());
   p->device = device; p->batch = batch; p->flags = flags; p->capacity = capacity;
   const size_t B = (size_t)batch;
@@ -179,7 +174,7 @@ int ffe_eplog_create(int batch, long long capacity, int flags, int device, ffe_e
 int ffe_eplog_arm(ffe_eplog_handle h, const uint8_t *mask_dev, void *stream) {
   if (!h) { g_lerr = "ffe_eplog_arm: null handle"; return -1; }
   if (!(h->flags & FFE_EPLOG_ONE_SHOT)) { h->err = "ffe_eplog_arm: the log was not created one-shot (FFE_EPLOG_ONE_SHOT): a plain log records every episode"; return -1; }
-  DeviceScope scope(h->device);
+  ffe::DeviceGuard guard(h->device);
   hipLaunchKernelGGL(ffl::episode_log_arm_kernel, dim3(1), dim3(256), 0, static_cast<hipStream_t>(stream), mask_dev, h->armed, h->info, h->batch);
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) { h->err = std::string("ffe_eplog_arm: ") + hipGetErrorString(e); return -2; }
@@ -191,7 +186,7 @@ int ffe_eplog_observe(ffe_eplog_handle h, const int32_t *step_type_dev, const fl
   if (!h) { g_lerr = "ffe_eplog_observe: null handle"; return -1; }
   if (!step_type_dev || !reward_dev || !discount_dev) { h->err = "ffe_eplog_observe: a null input (only info_dev and tag_dev may be NULL)"; return -1; }
   if (tag_dev && tag_stride_ints < 1) { h->err = "ffe_eplog_observe: tag_stride_ints " + std::to_string(tag_stride_ints) + " is below 1"; return -1; }
-  DeviceScope scope(h->device);
+  ffe::DeviceGuard guard(h->device);
   const dim3 grid((h->batch + 255) / 256), block(256);
   hipStream_t s = static_cast<hipStream_t>(stream);
   if (h->flags & FFE_EPLOG_ONE_SHOT)
@@ -216,7 +211,7 @@ int ffe_eplog_buffers(ffe_eplog_handle h, void **records_dev, long long **info_d
 int ffe_eplog_destroy(ffe_eplog_handle h) {
   if (!h) { g_lerr = "ffe_eplog_destroy: null handle"; return -1; }
   {
-    DeviceScope scope(h->device);
+    ffe::DeviceGuard guard(h->device);
     free_all(h);
   }
   delete h;

@@ -1,5 +1,5 @@
-// fly_env.hip - MI355X (gfx950) batched fruit-fly environment: HIP kernels + the C ABI of
-// include/flybody_env.h.
+// fly_env.hip - MI355X (gfx950) batched fruit-fly environment: the flight kernels and their host backend (FlightEnv, at the
+// end).  The C ABI of include/flybody_env.h lives in capi.hip and reaches this file through env_backend.hpp.
 //
 // Execution model: ONE 64-lane wavefront per environment instance, one workgroup = one wavefront, one
 // launch = one control step of every env (task pre-step, nsub physics substeps, observation, reward,
@@ -20,9 +20,7 @@
 #include <string>
 #include <vector>
 
-#include "../../include/flybody_env.h"
-#include "ball_env.hpp"
-#include "walk_env.hpp"
+#include "fly_env.hpp"
 #include "dev_model.hpp"
 #include "launch_order.hpp"
 #include "dev_math.hpp"
@@ -2026,15 +2024,14 @@ __global__ void test_quat_kernel(int op, const float *a, const float *b, float *
   out[4 * i] = r.w; out[4 * i + 1] = r.x; out[4 * i + 2] = r.y; out[4 * i + 3] = r.z;
 }
 
-}  // namespace ffe
+// ================================================================================================ host side: the flight backend
+// the ordering kernel pays for itself only while the launch is a couple of rounds of resident waves: +1.7 % at 8 192 envs,
+// -0.8 % at 16 384, -1.9 % at 32 768 (measured with the phase-aware key)
+#ifndef FFE_ORDER_MAX_BATCH
+#define FFE_ORDER_MAX_BATCH 8192
+#endif
 
-// ================================================================================================ C ABI
-using namespace ffe;
-
-struct ffe_env {
-  ffb::BallEnv *ball = nullptr;  // walk_on_ball handles dispatch to ball_env.hip; everything below is the flight env
-  ffw::WalkEnv *walk = nullptr;  // free-root walking-fly physics handles dispatch to walk_env.hip
-  int device = 0, batch = 0;
+struct FlightEnv final : EnvBackend {
   DevModel dm{};
   TaskDev task{};
   DevModel *dm_dev = nullptr;
@@ -2044,428 +2041,193 @@ struct ffe_env {
   size_t state_stride = sizeof(EnvState);
   int contact_capacity = kMC;
   int *order = nullptr, *cost = nullptr;  // launch order of the envs and its sort keys (launch_order.hpp)
-  bool timing = false; double timing_ms = 0.0;  // ffe_time_kernel: events around the step kernel alone
   unsigned char *arena = nullptr;
   std::vector<void *> allocs;
-  std::string err;
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  int *forced_traj_dev = nullptr;      // staging of ffe_force_next_episode (allocated on first use)
+  KernelTimer tm;
+  int *forced_traj_dev = nullptr;      // staging of force_next_episode (allocated on first use)
   double *forced_phase_dev = nullptr;
-};
 
-static thread_local std::string g_err;
-
-// Every entry point runs on the handle's device and leaves the caller's current device untouched.
-struct DeviceGuard {
-  int prev = -1;
-  bool switched = false;
-  explicit DeviceGuard(int device) {
-    if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-    if (prev != device) { switched = (hipSetDevice(device) == hipSuccess); }
-  }
-  ~DeviceGuard() { if (switched && prev >= 0) (void)hipSetDevice(prev); }
-  DeviceGuard(const DeviceGuard &) = delete;
-  DeviceGuard &operator=(const DeviceGuard &) = delete;
-};
-
-#define HIP_OK(expr)                                                                              \
-  do {                                                                                            \
-    hipError_t _e = (expr);                                                                       \
-    if (_e != hipSuccess) throw std::runtime_error(std::string(#expr) + ": " + hipGetErrorString(_e)); \
-  } while (0)
-
-template <typename T>
-static T *upload(ffe_env *h, const T *src, size_t n) {
-  T *p = nullptr;
-  HIP_OK(hipMalloc(reinterpret_cast<void **>(&p), (n ? n : 1) * sizeof(T)));
-  h->allocs.push_back(p);
-  if (n) HIP_OK(hipMemcpy(p, src, n * sizeof(T), hipMemcpyHostToDevice));
-  return p;
-}
-
-// walk_on_ball handles: run `body` on the ball env, translating exceptions into the ABI's error codes
-#define FFE_BALL_DISPATCH(h, body)                                    \
-  if ((h) && (h)->ball) {                                             \
-    try { body; } catch (const std::exception &e_) { (h)->err = e_.what(); return -2; } \
-    return 0;                                                         \
+  ~FlightEnv() override {
+    for (void *p : allocs) (void)hipFree(p);
   }
 
-// free-root walking-fly handles (ffe_create_walk_physics): the same for walk_env.hip
-#define FFE_WALK_DISPATCH(h, body)                                    \
-  if ((h) && (h)->walk) {                                             \
-    try { body; } catch (const std::exception &e_) { (h)->err = e_.what(); return -2; } \
-    return 0;                                                         \
+  template <typename T>
+  T *alloc(size_t n) {
+    T *p = nullptr;
+    HIP_OK(hipMalloc(reinterpret_cast<void **>(&p), (n ? n : 1) * sizeof(T)));
+    allocs.push_back(p);
+    return p;
   }
-// ... and the calls such a handle refuses: bare physics is all that is built
-#define FFE_WALK_REFUSE(h, what)                                      \
-  if ((h) && (h)->walk) {                                             \
-    (h)->err = what ": not available on a walk physics handle (bare physics only: limits, floor contacts, sensors and the episode protocol are not built yet)"; \
-    return -1;                                                        \
+  template <typename T>
+  T *upload(const T *src, size_t n) {
+    T *p = alloc<T>(n);
+    if (n) HIP_OK(hipMemcpy(p, src, n * sizeof(T), hipMemcpyHostToDevice));
+    return p;
   }
 
-extern "C" {
-
-int ffe_create_walk_physics(const void *model_blob, size_t blob_size, const ffe_walk_physics_task *task, int batch, int device, ffe_handle *out) {
-  if (!out) return -1;
-  *out = nullptr;
-  std::unique_ptr<ffe_env> h(new ffe_env());
-  try {
-    if (!task) throw std::runtime_error("ffe_create_walk_physics: bad arguments");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) throw std::runtime_error("no HIP device: the MI355X path has no CPU fallback");
-    if (device < 0 || device >= ndev) throw std::runtime_error("ffe_create_walk_physics: no such device");
-    DeviceGuard guard(device);
-    h->walk = ffw::walk_create(model_blob, blob_size, task->physics_flags, batch, device);
-    h->device = device; h->batch = batch;
-  } catch (const std::exception &e) { g_err = e.what(); return -1; }
-  *out = h.release();
-  return 0;
-}
-
-int ffe_create_walk_on_ball(const void *model_blob, size_t blob_size, const ffe_ball_task *task, int batch, int device, ffe_handle *out) {
-  if (!out) return -1;
-  *out = nullptr;
-  std::unique_ptr<ffe_env> h(new ffe_env());
-  try {
-    if (!task) throw std::runtime_error("ffe_create_walk_on_ball: bad arguments");
-    ffb::BallTaskHost t{task->time_limit_steps, task->pad_first_obs, task->physics_flags, task->canonical_actions, task->clip_actions,
-                        task->control_timestep};
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) throw std::runtime_error("no HIP device: the MI355X path has no CPU fallback");
-    if (device < 0 || device >= ndev) throw std::runtime_error("ffe_create_walk_on_ball: no such device");
-    DeviceGuard guard(device);
-    h->ball = ffb::ball_create(model_blob, blob_size, t, batch, device);
-    h->device = device; h->batch = batch;
-  } catch (const std::exception &e) { g_err = e.what(); return -1; }
-  *out = h.release();
-  return 0;
-}
-int ffe_get_act(ffe_handle h, double *act_dev, void *stream) {
-  if (!h || !act_dev || (!h->ball && !h->walk)) return -1;
-  DeviceGuard guard(h->device);
-  FFE_WALK_DISPATCH(h, ffw::walk_get_act(h->walk, act_dev, stream));
-  FFE_BALL_DISPATCH(h, ffb::ball_get_act(h->ball, act_dev, stream));
-  return -1;
-}
-int ffe_set_act(ffe_handle h, const double *act_dev, void *stream) {
-  if (!h || !act_dev || (!h->ball && !h->walk)) return -1;
-  DeviceGuard guard(h->device);
-  FFE_WALK_DISPATCH(h, ffw::walk_set_act(h->walk, act_dev, stream));
-  FFE_BALL_DISPATCH(h, ffb::ball_set_act(h->ball, act_dev, stream));
-  return -1;
-}
-
-const char *ffe_version(void) { return "flybody_amd 0.1 (gfx950, wave-per-env)"; }
-const char *ffe_last_error(ffe_handle h) { return h ? h->err.c_str() : g_err.c_str(); }
-
-int ffe_create_flight(const void *model_blob, size_t blob_size, const ffe_flight_task *task, int batch, int device, uint64_t seed,
-                      uint64_t env_id_base, ffe_handle *out) {
-  if (!out) return -1;
-  *out = nullptr;
-  std::unique_ptr<ffe_env> h(new ffe_env());
-  std::unique_ptr<DeviceGuard> guard;
-  try {
-    if (!model_blob || !task || batch <= 0) throw std::runtime_error("ffe_create_flight: bad arguments");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-      throw std::runtime_error("no HIP device: the MI355X path has no CPU fallback");
-    if (device < 0 || device >= ndev) throw std::runtime_error("ffe_create_flight: no such device");
-    guard.reset(new DeviceGuard(device));
-    Blob blob(model_blob, blob_size);
-    h->host = build_host_model(blob);
-    h->device = device; h->batch = batch;
-    h->arena = upload(h.get(), h->host.arena.data(), h->host.arena.size());
-    h->host.fixup(h->dm, h->arena);
-    const ffe_flight_task &t = *task;
-    if (t.wb_nfreq <= 0 || !t.wb_beat_freqs || !t.wb_tab_off || !t.wb_traj || !t.wb_phase || t.ntraj <= 0 || t.traj_len <= 0 || !t.ref_qpos || !t.ref_qvel)
-      throw std::runtime_error("ffe_create_flight: incomplete task tables");
-    if (t.future_steps + 1 > kMaxFuture) throw std::runtime_error("future_steps too large");
-    if (t.contact_capacity != 0 && t.contact_capacity != kMC && t.contact_capacity != kMCX)
-      throw std::runtime_error("ffe_create_flight: contact_capacity must be 6 or 12 (0 = 6), got " + std::to_string(t.contact_capacity));
-    h->contact_capacity = t.contact_capacity == kMCX ? kMCX : kMC;
-    h->state_stride = h->contact_capacity == kMCX ? sizeof(EnvStateX) : sizeof(EnvState);
-    // per-trajectory row offsets (ref: trajectory_loaders.py:98-100 - trajectories of different lengths)
-    std::vector<int> toff((size_t)t.ntraj + 1);
-    for (int i = 0; i <= t.ntraj; i++) toff[i] = t.traj_off ? t.traj_off[i] : i * t.traj_len;
-    if (toff[0] != 0) throw std::runtime_error("traj_off[0] must be 0");
-    for (int i = 0; i < t.ntraj; i++)
-      if (toff[i + 1] - toff[i] < t.future_steps + 2) throw std::runtime_error("trajectories too short");
-    const size_t ref_rows = (size_t)toff[t.ntraj];
-    if (h->dm.user_action < 0 || h->dm.nwing != 6) throw std::runtime_error("model is not the flight model");
-    h->dm.nsub = (int)llround(t.wb_dt_ctrl / (double)blob.get("opt").f(0));
-    const int rows = t.wb_tab_off[t.wb_nfreq];
-    std::vector<double> frac(rows);
-    std::vector<float> trajf((size_t)rows * 6);
-    for (int i = 0; i < rows; i++) frac[i] = std::fmod(t.wb_phase[i], 1.0);
-    for (size_t i = 0; i < trajf.size(); i++) trajf[i] = (float)t.wb_traj[i];
-    TaskDev &K = h->task;
-    K.nfreq = t.wb_nfreq; K.ntraj = t.ntraj; K.future_steps = t.future_steps; K.time_limit_steps = t.time_limit_steps;
-    K.episode_limit_steps = t.episode_limit_steps > 0 ? t.episode_limit_steps : t.time_limit_steps;
-    K.pad_first_obs = t.pad_first_obs; K.flags = t.physics_flags; K.canonical = t.canonical_actions; K.clip = t.clip_actions;
-    for (int k = 0; k < 16; k++) { K.act_lo[k] = k < h->dm.naction ? h->host.action_min[k] : 0.f; K.act_hi[k] = k < h->dm.naction ? h->host.action_max[k] : 0.f; }
-    K.base_freq = t.wb_base_freq; K.rel_range = t.wb_rel_range; K.rate = t.wb_rate; K.dt_ctrl = t.wb_dt_ctrl;
-    K.terminal_com_dist = t.terminal_com_dist; K.ghost_accel_z = t.ghost_accel_z;
-    K.grid_inv_step = 0.0;
-    if (t.wb_nfreq >= 3) {  // evenly spaced and increasing (ref: pattern_generators.py:65-69 np.linspace)? then the lookup is arithmetic
-      const double step = (t.wb_beat_freqs[t.wb_nfreq - 1] - t.wb_beat_freqs[0]) / (t.wb_nfreq - 1);
-      bool even = step > 0;
-      for (int i = 0; i < t.wb_nfreq && even; i++) even = std::fabs(t.wb_beat_freqs[i] - (t.wb_beat_freqs[0] + i * step)) < 0.25 * step;
-      if (even) K.grid_inv_step = 1.0 / step;
-    }
-    set_off(K.beat_freqs, (size_t)upload(h.get(), t.wb_beat_freqs, (size_t)t.wb_nfreq));
-    set_off(K.tab_off, (size_t)upload(h.get(), t.wb_tab_off, (size_t)t.wb_nfreq + 1));
-    set_off(K.phase, (size_t)upload(h.get(), t.wb_phase, (size_t)rows));
-    set_off(K.phase_frac, (size_t)upload(h.get(), frac.data(), frac.size()));
-    set_off(K.traj, (size_t)upload(h.get(), trajf.data(), trajf.size()));
-    set_off(K.ref_qpos, (size_t)upload(h.get(), t.ref_qpos, ref_rows * 7));
-    set_off(K.ref_qvel, (size_t)upload(h.get(), t.ref_qvel, ref_rows * 6));
-    set_off(K.traj_off, (size_t)upload(h.get(), toff.data(), toff.size()));
-    K.seed = seed; K.env_id_base = env_id_base;
-    K.obs_dim = 12 + 2 * h->dm.nobsj + 7 * (t.future_steps + 1);
-    h->host.nobs = K.obs_dim;
-    h->dm_dev = upload(h.get(), &h->dm, 1);
-    h->task_dev = upload(h.get(), &h->task, 1);
-    HIP_OK(hipMalloc(&h->states, h->state_stride * (size_t)batch));
-    h->allocs.push_back(h->states);
-    HIP_OK(hipMalloc(reinterpret_cast<void **>(&h->order), sizeof(int) * (size_t)batch));
-    h->allocs.push_back(h->order);
-    HIP_OK(hipMalloc(reinterpret_cast<void **>(&h->cost), sizeof(int) * (size_t)batch));
-    h->allocs.push_back(h->cost);
-    hipLaunchKernelGGL(init_states_kernel, dim3((batch + 255) / 256), dim3(256), 0, 0, h->states, h->state_stride, h->order, h->cost, batch);
-    HIP_OK(hipGetLastError());
-    HIP_OK(hipDeviceSynchronize());
-    HIP_OK(hipEventCreate(&h->ev0));
-    HIP_OK(hipEventCreate(&h->ev1));
-  } catch (const std::exception &e) {
-    g_err = e.what();
-    for (void *p : h->allocs) (void)hipFree(p);
-    if (h->ev0) (void)hipEventDestroy(h->ev0);
-    if (h->ev1) (void)hipEventDestroy(h->ev1);
-    return -1;
+  void spec(ffe_spec_t &s) const override {
+    const int nref = task.future_steps + 1, nj = dm.nobsj;
+    s.batch = batch; s.nq = dm.nq; s.nv = dm.nv; s.nu = dm.nu; s.action_dim = dm.naction; s.obs_dim = task.obs_dim; s.nsub = dm.nsub;
+    s.physics_timestep = (double)dm.h; s.control_timestep = task.dt_ctrl;
+    s.off_accelerometer = 0; s.off_gyro = 3; s.off_joints_pos = 6; s.off_joints_vel = 6 + nj; s.off_velocimeter = 6 + 2 * nj;
+    s.off_world_zaxis = 9 + 2 * nj; s.off_ref_displacement = 12 + 2 * nj; s.off_ref_root_quat = 12 + 2 * nj + 3 * nref;
+    s.n_obs_joints = nj; s.n_ref = nref;
   }
-  *out = h.release();
-  return 0;
-}
-
-int ffe_destroy(ffe_handle h) {
-  if (!h) return -1;
-  DeviceGuard guard(h->device);
-  if (h->ball) { ffb::ball_destroy(h->ball); delete h; return 0; }
-  if (h->walk) { ffw::walk_destroy(h->walk); delete h; return 0; }
-  for (void *p : h->allocs) (void)hipFree(p);
-  if (h->ev0) (void)hipEventDestroy(h->ev0);
-  if (h->ev1) (void)hipEventDestroy(h->ev1);
-  delete h;
-  return 0;
-}
-
-int ffe_spec(ffe_handle h, ffe_spec_t *s) {
-  if (!h || !s) return -1;
-  if (h->walk) {  // no observation row: every offset is -1
-    std::memset(s, 0, sizeof(*s));
-    ffw::walk_spec(h->walk, &s->nq, &s->nv, &s->nu, &s->action_dim, &s->obs_dim, &s->nsub, &s->physics_timestep, &s->control_timestep);
-    s->batch = h->batch;
-    s->off_accelerometer = s->off_gyro = s->off_joints_pos = s->off_joints_vel = s->off_velocimeter = s->off_world_zaxis = -1;
-    s->off_ref_displacement = -1; s->off_ref_root_quat = -1;
-    return 0;
+  void action_bounds(float *mn, float *mx) const override {
+    std::memcpy(mn, host.action_min.data(), host.action_min.size() * sizeof(float));
+    std::memcpy(mx, host.action_max.data(), host.action_max.size() * sizeof(float));
   }
-  if (h->ball) {
-    std::memset(s, 0, sizeof(*s));
-    ffb::ball_spec(h->ball, &s->nq, &s->nv, &s->nu, &s->action_dim, &s->obs_dim, &s->nsub, &s->physics_timestep, &s->control_timestep);
-    s->batch = h->batch;
-    // walk_on_ball row: accelerometer 3 | actuator_activation 59 | appendages_pos 21 | ball_qvel 3 | force 18 | gyro 3 |
-    //                   joints_pos 85 | joints_vel 85 | touch 6 | velocimeter 3 | world_zaxis 3
-    s->off_accelerometer = 0; s->off_gyro = 104; s->off_joints_pos = 107; s->off_joints_vel = 192; s->off_velocimeter = 283; s->off_world_zaxis = 286;
-    s->off_ref_displacement = -1; s->off_ref_root_quat = -1; s->n_obs_joints = 85; s->n_ref = 0;
-    return 0;
-  }
-  const DevModel &M = h->dm;
-  const int nref = h->task.future_steps + 1, nj = M.nobsj;
-  s->batch = h->batch; s->nq = M.nq; s->nv = M.nv; s->nu = M.nu; s->action_dim = M.naction; s->obs_dim = h->task.obs_dim; s->nsub = M.nsub;
-  s->physics_timestep = (double)M.h; s->control_timestep = h->task.dt_ctrl;
-  s->off_accelerometer = 0; s->off_gyro = 3; s->off_joints_pos = 6; s->off_joints_vel = 6 + nj; s->off_velocimeter = 6 + 2 * nj;
-  s->off_world_zaxis = 9 + 2 * nj; s->off_ref_displacement = 12 + 2 * nj; s->off_ref_root_quat = 12 + 2 * nj + 3 * nref;
-  s->n_obs_joints = nj; s->n_ref = nref;
-  return 0;
-}
+  KernelTimer *timer() override { return &tm; }
 
-int ffe_action_bounds(ffe_handle h, float *mn, float *mx) {
-  if (!h || !mn || !mx) return -1;
-  FFE_WALK_DISPATCH(h, ffw::walk_action_bounds(h->walk, mn, mx));
-  FFE_BALL_DISPATCH(h, ffb::ball_action_bounds(h->ball, mn, mx));
-  std::memcpy(mn, h->host.action_min.data(), h->host.action_min.size() * sizeof(float));
-  std::memcpy(mx, h->host.action_max.data(), h->host.action_max.size() * sizeof(float));
-  return 0;
-}
-
-// the ordering kernel pays for itself only while the launch is a couple of rounds of resident waves: +1.7 % at 8 192 envs,
-// -0.8 % at 16 384, -1.9 % at 32 768 (measured with the phase-aware key)
-#ifndef FFE_ORDER_MAX_BATCH
-#define FFE_ORDER_MAX_BATCH 8192
-#endif
-static int launch_step(ffe_handle h, const float *act, float *obs, float *rew, float *disc, int32_t *st, void *stream, int mode, int nphys = 0,
-                       const uint8_t *mask = nullptr) {
-  if (!h) return -1;
-  if (h->walk && mode != 2) { FFE_WALK_REFUSE(h, "ffe_reset / ffe_reset_envs / ffe_step"); }
-  DeviceGuard guard(h->device);
-  FFE_WALK_DISPATCH(h, ffw::walk_physics(h->walk, act, nphys, stream));
-  FFE_BALL_DISPATCH(h, ffb::ball_launch(h->ball, act, obs, rew, disc, st, stream, mode, nphys, mask));
-  if (mode != 2 && (!obs || !rew || !disc || !st || (mode == 0 && !act))) { h->err = "null device buffer"; return -1; }
-  if (h->timing && hipEventRecord(h->ev0, static_cast<hipStream_t>(stream)) != hipSuccess) return -2;
-  if (h->contact_capacity == kMCX)
-    hipLaunchKernelGGL(flight_step_kernel<kMCX>, dim3(h->batch), dim3(kWave), 0, static_cast<hipStream_t>(stream), h->dm_dev, h->task_dev, static_cast<EnvStateX *>(h->states), act,
-                       obs, rew, disc, st, h->batch, mode, nphys, h->order, h->cost, mask);
-  else
-    hipLaunchKernelGGL(flight_step_kernel<kMC>, dim3(h->batch), dim3(kWave), 0, static_cast<hipStream_t>(stream), h->dm_dev, h->task_dev, static_cast<EnvState *>(h->states), act, obs, rew,
-                       disc, st, h->batch, mode, nphys, h->order, h->cost, mask);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) { h->err = hipGetErrorString(e); return -2; }
-  if (h->timing && hipEventRecord(h->ev1, static_cast<hipStream_t>(stream)) != hipSuccess) return -2;
-  // measured: +2 % env-steps/s at B = 8 192 (two rounds of the 4 096 resident waves); beyond that the tail the order shortens
-  // is a smaller share of the launch than the serialised sort kernel itself (-1.5 % at 16 384, -2 % at 32 768): not sorted
-  if (mode == 0 && h->batch > 1 && h->batch <= FFE_ORDER_MAX_BATCH && !(h->task.flags & DBG_NO_ORDER)) {
-    hipLaunchKernelGGL(ffe_order::order_by_cost, dim3(1), dim3(1024), 0, static_cast<hipStream_t>(stream), h->cost, h->order, h->batch);
-    e = hipGetLastError();
-    if (e != hipSuccess) { h->err = hipGetErrorString(e); return -2; }
-  }
-  if (h->timing) {
-    float t = 0.f;
-    if (hipEventSynchronize(h->ev1) != hipSuccess || hipEventElapsedTime(&t, h->ev0, h->ev1) != hipSuccess) return -2;
-    h->timing_ms += t;
-  }
-  return 0;
-}
-
-int ffe_reset(ffe_handle h, float *obs, float *rew, float *disc, int32_t *st, void *stream) { return launch_step(h, nullptr, obs, rew, disc, st, stream, 1); }
-int ffe_reset_envs(ffe_handle h, const uint8_t *mask, float *obs, float *rew, float *disc, int32_t *st, void *stream) {
-  if (!h) return -1;
-  if (!mask) { h->err = "null reset mask"; return -1; }
-  return launch_step(h, nullptr, obs, rew, disc, st, stream, 3, 0, mask);
-}
-int ffe_step(ffe_handle h, const float *act, float *obs, float *rew, float *disc, int32_t *st, void *stream) {
-  return launch_step(h, act, obs, rew, disc, st, stream, 0);
-}
-
-int ffe_physics_step(ffe_handle h, const float *ctrl, int nsteps, void *stream) {
-  if (!h || !ctrl || nsteps <= 0) return -1;
-  return launch_step(h, ctrl, nullptr, nullptr, nullptr, nullptr, stream, 2, nsteps);
-}
-
-int ffe_force_next_episode(ffe_handle h, const int32_t *traj, const double *phase, void *stream) {
-  if (!h || !traj || !phase) return -1;
-  FFE_WALK_REFUSE(h, "ffe_force_next_episode");
-  if (h->ball) { h->err = "walk_on_ball episodes have no per-episode randomness"; return -1; }
-  DeviceGuard guard(h->device);
-  try {
-    for (int i = 0; i < h->batch; i++)
-      if (traj[i] >= h->task.ntraj) throw std::runtime_error("ffe_force_next_episode: trajectory index out of range");
+  void launch(const float *act, float *obs, float *rew, float *disc, int32_t *st, void *stream, int mode, int nphys, const uint8_t *mask) override {
+    if (mode != 2 && (!obs || !rew || !disc || !st || (mode == 0 && !act))) throw Refused("null device buffer");
     hipStream_t s = static_cast<hipStream_t>(stream);
-    if (!h->forced_traj_dev) {
-      HIP_OK(hipMalloc(reinterpret_cast<void **>(&h->forced_traj_dev), sizeof(int) * h->batch));
-      h->allocs.push_back(h->forced_traj_dev);
-      HIP_OK(hipMalloc(reinterpret_cast<void **>(&h->forced_phase_dev), sizeof(double) * h->batch));
-      h->allocs.push_back(h->forced_phase_dev);
+    tm.start(s);
+    if (contact_capacity == kMCX)
+      hipLaunchKernelGGL(flight_step_kernel<kMCX>, dim3(batch), dim3(kWave), 0, s, dm_dev, task_dev, static_cast<EnvStateX *>(states), act, obs, rew, disc, st, batch,
+                         mode, nphys, order, cost, mask);
+    else
+      hipLaunchKernelGGL(flight_step_kernel<kMC>, dim3(batch), dim3(kWave), 0, s, dm_dev, task_dev, static_cast<EnvState *>(states), act, obs, rew, disc, st, batch,
+                         mode, nphys, order, cost, mask);
+    HIP_OK(hipGetLastError());
+    tm.stop(s);
+    // measured: +2 % env-steps/s at B = 8 192 (two rounds of the 4 096 resident waves); beyond that the tail the order shortens
+    // is a smaller share of the launch than the serialised sort kernel itself (-1.5 % at 16 384, -2 % at 32 768): not sorted
+    if (mode == 0 && batch > 1 && batch <= FFE_ORDER_MAX_BATCH && !(task.flags & DBG_NO_ORDER)) {
+      hipLaunchKernelGGL(ffe_order::order_by_cost, dim3(1), dim3(1024), 0, s, cost, order, batch);
+      HIP_OK(hipGetLastError());
+    }
+    tm.collect();
+  }
+
+  void force_next_episode(const int32_t *traj, const double *phase, void *stream) override {
+    for (int i = 0; i < batch; i++)
+      if (traj[i] >= task.ntraj) throw Refused("ffe_force_next_episode: trajectory index out of range");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (!forced_traj_dev) {
+      forced_traj_dev = alloc<int>(batch);
+      forced_phase_dev = alloc<double>(batch);
     }
     // pageable host memory: the copies are staged before the calls return, ordered on `s` with the kernel below; the stream
     // is synchronised once so that a second call cannot overwrite the staging buffers under a pending kernel
-    HIP_OK(hipMemcpyAsync(h->forced_traj_dev, traj, sizeof(int) * h->batch, hipMemcpyHostToDevice, s));
-    HIP_OK(hipMemcpyAsync(h->forced_phase_dev, phase, sizeof(double) * h->batch, hipMemcpyHostToDevice, s));
-    hipLaunchKernelGGL(force_next_kernel, dim3((h->batch + 255) / 256), dim3(256), 0, s, h->states, h->state_stride, h->forced_traj_dev, h->forced_phase_dev, h->batch);
+    HIP_OK(hipMemcpyAsync(forced_traj_dev, traj, sizeof(int) * batch, hipMemcpyHostToDevice, s));
+    HIP_OK(hipMemcpyAsync(forced_phase_dev, phase, sizeof(double) * batch, hipMemcpyHostToDevice, s));
+    hipLaunchKernelGGL(force_next_kernel, dim3((batch + 255) / 256), dim3(256), 0, s, states, state_stride, forced_traj_dev, forced_phase_dev, batch);
     HIP_OK(hipGetLastError());
     HIP_OK(hipStreamSynchronize(s));
-  } catch (const std::exception &e) { h->err = e.what(); return -1; }
-  return 0;
-}
-
-int ffe_get_state(ffe_handle h, double *qpos, double *qvel, void *stream) {
-  if (!h || !qpos || !qvel) return -1;
-  DeviceGuard guard(h->device);
-  FFE_WALK_DISPATCH(h, ffw::walk_get_state(h->walk, qpos, qvel, stream));
-  FFE_BALL_DISPATCH(h, ffb::ball_get_state(h->ball, qpos, qvel, stream));
-  hipLaunchKernelGGL(get_state_kernel, dim3(h->batch), dim3(kWave), 0, static_cast<hipStream_t>(stream), h->states, h->state_stride, qpos, qvel, h->batch, h->dm.nq, h->dm.nv);
-  return hipGetLastError() == hipSuccess ? 0 : -2;
-}
-int ffe_set_state(ffe_handle h, const double *qpos, const double *qvel, void *stream) {
-  if (!h || !qpos || !qvel) return -1;
-  DeviceGuard guard(h->device);
-  FFE_WALK_DISPATCH(h, ffw::walk_set_state(h->walk, qpos, qvel, stream));
-  FFE_BALL_DISPATCH(h, ffb::ball_set_state(h->ball, qpos, qvel, stream));
-  hipLaunchKernelGGL(set_state_kernel, dim3(h->batch), dim3(kWave), 0, static_cast<hipStream_t>(stream), h->states, h->state_stride, qpos, qvel, h->batch, h->dm.nq, h->dm.nv);
-  return hipGetLastError() == hipSuccess ? 0 : -2;
-}
-int ffe_get_validity(ffe_handle h, int32_t *info, void *stream) {
-  if (!h) return -1;
-  if (!info || (reinterpret_cast<uintptr_t>(info) & 15)) { h->err = "ffe_get_validity: info_dev must be a 16-byte aligned device buffer"; return -1; }
-  DeviceGuard guard(h->device);
-  FFE_WALK_DISPATCH(h, ffw::walk_get_validity(h->walk, info, stream));
-  FFE_BALL_DISPATCH(h, ffb::ball_get_validity(h->ball, info, stream));
-  hipLaunchKernelGGL(get_validity_kernel, dim3((h->batch + 255) / 256), dim3(256), 0, static_cast<hipStream_t>(stream), h->states, h->state_stride, info, h->batch);
-  return hipGetLastError() == hipSuccess ? 0 : -2;
-}
-int ffe_get_task_state(ffe_handle h, int32_t *ints, double *reals, void *stream) {
-  if (!h || !ints || !reals) return -1;
-  DeviceGuard guard(h->device);
-  FFE_WALK_DISPATCH(h, ffw::walk_get_task_state(h->walk, ints, reals, stream));
-  FFE_BALL_DISPATCH(h, ffb::ball_get_task_state(h->ball, ints, reals, stream));
-  hipLaunchKernelGGL(get_task_state_kernel, dim3((h->batch + 255) / 256), dim3(256), 0, static_cast<hipStream_t>(stream), h->states, h->state_stride, ints, reals, h->batch);
-  return hipGetLastError() == hipSuccess ? 0 : -2;
-}
-
-int ffe_time_steps(ffe_handle h, const float *act, float *obs, float *rew, float *disc, int32_t *st, int iters, void *stream, float *ms) {
-  if (!h || !ms || iters <= 0) return -1;
-  FFE_WALK_REFUSE(h, "ffe_time_steps");
-  DeviceGuard guard(h->device);
-  FFE_BALL_DISPATCH(h, *ms = ffb::ball_time_steps(h->ball, act, obs, rew, disc, st, iters, stream));
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  if (hipEventRecord(h->ev0, s) != hipSuccess) return -2;
-  for (int i = 0; i < iters; i++) {
-    int rc = launch_step(h, act, obs, rew, disc, st, stream, 0);
-    if (rc) return rc;
   }
-  if (hipEventRecord(h->ev1, s) != hipSuccess) return -2;
-  if (hipEventSynchronize(h->ev1) != hipSuccess) return -2;
-  float total = 0.f;
-  if (hipEventElapsedTime(&total, h->ev0, h->ev1) != hipSuccess) return -2;
-  *ms = total / (float)iters;
-  return 0;
+
+  void get_state(double *qpos, double *qvel, void *stream) override {
+    hipLaunchKernelGGL(get_state_kernel, dim3(batch), dim3(kWave), 0, static_cast<hipStream_t>(stream), states, state_stride, qpos, qvel, batch, dm.nq, dm.nv);
+    HIP_OK(hipGetLastError());
+  }
+  void set_state(const double *qpos, const double *qvel, void *stream) override {
+    hipLaunchKernelGGL(set_state_kernel, dim3(batch), dim3(kWave), 0, static_cast<hipStream_t>(stream), states, state_stride, qpos, qvel, batch, dm.nq, dm.nv);
+    HIP_OK(hipGetLastError());
+  }
+  void get_validity(int32_t *info, void *stream) override {
+    hipLaunchKernelGGL(get_validity_kernel, dim3((batch + 255) / 256), dim3(256), 0, static_cast<hipStream_t>(stream), states, state_stride, info, batch);
+    HIP_OK(hipGetLastError());
+  }
+  void get_task_state(int32_t *ints, double *reals, void *stream) override {
+    hipLaunchKernelGGL(get_task_state_kernel, dim3((batch + 255) / 256), dim3(256), 0, static_cast<hipStream_t>(stream), states, state_stride, ints, reals, batch);
+    HIP_OK(hipGetLastError());
+  }
+};
+
+std::unique_ptr<EnvBackend> flight_create(const void *model_blob, size_t blob_size, const ffe_flight_task &t, int batch, int device, uint64_t seed,
+                                          uint64_t env_id_base) {
+  std::unique_ptr<FlightEnv> h(new FlightEnv());  // frees the device allocations made so far if a later step throws
+  Blob blob(model_blob, blob_size);
+  h->host = build_host_model(blob);
+  h->device = device; h->batch = batch;
+  h->arena = h->upload(h->host.arena.data(), h->host.arena.size());
+  h->host.fixup(h->dm, h->arena);
+  if (t.wb_nfreq <= 0 || !t.wb_beat_freqs || !t.wb_tab_off || !t.wb_traj || !t.wb_phase || t.ntraj <= 0 || t.traj_len <= 0 || !t.ref_qpos || !t.ref_qvel)
+    throw std::runtime_error("ffe_create_flight: incomplete task tables");
+  if (t.future_steps + 1 > kMaxFuture) throw std::runtime_error("future_steps too large");
+  if (t.contact_capacity != 0 && t.contact_capacity != kMC && t.contact_capacity != kMCX)
+    throw std::runtime_error("ffe_create_flight: contact_capacity must be 6 or 12 (0 = 6), got " + std::to_string(t.contact_capacity));
+  h->contact_capacity = t.contact_capacity == kMCX ? kMCX : kMC;
+  h->state_stride = h->contact_capacity == kMCX ? sizeof(EnvStateX) : sizeof(EnvState);
+  // per-trajectory row offsets (ref: trajectory_loaders.py:98-100 - trajectories of different lengths)
+  std::vector<int> toff((size_t)t.ntraj + 1);
+  for (int i = 0; i <= t.ntraj; i++) toff[i] = t.traj_off ? t.traj_off[i] : i * t.traj_len;
+  if (toff[0] != 0) throw std::runtime_error("traj_off[0] must be 0");
+  for (int i = 0; i < t.ntraj; i++)
+    if (toff[i + 1] - toff[i] < t.future_steps + 2) throw std::runtime_error("trajectories too short");
+  const size_t ref_rows = (size_t)toff[t.ntraj];
+  if (h->dm.user_action < 0 || h->dm.nwing != 6) throw std::runtime_error("model is not the flight model");
+  h->dm.nsub = (int)llround(t.wb_dt_ctrl / (double)blob.get("opt").f(0));
+  const int rows = t.wb_tab_off[t.wb_nfreq];
+  std::vector<double> frac(rows);
+  std::vector<float> trajf((size_t)rows * 6);
+  for (int i = 0; i < rows; i++) frac[i] = std::fmod(t.wb_phase[i], 1.0);
+  for (size_t i = 0; i < trajf.size(); i++) trajf[i] = (float)t.wb_traj[i];
+  TaskDev &K = h->task;
+  K.nfreq = t.wb_nfreq; K.ntraj = t.ntraj; K.future_steps = t.future_steps; K.time_limit_steps = t.time_limit_steps;
+  K.episode_limit_steps = t.episode_limit_steps > 0 ? t.episode_limit_steps : t.time_limit_steps;
+  K.pad_first_obs = t.pad_first_obs; K.flags = t.physics_flags; K.canonical = t.canonical_actions; K.clip = t.clip_actions;
+  for (int k = 0; k < 16; k++) { K.act_lo[k] = k < h->dm.naction ? h->host.action_min[k] : 0.f; K.act_hi[k] = k < h->dm.naction ? h->host.action_max[k] : 0.f; }
+  K.base_freq = t.wb_base_freq; K.rel_range = t.wb_rel_range; K.rate = t.wb_rate; K.dt_ctrl = t.wb_dt_ctrl;
+  K.terminal_com_dist = t.terminal_com_dist; K.ghost_accel_z = t.ghost_accel_z;
+  K.grid_inv_step = 0.0;
+  if (t.wb_nfreq >= 3) {  // evenly spaced and increasing (ref: pattern_generators.py:65-69 np.linspace)? then the lookup is arithmetic
+    const double step = (t.wb_beat_freqs[t.wb_nfreq - 1] - t.wb_beat_freqs[0]) / (t.wb_nfreq - 1);
+    bool even = step > 0;
+    for (int i = 0; i < t.wb_nfreq && even; i++) even = std::fabs(t.wb_beat_freqs[i] - (t.wb_beat_freqs[0] + i * step)) < 0.25 * step;
+    if (even) K.grid_inv_step = 1.0 / step;
+  }
+  set_off(K.beat_freqs, (size_t)h->upload(t.wb_beat_freqs, (size_t)t.wb_nfreq));
+  set_off(K.tab_off, (size_t)h->upload(t.wb_tab_off, (size_t)t.wb_nfreq + 1));
+  set_off(K.phase, (size_t)h->upload(t.wb_phase, (size_t)rows));
+  set_off(K.phase_frac, (size_t)h->upload(frac.data(), frac.size()));
+  set_off(K.traj, (size_t)h->upload(trajf.data(), trajf.size()));
+  set_off(K.ref_qpos, (size_t)h->upload(t.ref_qpos, ref_rows * 7));
+  set_off(K.ref_qvel, (size_t)h->upload(t.ref_qvel, ref_rows * 6));
+  set_off(K.traj_off, (size_t)h->upload(toff.data(), toff.size()));
+  K.seed = seed; K.env_id_base = env_id_base;
+  K.obs_dim = 12 + 2 * h->dm.nobsj + 7 * (t.future_steps + 1);
+  h->host.nobs = K.obs_dim;
+  h->dm_dev = h->upload(&h->dm, 1);
+  h->task_dev = h->upload(&h->task, 1);
+  h->states = h->alloc<unsigned char>(h->state_stride * (size_t)batch);
+  h->order = h->alloc<int>((size_t)batch);
+  h->cost = h->alloc<int>((size_t)batch);
+  hipLaunchKernelGGL(init_states_kernel, dim3((batch + 255) / 256), dim3(256), 0, 0, h->states, h->state_stride, h->order, h->cost, batch);
+  HIP_OK(hipGetLastError());
+  HIP_OK(hipDeviceSynchronize());
+  h->tm.create();
+  return h;
 }
 
-int ffe_time_kernel(ffe_handle h, const float *act, float *obs, float *rew, float *disc, int32_t *st, int iters, void *stream, float *ms) {
-  if (!h || !ms || iters <= 0) return -1;
-  FFE_WALK_REFUSE(h, "ffe_time_kernel");
-  DeviceGuard guard(h->device);
-  FFE_BALL_DISPATCH(h, *ms = ffb::ball_time_kernel(h->ball, act, obs, rew, disc, st, iters, stream));
-  h->timing = true; h->timing_ms = 0.0;
-  int rc = 0;
-  for (int i = 0; i < iters && !rc; i++) rc = launch_step(h, act, obs, rew, disc, st, stream, 0);
-  h->timing = false;
-  *ms = (float)(h->timing_ms / iters);
-  return rc;
-}
+}  // namespace ffe
+
+extern "C" {
 
 #ifdef FFE_STAMPS
 int ffe_debug_read_stamps(unsigned long long *out16, int reset) {
-  if (hipMemcpyFromSymbol(out16, HIP_SYMBOL(g_stamps), 20 * sizeof(unsigned long long)) != hipSuccess) return -1;
-  if (reset) { unsigned long long z[20] = {0}; if (hipMemcpyToSymbol(HIP_SYMBOL(g_stamps), z, sizeof(z)) != hipSuccess) return -1; }
+  if (hipMemcpyFromSymbol(out16, HIP_SYMBOL(ffe::g_stamps), 20 * sizeof(unsigned long long)) != hipSuccess) return -1;
+  if (reset) { unsigned long long z[20] = {0}; if (hipMemcpyToSymbol(HIP_SYMBOL(ffe::g_stamps), z, sizeof(z)) != hipSuccess) return -1; }
   return 0;
 }
 #endif
 
 #ifdef FFE_DBGCF
-int ffe_debug_read_cf(float *out) { return hipMemcpyFromSymbol(out, HIP_SYMBOL(g_dbgcf), sizeof(float) * 64 * (4 + 6 * 12)) == hipSuccess ? 0 : -1; }
+int ffe_debug_read_cf(float *out) { return hipMemcpyFromSymbol(out, HIP_SYMBOL(ffe::g_dbgcf), sizeof(float) * 64 * (4 + 6 * 12)) == hipSuccess ? 0 : -1; }
 #endif
 
 #ifdef FFE_TRACE
 // rows of {start clock, end clock, HW_ID, XCC_ID} per workgroup of the last flight launch (walk_on_ball: ffb_debug_read_trace)
 int ffe_debug_read_trace(unsigned long long *out, int nrows) {
-  if (hipMemcpyFromSymbol(out, HIP_SYMBOL(g_trace), (size_t)nrows * 4 * sizeof(unsigned long long)) != hipSuccess) return -1;
+  if (hipMemcpyFromSymbol(out, HIP_SYMBOL(ffe::g_trace), (size_t)nrows * 4 * sizeof(unsigned long long)) != hipSuccess) return -1;
   return 0;
 }
 #endif
 
 int ffe_test_quat(int op, const float *a, const float *b, float *out, int n, void *stream) {
   if (!a || !b || !out || n <= 0) return -1;
-  hipLaunchKernelGGL(test_quat_kernel, dim3((n + 255) / 256), dim3(256), 0, static_cast<hipStream_t>(stream), op, a, b, out, n);
+  hipLaunchKernelGGL(ffe::test_quat_kernel, dim3((n + 255) / 256), dim3(256), 0, static_cast<hipStream_t>(stream), op, a, b, out, n);
   return hipGetLastError() == hipSuccess ? 0 : -2;
 }
 

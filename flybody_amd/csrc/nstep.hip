@@ -29,7 +29,7 @@
 #include <stdexcept>
 #include <string>
 
-#include "../../include/flybody_env.h"
+#include "env_backend.hpp"
 #include "nstep_ring.hpp"
 
 namespace ffn {
@@ -270,10 +270,9 @@ static int nstep_create(int batch, int obs_dim, int act_dim, int n_step, float d
              ", the rows one call can write: they would share slots of the ring";
     return -1;
   }
-  int ndev = 0, prev = -1;
+  int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || device < 0 || device >= ndev) { g_nerr = "no such HIP device: the MI355X path has no CPU fallback"; return -1; }
-  (void)hipGetDevice(&prev);
-  (void)hipSetDevice(device);
+  ffe::DeviceGuard guard(device);
   std::unique_ptr<ffe_nstep> p(new ffe_nstep());
   Handle &H = p->h;
   H.device = device;
@@ -294,7 +293,6 @@ static int nstep_create(int batch, int obs_dim, int act_dim, int n_step, float d
   D.t_next = (float *)alloc(C * O * 4); D.written = (unsigned long long *)alloc(8);
   if (tracked) { D.r_mark = (unsigned char *)alloc(B * n); D.prev_bits = (int *)alloc(B * 4); D.t_taint = (unsigned char *)alloc(C); }
   (void)hipDeviceSynchronize();
-  if (prev >= 0 && prev != device) (void)hipSetDevice(prev);
   if (!ok) {
     for (int k = 0; k < H.nalloc; k++) (void)hipFree(H.allocs[k]);
     g_nerr = "ffe_nstep_create: out of device memory";
@@ -313,11 +311,8 @@ int ffe_nstep_create_tracked(int batch, int obs_dim, int act_dim, int n_step, fl
 
 int ffe_nstep_destroy(ffe_nstep_handle p) {
   if (!p) return -1;
-  int prev = -1;
-  (void)hipGetDevice(&prev);
-  (void)hipSetDevice(p->h.device);
+  ffe::DeviceGuard guard(p->h.device);
   for (int k = 0; k < p->h.nalloc; k++) (void)hipFree(p->h.allocs[k]);
-  if (prev >= 0 && prev != p->h.device) (void)hipSetDevice(prev);
   delete p;
   return 0;
 }
@@ -326,9 +321,7 @@ int ffe_nstep_destroy(ffe_nstep_handle p) {
 static int nstep_observe(ffe_nstep_handle p, const float *action_dev, const int32_t *step_type_dev, const float *reward_dev, const float *discount_dev,
                          const float *obs_dev, const int32_t *step_bits_dev, int stride_ints, void *stream) {
   if (!p || !step_type_dev || !reward_dev || !discount_dev || !obs_dev || !action_dev) return -1;
-  int prev = -1;
-  (void)hipGetDevice(&prev);
-  if (prev != p->h.device) (void)hipSetDevice(p->h.device);
+  ffe::DeviceGuard guard(p->h.device);
   const dim3 grid((p->h.d.batch + ffn::kEnvsPerBlock - 1) / ffn::kEnvsPerBlock), block(64 * ffn::kEnvsPerBlock);
   if (p->h.d.t_taint)
     hipLaunchKernelGGL(ffn::nstep_observe_kernel<true>, grid, block, 0, static_cast<hipStream_t>(stream), p->h.d, action_dev, step_type_dev, reward_dev, discount_dev,
@@ -337,7 +330,6 @@ static int nstep_observe(ffe_nstep_handle p, const float *action_dev, const int3
     hipLaunchKernelGGL(ffn::nstep_observe_kernel<false>, grid, block, 0, static_cast<hipStream_t>(stream), p->h.d, action_dev, step_type_dev, reward_dev, discount_dev,
                        obs_dev, static_cast<const int32_t *>(nullptr), 0);
   const hipError_t e = hipGetLastError();
-  if (prev >= 0 && prev != p->h.device) (void)hipSetDevice(prev);
   if (e != hipSuccess) { p->h.err = hipGetErrorString(e); return -2; }
   return 0;
 }

@@ -24,7 +24,7 @@
 #include <memory>
 #include <string>
 
-#include "../../include/flybody_env.h"
+#include "env_backend.hpp"
 #include "nstep_ring.hpp"
 
 namespace ffs {
@@ -227,10 +227,9 @@ int ffe_sampler_create(const ffe_nstep_handle *writers, int n_writers, int batch
     host[r] = ffs::Ring{D.t_obs, D.t_act, D.t_ret, D.t_disc, D.t_next, D.t_taint, D.written, (unsigned long long)D.capacity};
   }
   if ((flags & FFE_SAMPLE_SKIP_TAINTED) && !tracked) return fail("FFE_SAMPLE_SKIP_TAINTED needs every writer created with validity tracking (ffe_nstep_create_tracked)");
-  int ndev = 0, prev = -1;
+  int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || device < 0 || device >= ndev) return fail("no such HIP device: the MI355X path has no CPU fallback");
-  (void)hipGetDevice(&prev);
-  (void)hipSetDevice(device);
+  ffe::DeviceGuard guard(device);
   std::unique_ptr<ffe_sampler> p(new ffe_sampler());
   p->device = device; p->n_rings = n_writers; p->batch = batch; p->flags = flags; p->tracked = tracked;
   p->obs_dim = writers[0]->h.d.obs_dim; p->act_dim = writers[0]->h.d.act_dim;
@@ -244,7 +243,6 @@ int ffe_sampler_create(const ffe_nstep_handle *writers, int n_writers, int batch
          hipDeviceSynchronize() == hipSuccess;
   }
   if (!ok) { (void)hipFree(p->rings); (void)hipFree(p->ctrl); (void)hipFree(p->state); (void)hipFree(p->info); }
-  if (prev >= 0 && prev != device) (void)hipSetDevice(prev);
   if (!ok) return fail("out of device memory");
   *out = p.release();
   return 0;
@@ -255,9 +253,7 @@ int ffe_sampler_sample(ffe_sampler_handle s, float *obs_dev, float *act_dev, flo
   if (!s) { g_serr = "ffe_sampler_sample: null handle"; return -1; }
   if (!obs_dev || !act_dev || !ret_dev || !disc_dev || !next_obs_dev) { s->err = "ffe_sampler_sample: a null output (only taint_dev and index_dev may be NULL)"; return -1; }
   if (taint_dev && !s->tracked) { s->err = "ffe_sampler_sample: taint_dev needs every writer created with validity tracking (ffe_nstep_create_tracked)"; return -1; }
-  int prev = -1;
-  (void)hipGetDevice(&prev);
-  if (prev != s->device) (void)hipSetDevice(s->device);
+  ffe::DeviceGuard guard(s->device);
   hipStream_t st = static_cast<hipStream_t>(stream);
   hipLaunchKernelGGL(ffs::sampler_prologue_kernel, dim3(1), dim3(64), 0, st, s->rings, s->n_rings, s->seed, s->min_size, (unsigned long long)s->batch, s->state,
                      s->ctrl, s->info);
@@ -273,7 +269,6 @@ int ffe_sampler_sample(ffe_sampler_handle s, float *obs_dev, float *act_dev, flo
                          ret_dev, disc_dev, next_obs_dev, taint_dev, index, s->info);
     e = hipGetLastError();
   }
-  if (prev >= 0 && prev != s->device) (void)hipSetDevice(prev);
   if (e != hipSuccess) { s->err = std::string("ffe_sampler_sample: ") + hipGetErrorString(e); return -2; }
   return 0;
 }
@@ -287,11 +282,8 @@ int ffe_sampler_info(ffe_sampler_handle s, long long **info_dev) {
 
 int ffe_sampler_destroy(ffe_sampler_handle s) {
   if (!s) { g_serr = "ffe_sampler_destroy: null handle"; return -1; }
-  int prev = -1;
-  (void)hipGetDevice(&prev);
-  (void)hipSetDevice(s->device);
+  ffe::DeviceGuard guard(s->device);
   (void)hipFree(s->rings); (void)hipFree(s->ctrl); (void)hipFree(s->state); (void)hipFree(s->info);
-  if (prev >= 0 && prev != s->device) (void)hipSetDevice(prev);
   delete s;
   return 0;
 }

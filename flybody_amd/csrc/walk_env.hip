@@ -350,78 +350,78 @@ __global__ void walk_act_kernel(WState *states, double *act, int batch, int set)
 }
 
 // ================================================================================================ host side
-#define HIPW_OK(expr)                                                                               \
-  do {                                                                                              \
-    hipError_t _e = (expr);                                                                         \
-    if (_e != hipSuccess) throw std::runtime_error(std::string(#expr) + ": " + hipGetErrorString(_e)); \
-  } while (0)
-
-struct WalkEnv {
-  int device = 0, batch = 0, flags = 0;
+// Bare physics is all that is built: reset, step, forced episodes and the timers are refused.
+struct WalkEnv final : ffe::EnvBackend {
+  int flags = 0;
   WalkHost host;
   WalkModel *model_dev = nullptr;
   WState *states = nullptr;
+
+  ~WalkEnv() override {
+    (void)hipFree(model_dev); (void)hipFree(states);
+  }
+
+  [[noreturn]] void refuse(const char *what) const override {
+    throw ffe::Refused(std::string(what) + ": not available on a walk physics handle (bare physics only: limits, floor contacts, sensors and the episode protocol are not built yet)");
+  }
+
+  void spec(ffe_spec_t &s) const override {  // no observation row: every offset is -1
+    s = ffe_spec_t{};
+    s.batch = batch; s.nq = host.nq; s.nv = host.nv; s.nu = NU; s.action_dim = NACT; s.obs_dim = 0; s.nsub = host.m.b.nsub;
+    s.physics_timestep = host.m.b.h; s.control_timestep = (double)host.m.b.nsub * (double)host.m.b.h;
+    s.off_accelerometer = s.off_gyro = s.off_joints_pos = s.off_joints_vel = s.off_velocimeter = s.off_world_zaxis = -1;
+    s.off_ref_displacement = -1; s.off_ref_root_quat = -1;
+  }
+  void action_bounds(float *mn, float *mx) const override {
+    for (int k = 0; k < NACT; k++) { mn[k] = host.action_min[k]; mx[k] = host.action_max[k]; }
+  }
+  void launch(const float *ctrl, float *, float *, float *, int32_t *, void *stream, int mode, int nphys, const uint8_t *) override {  // ctrl[B][59]
+    if (mode != 2) refuse("ffe_reset / ffe_reset_envs / ffe_step");
+    if (!ctrl || nphys <= 0) throw std::runtime_error("walk physics: null control buffer or no steps");
+    hipLaunchKernelGGL(walk_step_kernel, dim3(batch), dim3(64), 0, (hipStream_t)stream, model_dev, flags, states, ctrl, batch, nphys);
+    HIP_OK(hipGetLastError());
+  }
+  void get_state(double *qpos, double *qvel, void *stream) override {  // qpos[B][109], qvel[B][108]: MuJoCo's free-joint layout
+    hipLaunchKernelGGL(walk_get_state_kernel, dim3(batch), dim3(128), 0, (hipStream_t)stream, states, qpos, qvel, batch);
+    HIP_OK(hipGetLastError());
+  }
+  void set_state(const double *qpos, const double *qvel, void *stream) override {
+    hipLaunchKernelGGL(walk_set_state_kernel, dim3(batch), dim3(128), 0, (hipStream_t)stream, states, qpos, qvel, batch);
+    HIP_OK(hipGetLastError());
+  }
+  void get_act(double *act, void *stream) override {
+    hipLaunchKernelGGL(walk_act_kernel, dim3(batch), dim3(64), 0, (hipStream_t)stream, states, act, batch, 0);
+    HIP_OK(hipGetLastError());
+  }
+  void set_act(const double *act, void *stream) override {
+    hipLaunchKernelGGL(walk_act_kernel, dim3(batch), dim3(64), 0, (hipStream_t)stream, states, const_cast<double *>(act), batch, 1);
+    HIP_OK(hipGetLastError());
+  }
+  void get_task_state(int32_t *ints, double *reals, void *stream) override {  // int32[B][8] and float64[B][8]: zeros
+    HIP_OK(hipMemsetAsync(ints, 0, sizeof(int32_t) * 8 * (size_t)batch, (hipStream_t)stream));
+    HIP_OK(hipMemsetAsync(reals, 0, sizeof(double) * 8 * (size_t)batch, (hipStream_t)stream));
+  }
+  void get_validity(int32_t *info, void *stream) override {  // int32[B][4]: zeros
+    HIP_OK(hipMemsetAsync(info, 0, sizeof(int32_t) * 4 * (size_t)batch, (hipStream_t)stream));
+  }
 };
 
-struct WalkEnvDeleter { void operator()(WalkEnv *e) const { walk_destroy(e); } };
-
-WalkEnv *walk_create(const void *blob, size_t blob_size, int physics_flags, int batch, int device) {
+std::unique_ptr<ffe::EnvBackend> walk_create(const void *blob, size_t blob_size, int physics_flags, int batch, int device) {
   if (!blob || batch <= 0) throw std::runtime_error("ffe_create_walk_physics: bad arguments");
   if ((physics_flags & (BF_NO_CONTACT | BF_NO_LIMIT)) != (BF_NO_CONTACT | BF_NO_LIMIT))
     throw std::runtime_error("ffe_create_walk_physics: floor contacts and joint limits are not built yet: physics_flags must contain FFE_NO_CONTACT | FFE_NO_LIMIT");
-  std::unique_ptr<WalkEnv, WalkEnvDeleter> e(new WalkEnv());  // frees the device allocations made so far if a later step throws
+  std::unique_ptr<WalkEnv> e(new WalkEnv());  // frees the device allocations made so far if a later step throws
   Blob b(blob, blob_size);
   e->host = build_walk_model(b);
   e->device = device; e->batch = batch; e->flags = physics_flags;
   e->host.m.b.nsub = 10;  // ffe_spec's figure: the reference's control step of 2 ms over the model's 0.2 ms (nothing here steps by it)
-  HIPW_OK(hipMalloc((void **)&e->model_dev, sizeof(WalkModel)));
-  HIPW_OK(hipMemcpy(e->model_dev, &e->host.m, sizeof(WalkModel), hipMemcpyHostToDevice));
-  HIPW_OK(hipMalloc((void **)&e->states, sizeof(WState) * (size_t)batch));
+  HIP_OK(hipMalloc((void **)&e->model_dev, sizeof(WalkModel)));
+  HIP_OK(hipMemcpy(e->model_dev, &e->host.m, sizeof(WalkModel), hipMemcpyHostToDevice));
+  HIP_OK(hipMalloc((void **)&e->states, sizeof(WState) * (size_t)batch));
   hipLaunchKernelGGL(walk_init_states, dim3(batch), dim3(64), 0, 0, e->states, e->model_dev, batch);
-  HIPW_OK(hipGetLastError());
-  HIPW_OK(hipDeviceSynchronize());
-  return e.release();
-}
-void walk_destroy(WalkEnv *e) {
-  if (!e) return;
-  if (e->model_dev) (void)hipFree(e->model_dev);
-  if (e->states) (void)hipFree(e->states);
-  delete e;
-}
-void walk_spec(const WalkEnv *e, int *nq, int *nv, int *nu, int *action_dim, int *obs_dim, int *nsub, double *h, double *ctrl_dt) {
-  *nq = e->host.nq; *nv = e->host.nv; *nu = NU; *action_dim = NACT; *obs_dim = 0; *nsub = e->host.m.b.nsub; *h = e->host.m.b.h;
-  *ctrl_dt = (double)e->host.m.b.nsub * (double)e->host.m.b.h;
-}
-void walk_action_bounds(const WalkEnv *e, float *mn, float *mx) {
-  for (int k = 0; k < NACT; k++) { mn[k] = e->host.action_min[k]; mx[k] = e->host.action_max[k]; }
-}
-void walk_physics(WalkEnv *e, const float *ctrl, int nphys, void *stream) {
-  if (!ctrl || nphys <= 0) throw std::runtime_error("walk physics: null control buffer or no steps");
-  hipLaunchKernelGGL(walk_step_kernel, dim3(e->batch), dim3(64), 0, (hipStream_t)stream, e->model_dev, e->flags, e->states, ctrl, e->batch, nphys);
-  HIPW_OK(hipGetLastError());
-}
-void walk_get_state(WalkEnv *e, double *qpos, double *qvel, void *stream) {
-  hipLaunchKernelGGL(walk_get_state_kernel, dim3(e->batch), dim3(128), 0, (hipStream_t)stream, e->states, qpos, qvel, e->batch);
-  HIPW_OK(hipGetLastError());
-}
-void walk_set_state(WalkEnv *e, const double *qpos, const double *qvel, void *stream) {
-  hipLaunchKernelGGL(walk_set_state_kernel, dim3(e->batch), dim3(128), 0, (hipStream_t)stream, e->states, qpos, qvel, e->batch);
-  HIPW_OK(hipGetLastError());
-}
-void walk_get_act(WalkEnv *e, double *act, void *stream) {
-  hipLaunchKernelGGL(walk_act_kernel, dim3(e->batch), dim3(64), 0, (hipStream_t)stream, e->states, act, e->batch, 0);
-  HIPW_OK(hipGetLastError());
-}
-void walk_set_act(WalkEnv *e, const double *act, void *stream) {
-  hipLaunchKernelGGL(walk_act_kernel, dim3(e->batch), dim3(64), 0, (hipStream_t)stream, e->states, const_cast<double *>(act), e->batch, 1);
-  HIPW_OK(hipGetLastError());
-}
-void walk_get_task_state(WalkEnv *e, int32_t *ints, double *reals, void *stream) {
-  HIPW_OK(hipMemsetAsync(ints, 0, sizeof(int32_t) * 8 * (size_t)e->batch, (hipStream_t)stream));
-  HIPW_OK(hipMemsetAsync(reals, 0, sizeof(double) * 8 * (size_t)e->batch, (hipStream_t)stream));
-}
-void walk_get_validity(WalkEnv *e, int32_t *info, void *stream) {
-  HIPW_OK(hipMemsetAsync(info, 0, sizeof(int32_t) * 4 * (size_t)e->batch, (hipStream_t)stream));
+  HIP_OK(hipGetLastError());
+  HIP_OK(hipDeviceSynchronize());
+  return e;
 }
 
 }  // namespace ffw

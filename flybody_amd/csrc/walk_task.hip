@@ -7,6 +7,7 @@
 #include <memory>
 #include <string>
 
+#include "env_backend.hpp"
 #include "walk_task.hpp"
 
 namespace wt {
@@ -65,11 +66,6 @@ struct ffe_walktask {
 static thread_local std::string g_werr;
 
 namespace {
-struct DeviceScope {
-  int prev = -1, dev;
-  explicit DeviceScope(int d) : dev(d) { (void)hipGetDevice(&prev); if (prev != dev) (void)hipSetDevice(dev); }
-  ~DeviceScope() { if (prev >= 0 && prev != dev) (void)hipSetDevice(prev); }
-};
 int launched(ffe_walktask *h, const char *who) {
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) { h->err = std::string(who) + ": " + hipGetErrorString(e); return -2; }
@@ -95,7 +91,7 @@ int ffe_walktask_create(const void *model_blob, size_t blob_size, const ffe_walk
                 std::to_string(wt::kMaxBody) + " and " + std::to_string(wt::kMaxJnt));
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || device < 0 || device >= ndev) return fail("no such HIP device: the MI355X path has no CPU fallback");
-  DeviceScope scope(device);
+  ffe::DeviceGuard guard(device);
   const std::vector<unsigned char> &arena = p->f64 ? p->pd.arena : p->pf.arena;
   if (hipMalloc(&p->arena, arena.size()) != hipSuccess) return fail("out of device memory");
   if (hipMemcpy(p->arena, arena.data(), arena.size(), hipMemcpyHostToDevice) != hipSuccess || hipDeviceSynchronize() != hipSuccess) {
@@ -113,7 +109,7 @@ int ffe_walktask_features(ffe_walktask_handle h, const double *qpos_dev, const d
   if (!qpos_dev || (qvel_out_dev && !qvel_dev)) { h->err = "ffe_walktask_features: a null required pointer (qpos_dev; qvel_dev when qvel_out_dev is given)"; return -1; }
   if (n < 0) { h->err = "ffe_walktask_features: n " + std::to_string(n) + " is negative"; return -1; }
   if (n == 0) return 0;
-  DeviceScope scope(h->device);
+  ffe::DeviceGuard guard(h->device);
   hipStream_t s = static_cast<hipStream_t>(stream);
   if (h->f64)
     hipLaunchKernelGGL(wt::walk_features_kernel<double>, dim3(n), dim3(64), 0, s, h->td, qpos_dev, qvel_dev, com_dev, (double *)qvel_out_dev,
@@ -136,7 +132,7 @@ int ffe_walktask_evaluate(ffe_walktask_handle h, const double *qpos_dev, const d
     return -1;
   }
   if (n == 0) return 0;
-  DeviceScope scope(h->device);
+  ffe::DeviceGuard guard(h->device);
   hipStream_t s = static_cast<hipStream_t>(stream);
   if (h->f64)
     hipLaunchKernelGGL(wt::walk_evaluate_kernel<double>, dim3(n), dim3(64), 0, s, h->td, qpos_dev, qvel_dev, clip_dev, step_dev, (double *)factors_dev,
@@ -154,7 +150,7 @@ int ffe_walktask_reference_pose(ffe_walktask_handle h, const int32_t *clip_dev, 
   if (!clip_dev || !step_dev) { h->err = "ffe_walktask_reference_pose: a null required pointer (clip_dev, step_dev)"; return -1; }
   if (n < 0) { h->err = "ffe_walktask_reference_pose: n " + std::to_string(n) + " is negative"; return -1; }
   if (n == 0) return 0;
-  DeviceScope scope(h->device);
+  ffe::DeviceGuard guard(h->device);
   hipStream_t s = static_cast<hipStream_t>(stream);
   if (h->f64)
     hipLaunchKernelGGL(wt::walk_reference_pose_kernel<double>, dim3(n), dim3(64), 0, s, h->td, clip_dev, step_dev, qpos_dev, qvel_dev);
@@ -180,7 +176,7 @@ int ffe_walktask_info(ffe_walktask_handle h, int32_t *dims, int32_t *episode_ste
 int ffe_walktask_destroy(ffe_walktask_handle h) {
   if (!h) { g_werr = "ffe_walktask_destroy: null handle"; return -1; }
   {
-    DeviceScope scope(h->device);
+    ffe::DeviceGuard guard(h->device);
     (void)hipFree(h->arena);
   }
   delete h;

@@ -13,6 +13,21 @@
  *   - one handle per (device, stream); handles are not thread-safe; every entry point runs on the handle's device
  *     whatever the caller's current device is, and leaves the caller's current device as it found it;
  *   - layouts are row-major with the env index leading: act[B][A], obs[B][O].
+ *
+ * Return codes of the env-handle calls (csrc/capi.hip maps them in one place; tests/test_gpu_capi_contract.py pins them)
+ *    0  done (asynchronously on `stream`).
+ *   -1  refused, nothing was launched: a NULL handle (the only case without a text: there is no handle to keep one), a NULL or
+ *       otherwise bad argument ("ffe_get_state: null buffer", "null device buffer" from a flight step,
+ *       "null reset mask", an `info_dev` that is not 16-byte aligned, a trajectory index out of range), every failure of a create
+ *       function (text in ffe_last_error(NULL), *out = NULL), or a call this kind of handle does not have:
+ *         flight        ffe_get_act, ffe_set_act
+ *         walk_on_ball  ffe_force_next_episode ("no per-episode randomness")
+ *         walk physics  ffe_reset, ffe_reset_envs, ffe_step, ffe_force_next_episode, ffe_time_steps, ffe_time_kernel
+ *                       ("... not available on a walk physics handle"); ffe_get_task_state / ffe_get_validity zero-fill.
+ *   -2  a HIP call failed (text: the call and hipGetErrorString).  For historical reasons also walk_on_ball's NULL-buffer
+ *       checks of ffe_step / ffe_reset ("walk_on_ball: null output buffer" / "null action buffer").
+ *   Since the calls moved into csrc/capi.hip every -1 / -2 on a non-NULL handle sets ffe_last_error(h) (NULL-argument -1s and some
+ *   -2 paths used to leave it stale), and a HIP failure inside a flight handle's ffe_force_next_episode is -2 (it was -1).
  */
 #ifndef FLYBODY_ENV_H_
 #define FLYBODY_ENV_H_

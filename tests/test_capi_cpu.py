@@ -83,3 +83,43 @@ def test_hdf5_converter_keeps_individual_lengths(tmp_path):
     rq, rv = T.preprocess(qs[1][None], vs[1][None])
     assert np.array_equal(refs.trajectory(1)[0], rq[0]) and np.array_equal(refs.trajectory(1)[1], rv[0])
     assert np.abs(T.root2com(refs.trajectory(2)[0])[0, :2]).max() < 1e-12
+
+
+def test_env_entry_points_live_in_capi_hip():
+    """Every declared `ffe_*` function is defined in exactly one file of csrc/, the env-handle ones in capi.hip."""
+    from flybody_amd import build
+
+    csrc = os.path.join(ROOT, "flybody_amd", "csrc")
+    hdr = open(os.path.join(ROOT, "include", "flybody_env.h")).read()
+    declared = set(re.findall(r"\b(ffe_[a-z_]+)\s*\(", hdr))
+    defined = {}
+    for f in sorted(os.listdir(csrc)):
+        if f.endswith((".hip", ".hpp", ".inc")):
+            txt = open(os.path.join(csrc, f)).read()
+            # a definition: return type at the start of a line, the name, a parameter list, an opening brace
+            for name in re.findall(r"^(?:const char \*|int )(ffe_[a-z_]+)\s*\([^;{]*\)\s*\{", txt, re.M):
+                defined.setdefault(name, []).append(f)
+    assert set(defined) >= declared, declared - set(defined)
+    assert all(len(defined[n]) == 1 for n in declared), {n: defined[n] for n in declared if len(defined[n]) != 1}
+    other = ("ffe_nstep_", "ffe_sampler_", "ffe_eplog_", "ffe_walktask_")
+    alone = {"ffe_pack_timestep", "ffe_episode_stats", "ffe_validity_stats", "ffe_test_quat"}
+    env_calls = {n for n in declared if not n.startswith(other) and n not in alone}
+    assert len(env_calls) == 21 and {"ffe_create_flight", "ffe_step", "ffe_time_kernel", "ffe_destroy", "ffe_last_error"} <= env_calls
+    assert {n: defined[n] for n in env_calls} == {n: ["capi.hip"] for n in env_calls}
+    assert all(defined[n] != ["capi.hip"] for n in declared - env_calls)
+    assert "capi.hip" in build.SOURCES and {"env_backend.hpp", "fly_env.hpp", "ball_env.hpp", "walk_env.hpp"} <= set(build.HEADERS)
+
+
+def test_python_handles_share_one_base():
+    import inspect
+
+    from flybody_amd.batched_env import BatchedBallEnv, BatchedFlyEnv, BatchedWalkPhysics, EnvHandle
+
+    assert inspect.getmro(BatchedFlyEnv)[1] is EnvHandle and inspect.getmro(BatchedWalkPhysics)[1] is EnvHandle
+    assert inspect.getmro(BatchedBallEnv)[1] is BatchedFlyEnv
+    for name in ("_check", "_stream", "close", "__del__", "raw_action_bounds", "get_state", "set_state", "physics_step", "get_task_state",
+                 "get_act", "set_act"):
+        owners = [c for c in (EnvHandle, BatchedFlyEnv, BatchedBallEnv, BatchedWalkPhysics) if name in vars(c)]
+        assert owners == [EnvHandle], (name, owners)
+        assert getattr(BatchedWalkPhysics, name) is getattr(BatchedFlyEnv, name) is getattr(BatchedBallEnv, name)
+    assert (BatchedFlyEnv.task_kind, BatchedBallEnv.task_kind, BatchedWalkPhysics.task_kind) == ("flight_imitation", "walk_on_ball", "walk_physics")

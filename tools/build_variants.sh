@@ -12,8 +12,10 @@ variant() {  # name, extra macro flags
   local T=$(mktemp -d)
   /opt/rocm/bin/hipcc $FLAGS -mllvm -disable-machine-licm "$@" -c $C/fly_env.hip -o $T/fly.o
   /opt/rocm/bin/hipcc $FLAGS -mllvm -sink-insts-to-avoid-spills=1 "$@" -c $C/ball_env.hip -o $T/ball.o
+  /opt/rocm/bin/hipcc $FLAGS -mllvm -sink-insts-to-avoid-spills=1 "$@" -c $C/walk_env.hip -o $T/walk.o
+  /opt/rocm/bin/hipcc $FLAGS "$@" -c $C/capi.hip -o $T/capi.o
   /opt/rocm/bin/hipcc $FLAGS "$@" -c $C/nstep.hip -o $T/nstep.o
-  /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o $C/variants/libflybody_env_$name.so $T/fly.o $T/ball.o $T/nstep.o
+  /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o $C/variants/libflybody_env_$name.so $T/capi.o $T/fly.o $T/ball.o $T/walk.o $T/nstep.o
   rm -rf $T
 }
 variant stamps -DFFE_STAMPS
