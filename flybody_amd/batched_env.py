@@ -24,6 +24,7 @@ FLIGHT_BLOB = os.path.join(_ASSETS, "fly_flight.ffmb")
 BALL_BLOB = os.path.join(_ASSETS, "fly_ball.ffmb")
 WALK_BLOB = os.path.join(_ASSETS, "fly_walk.ffmb")
 FFE_NO_LIMIT, FFE_NO_CONTACT = 2, 64  # include/flybody_env.h
+FFE_WALK_JOINT_LIMITS = 512  # ffe_create_walk_physics only: joint limits on (provisional opt-in, see the header)
 
 
 # `env.validity()`: four int32 [B] views of one [B, 4] device buffer (include/flybody_env.h, ffe_get_validity)
@@ -397,9 +398,15 @@ class BatchedBallEnv(BatchedFlyEnv):
 
 class BatchedWalkPhysics(EnvHandle):
     """B walking flies (`assets/fly_walk.ffmb`: free thorax, 6 + 102 dofs, 59 filtered actuators) advanced on one MI355X by
-    `ffe_physics_step` with constraints off: the smooth dynamics of `walk_imitation`.  Not an
-    environment: there is no reset, step, observation or reward - joint limits, floor contacts, sensors and the episode protocol are
-    not built yet, and `physics_flags` must contain FFE_NO_CONTACT | FFE_NO_LIMIT.  The handle starts at the model's `qpos0` at rest.
+    `ffe_physics_step`: the smooth dynamics of `walk_imitation` with constraints off or, with
+    `joint_limits=True`, with the joint limits of the 102 hinges on (step 3a).  Not an environment: there is no reset, step, observation
+    or reward - floor contacts, sensors and the episode protocol are not built yet.  The handle starts at the model's `qpos0` at rest.
+
+    `physics_flags` must contain FFE_NO_CONTACT and exactly one of FFE_NO_LIMIT (the default) or FFE_WALK_JOINT_LIMITS;
+    `joint_limits=True` sets FFE_NO_CONTACT | FFE_WALK_JOINT_LIMITS plus whatever force switches (FFE_NO_FLUID, ...) `physics_flags`
+    carries.  A limits handle carries up to 48 limit rows per env and substep; beyond that the rows that did not fit are dropped for the
+    substep and `validity()`'s step_bits (and int 7 of `get_task_state()`) carry bit value 2.  `get_task_state()` ints 4 and 6 are the
+    limit rows and the solver iterations of the last substep.
 
     Tensor conventions are `BatchedBallEnv`'s: `get_state` returns float64 cuda tensors qpos[B, 109] = root position (float64 on the
     device too), root quaternion, 102 hinges and qvel[B, 108] = root linear velocity (world frame), root angular velocity (body
@@ -407,7 +414,10 @@ class BatchedWalkPhysics(EnvHandle):
 
     task_kind = "walk_physics"
 
-    def __init__(self, *, batch_size: int, device: int = 0, physics_flags: int = FFE_NO_CONTACT | FFE_NO_LIMIT, blob_path: str = WALK_BLOB):
+    def __init__(self, *, batch_size: int, device: int = 0, physics_flags: int = FFE_NO_CONTACT | FFE_NO_LIMIT, blob_path: str = WALK_BLOB,
+                 joint_limits: bool = False):
+        if joint_limits:
+            physics_flags = (int(physics_flags) & ~(FFE_NO_CONTACT | FFE_NO_LIMIT)) | FFE_NO_CONTACT | FFE_WALK_JOINT_LIMITS
         self._open(batch_size, device)
         with open(blob_path, "rb") as f:
             blob = f.read()

@@ -13,9 +13,20 @@
 // solution with it is the solution without it plus (0, R' g) on the root alone.  It is added there, in the world frame, after the
 // solve: free fall is exact, and no gravity torque about the root origin is rounded in float32 and divided by the small rotational
 // inertias of S (which cost 2e-3 rad/s^2 of root angular acceleration when gravity went through the solve).
-// Collision, contact and limit rows, the constraint solver, sensors, observation, reward and reset are not compiled into this
-// kernel: only bare physics (`ffe_physics_step`) exists, and a handle is only created with FFE_NO_CONTACT | FFE_NO_LIMIT.
-// Parity tests: tests/test_gpu_walk_physics.py.
+// Collision, contact rows, sensors, observation, reward and reset are not compiled in: only bare physics (`ffe_physics_step`) exists.
+// Two kernels share the code below.  `walk_step_kernel` is the smooth dynamics alone (a handle created with FFE_NO_CONTACT |
+// FFE_NO_LIMIT).  `walk_limits_kernel` (FFE_NO_CONTACT | FFE_WALK_JOINT_LIMITS) adds the joint-limit
+// rows and the constraint solve on the arrowhead matrix between the smooth forces and the Euler solve of stage 2:
+//   rows     mj_instantiateLimit with margin 0 (sign, D, aref per hinge slot), compacted by ballots in (slot, lane) order, at most RMAX;
+//   M^-1     through M's own factor (not M + h B): z_m = M_jj^-1 f_j, Y_m = M_jj^-1 M_jr, S_m = M_rr - M_rj Y_m = L L',
+//            x_r = S_m^-1 (b_r - M_rj z_m), a_s = z_m - Y_m x_r on the hinges;
+//   G        G_ik = s_i s_k [(M_jj^-1)_{f_i f_k} + (L^-1 Y_m[f_i]) . (L^-1 Y_m[f_k])]: the block part four columns per block solve, rows
+//            of different blocks sharing a column; the rank-6 part from each row lane's own 6-vector, the others' by v_readlane;
+//   solve    the dual Newton in row space of ball_env.hip, scalar rows only (`limits_newton`, out of line, a leaf);
+//   forces   qfrc_constraint = s f on the hinge right-hand side of the Euler solve; the root's is unchanged (J_r = 0): the root
+//            feels a limit through M_rj alone.
+// A substep that instantiates no row skips all of it by a wave-uniform branch.
+// Parity tests: tests/test_gpu_walk_physics.py, tests/test_gpu_walk_limits.py.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -38,8 +49,15 @@ struct alignas(16) WState {
   float quat[4];
   float vlin[3], wb[3];
   float q[NDP], v[NDP], act[64];
-  int pad[2];
+  // limits handle only (zero otherwise): limit rows and solver iterations of the last substep, overflow bits of the last launch
+  // (2: some substep instantiated more limits than RMAX rows; the rows beyond were dropped for that substep)
+  int nlim, iters, step_bits, pad;
 };
+static_assert(sizeof(WState) == 1168, "the four ints fill what used to be padding");
+
+constexpr int BF_WALK_JOINT_LIMITS = 512;  // FFE_WALK_JOINT_LIMITS: host side only, the kernels do not read it
+constexpr int LCOL = 16;                   // solve columns per block of M: a block has at most NSTEP = 14 hinges, each with one limit row
+static_assert(NSTEP <= LCOL, "a block's limit rows must fit its columns");
 
 struct alignas(16) WTile {
   union {
@@ -60,10 +78,35 @@ struct alignas(16) WTile {
 };
 static_assert(sizeof(WTile) <= 20480, "the tile must leave room for 8 waves per CU");
 
-struct Ctx {
+// Tile of the limits kernel: WTile without Y (a row lane reads its hinge's Y_m straight from the solve), with the packed G over the
+// two arrays that are dead once stage 1 has factorised (G dies with the substep), and the row tables.
+struct alignas(16) WTileL {
+  union {
+    struct { float Q[NDP], V[NDP]; };
+    float4 X4[NDP];
+  };
+  union {
+    struct { float dadd[NDP]; float Mq[NMMAX]; };
+    float G[RMAX * (RMAX + 1) / 2];     // G = J M^-1 J' over the limit rows, lower triangle packed by rows (lane r owns row r); the
+  };                                    // Newton transposes its factor through the same floats once G sits in registers
+  union {
+    float F[NDP][6];
+    float lk[NL][12];
+  };
+  float Lm[NMMAX], Lh[NMMAX];
+  float dinv_m[NDP], dinv_h[NDP];
+  float C[NDP][6];
+  float frc[64];
+  float r_y0[RMAX], r_D[RMAX], r_f[RMAX], r_sgn[RMAX];
+  unsigned char r_dof[RMAX], r_blk[RMAX], r_col[RMAX], rowof[NBLK][LCOL];
+};
+static_assert(sizeof(WTileL) <= 20480, "the tile must leave room for 8 waves per CU");
+
+template <class Tile>
+struct CtxT {
   const BallModel *M;
   const WalkExtra FFE_GLOBAL *X;
-  WTile *T;
+  Tile *T;
   int lane, flags;
   unsigned lpack;
   int sdof[3];
@@ -80,13 +123,14 @@ struct Ctx {
   S6 V0;        // (w_b, R' v_w)
   I10 Itree;    // spatial inertia of the whole tree about the root origin = M_rr
   S6 Ftot;      // bias force of the whole tree without gravity = -(root rows of the smooth force)
+  int overflow; // limits kernel: overflow bits of this launch
 };
 
 // ------------------------------------------------------------------------------------------------ stage 1
 template <class C>  // (a template so that the fragment's tethered branches are discarded, not compiled)
 __device__ __forceinline__ void stage1(C &c) {
   constexpr bool FREE_ROOT = true;
-  WTile &T = *c.T;
+  auto &T = *c.T;
   const BallModel FFE_GLOBAL &M = model(c);
   {
     const M3 R = q2m(c.rq);
@@ -110,10 +154,334 @@ __device__ __forceinline__ void stage1(C &c) {
   }
 }
 
-// ------------------------------------------------------------------------------------------------ stage 2
+// ------------------------------------------------------------------------------------------------ 6 x 6 root system
+__device__ __forceinline__ float comp(const S6 &v, int k) { return k == 0 ? v.a0 : (k == 1 ? v.a1 : (k == 2 ? v.a2 : (k == 3 ? v.l0 : (k == 4 ? v.l1 : v.l2)))); }
+
+// Schur complement S = M_rr - M_rj Y (lower triangle) and right-hand side b_r = f_r - M_rj z: wave sums of the lanes' own hinges
 template <class C>
-__device__ __forceinline__ void stage2(C &c, float act_reg, float ctrl_reg, float &act_out) {
-  WTile &T = *c.T;
+__device__ __forceinline__ void schur(const C &c, const S6 (&mrj)[3], const S6 (&y)[3], const float (&z)[3], float (&Sm)[6][6], float (&br)[6]) {
+  // M_rr from the tree's spatial inertia: column k = I e_k
+#pragma unroll
+  for (int k = 0; k < 6; k++) {
+    const S6 e = {k == 0 ? 1.f : 0.f, k == 1 ? 1.f : 0.f, k == 2 ? 1.f : 0.f, k == 3 ? 1.f : 0.f, k == 4 ? 1.f : 0.f, k == 5 ? 1.f : 0.f};
+    const S6 col = mul_inert(c.Itree, e);
+#pragma unroll
+    for (int r = 0; r < 6; r++) Sm[r][k] = comp(col, r);
+  }
+#pragma unroll
+  for (int a = 0; a < 6; a++) {
+#pragma unroll
+    for (int b = 0; b <= a; b++) {
+      float p = 0.f;
+#pragma unroll
+      for (int s = 0; s < 3; s++) p += comp(mrj[s], a) * comp(y[s], b);
+      Sm[a][b] -= wave_sum(p);
+    }
+    float p = 0.f;
+#pragma unroll
+    for (int s = 0; s < 3; s++) p += comp(mrj[s], a) * z[s];
+    br[a] = -comp(c.Ftot, a) - wave_sum(p);
+  }
+}
+
+// S = L L' in place (lower triangle, in registers, uniform); id = 1 / diag(L)
+__device__ __forceinline__ void chol6(float (&Sm)[6][6], float (&id)[6]) {
+#pragma unroll
+  for (int j = 0; j < 6; j++) {
+    float d = Sm[j][j];
+#pragma unroll
+    for (int k = 0; k < j; k++) d -= Sm[j][k] * Sm[j][k];
+    const float r = __builtin_amdgcn_rsqf(d);
+    const float ir = r * (1.5f - 0.5f * d * r * r);  // 1 / sqrt(d), one Newton step
+    id[j] = ir;
+    Sm[j][j] = d * ir;
+#pragma unroll
+    for (int i = j + 1; i < 6; i++) {
+      float e = Sm[i][j];
+#pragma unroll
+      for (int k = 0; k < j; k++) e -= Sm[i][k] * Sm[j][k];
+      Sm[i][j] = e * ir;
+    }
+  }
+}
+__device__ __forceinline__ void chol6_forward(const float (&Sm)[6][6], const float (&id)[6], const float (&b)[6], float (&x)[6]) {  // L x = b
+#pragma unroll
+  for (int i = 0; i < 6; i++) {
+    float w = b[i];
+#pragma unroll
+    for (int k = 0; k < i; k++) w -= Sm[i][k] * x[k];
+    x[i] = w * id[i];
+  }
+}
+__device__ __forceinline__ void chol6_backward(const float (&Sm)[6][6], const float (&id)[6], float (&x)[6]) {  // L' x = w, in place
+#pragma unroll
+  for (int i = 5; i >= 0; i--) {
+    float w = x[i];
+#pragma unroll
+    for (int k = i + 1; k < 6; k++) w -= Sm[k][i] * x[k];
+    x[i] = w * id[i];
+  }
+}
+
+// ------------------------------------------------------------------------------------------------ joint-limit rows
+// mj: getimpedance with margin 0 (x = |dist|), as ball_env.hip
+__device__ __forceinline__ float impedance(const float *si, float x) {
+  float d0 = fminf(fmaxf(si[0], 1e-4f), 0.9999f), d1 = fminf(fmaxf(si[1], 1e-4f), 0.9999f);
+  const float width = fmaxf(0.f, si[2]), mid = fminf(fmaxf(si[3], 1e-4f), 0.9999f), power = fmaxf(1.f, si[4]);
+  if (d0 == d1 || width <= 1e-15f) return 0.5f * (d0 + d1);
+  x = x * frcp(width);
+  if (x >= 1.f) return d1;
+  if (x <= 0.f) return d0;
+  float y;
+  if (power == 1.f) y = x;
+  else if (power == 2.f) y = x <= mid ? x * x * frcp(mid) : 1.f - (1.f - x) * (1.f - x) * frcp(1.f - mid);
+  else if (x <= mid) y = powf(x, power) / powf(mid, power - 1.f);
+  else y = 1.f - powf(1.f - x, power) / powf(1.f - mid, power - 1.f);
+  return d0 + y * (d1 - d0);
+}
+
+constexpr int kMaxNewton = 20;
+constexpr float kNewtonTol2 = 1e-8f;  // stop when |grad| <= 1e-4 |force scale| in the M^-1 metric (ball_env.hip's figure)
+constexpr int kLsIter = 10;
+constexpr float kLsTol = 1e-2f;       // |phi'(alpha)| <= tol |phi'(0)|: an inexact line search, the Newton loop converges the rest
+
+// mj: mj_fwdConstraint in the space of the limit rows: the dense Newton of ball_env.hip (see the comment block of its stage 2)
+// specialised to scalar rows.  With y = y0 + G lambda the force law is f(y) = -D min(0, y) per row; the Newton step is
+// d = -(I + W G)^-1 (lambda - f), W = diag(D on the rows with y < 0), solved as d = -e + L u, (I + L G L) u = L G e, L = sqrt(W),
+// followed by an exact line search on the convex piecewise-quadratic cost.  Lane = row, R <= RB rows: the lane's row of G and of
+// S = I + L G L in registers, the other lanes' scalars by v_readlane.  Starts from lambda = 0 (no warm start: a limit row comes and
+// goes with its hinge).  Reads T.G, T.r_y0, T.r_D; leaves the forces in T.r_f.  A real call and a leaf: the loop then has the whole
+// register file to itself.
+template <int RB>
+__device__ __noinline__ int limits_newton(WTileL *Tp, const int lane, const int R, const float scale2) {
+  WTileL &T = *Tp;
+  int iters = 0;
+  f2 Gp[RB / 2], Sp[RB / 2];
+  auto G_ = [&](int j) -> float { return (j & 1) ? Gp[j >> 1].y : Gp[j >> 1].x; };
+  auto S_ = [&](int j) -> float { return (j & 1) ? Sp[j >> 1].y : Sp[j >> 1].x; };
+  auto setS = [&](int j, float v) { if (j & 1) Sp[j >> 1].y = v; else Sp[j >> 1].x = v; };
+  auto gload = [&](int j) -> float { return (lane < R && j < R) ? T.G[j <= lane ? lane * (lane + 1) / 2 + j : j * (j + 1) / 2 + lane] : 0.f; };
+#pragma unroll
+  for (int m = 0; m < RB / 2; m++) Gp[m] = f2{gload(2 * m), gload(2 * m + 1)};
+  const float y0v = lane < R ? T.r_y0[lane] : 0.f;
+  const float D = lane < R ? T.r_D[lane] : 0.f;
+  DM_SYNC();  // G sits in registers: its floats carry the factor's transpose from here on
+  auto gdot = [&](float vreg) {  // (G v)[lane], v given as one value per lane
+    f2 acc = f2{0.f, 0.f};
+#pragma unroll
+    for (int m = 0; m < RB / 2; m++) acc = __builtin_elementwise_fma(Gp[m], f2{rl_f(vreg, 2 * m), rl_f(vreg, 2 * m + 1)}, acc);  // G = 0 beyond the R live rows
+    return acc.x + acc.y;
+  };
+  auto eval = [&](float y) { return y < 0.f ? -D * y : 0.f; };
+  float lam = 0.f, yv = y0v, fv = 0.f;
+  bool fresh = false;  // fv belongs to the current yv
+#pragma unroll 1
+  for (int it = 0; it < kMaxNewton; it++) {
+    fresh = true;
+    fv = eval(yv);
+    const float Ld = (yv < 0.f && D > 0.f) ? fsqrt(D) : 0.f;
+    const float ev = lam - fv;
+    const float pv = gdot(ev);
+    const float gn2 = wave_sum(pv * ev);
+    if (gn2 <= kNewtonTol2 * scale2 + 1e-30f) break;
+    iters++;
+#pragma unroll
+    for (int j = 0; j < RB; j++) {
+      if (j < R) setS(j, (j == lane ? 1.f : 0.f) + Ld * G_(j) * rl_f(Ld, j));
+      else setS(j, j == lane ? 1.f : 0.f);
+    }
+    float w = Ld * pv;  // rhs = L p
+    // Cholesky of S (row per lane) as S = Lt D Lt', Lt unit lower triangular: S_(k) ends as Lt[lane][k] below the diagonal and 0 on
+    // and above it, so that the substitutions are one unconditional FMA per step; ipp = 1 / D[lane]
+    float ipp = 1.f;
+#pragma unroll
+    for (int k = 0; k < RB; k++) {
+      if (k < R) {
+        const float ip = __builtin_amdgcn_rsqf(rl_f(S_(k), k));
+        const float lik = S_(k) * ip;
+        if ((k & 1) == 0) Sp[k >> 1].y -= lik * rl_f(lik, k + 1);  // the pair partner of an even pivot column
+        const f2 nl = f2{-lik, -lik};
+#pragma unroll
+        for (int m = (k >> 1) + 1; m < RB / 2; m++)  // rows / columns beyond R are identity: no-ops
+          Sp[m] = __builtin_elementwise_fma(nl, f2{rl_f(lik, 2 * m), rl_f(lik, 2 * m + 1)}, Sp[m]);
+        setS(k, lane > k ? lik * ip : 0.f);
+        ipp = lane == k ? ip * ip : ipp;
+      }
+    }
+#pragma unroll
+    for (int k = 0; k < RB; k++)  // forward substitution Lt z = w
+      if (k < R) w -= S_(k) * rl_f(w, k);
+    w *= ipp;
+    // transpose through LDS (this lane's column of Lt; the strict lower triangle packed by rows, row i at i (i - 1) / 2), then the
+    // backward substitution Lt' u = D^-1 z
+    if (lane < R) {
+      const int tri = lane * (lane - 1) / 2;
+#pragma unroll
+      for (int j = 0; j < RB; j++) if (j < lane) T.G[tri + j] = S_(j);
+    }
+    DM_SYNC();
+#pragma unroll
+    for (int m = 0; m < RB / 2; m++) Sp[m] = f2{0.f, 0.f};
+    if (lane < R) {
+#pragma unroll
+      for (int k = 0; k < RB; k++) if (k < R && k > lane) setS(k, T.G[k * (k - 1) / 2 + lane]);
+    }
+    DM_SYNC();
+#pragma unroll
+    for (int k = RB - 1; k >= 0; k--)
+      if (k < R) w -= S_(k) * rl_f(w, k);
+    const float dl = lane < R ? -ev + Ld * w : 0.f;  // d = -e + L u
+    const float jdv = gdot(dl);
+    const float c1s = wave_sum(dl * jdv);
+    const float d0 = wave_sum(ev * jdv);  // phi'(0) = (lambda - f(y)) . G d
+    // exact line search on the convex phi(alpha): root of phi'(alpha) = phi'(0) + alpha c1 - sum_rows (f(y + alpha jd) - f(y)) jd
+    auto dphi = [&](float al) { return d0 + al * c1s + wave_sum((fv - eval(yv + al * jdv)) * jdv); };
+    float alpha = 0.f;
+    {
+      if (!(d0 < 0.f)) break;  // not a descent direction any more: converged to rounding
+      float lo = 0.f, hi = 1.f, dlo = d0, dhi = dphi(1.f);
+      int guard = 0;
+      while (dhi < 0.f && fabsf(dhi) > kLsTol * fabsf(d0) && guard++ < 8) { lo = hi; dlo = dhi; hi *= 2.f; dhi = dphi(hi); }
+      if (dhi < 0.f || fabsf(dhi) <= kLsTol * fabsf(d0)) alpha = hi;  // full (or doubled) Newton step: |phi'| already small
+      else {
+#pragma unroll 1
+        for (int ls = 0; ls < kLsIter; ls++) {
+          float mid = lo - dlo * (hi - lo) / (dhi - dlo);
+          if (!(mid > lo + 0.05f * (hi - lo)) || !(mid < hi - 0.05f * (hi - lo))) mid = 0.5f * (lo + hi);
+          const float dm_ = dphi(mid);
+          if (dm_ < 0.f) { lo = mid; dlo = dm_; } else { hi = mid; dhi = dm_; }
+          if (fabsf(dm_) <= kLsTol * fabsf(d0) || hi - lo <= 1e-6f * hi) break;
+        }
+        alpha = (dhi - dlo) != 0.f ? lo - dlo * (hi - lo) / (dhi - dlo) : hi;
+        if (!(alpha >= lo) || !(alpha <= hi)) alpha = 0.5f * (lo + hi);
+      }
+    }
+    lam += alpha * dl;
+    yv += alpha * jdv;  // y = y0 + G lambda stays current without another product
+    fresh = false;
+  }
+  if (!fresh) fv = eval(yv);  // forces at the solution
+  if (lane < R) T.r_f[lane] = fv;
+  DM_SYNC();
+  return iters;
+}
+
+// The constraint block of a substep with R > 0 limit rows (rows already in T.r_sgn / r_D / r_dof / r_blk, -aref in T.r_y0): adds the
+// hinges' constraint forces to `qs`.  Returns the solver's iterations.
+template <class C>
+__device__ __forceinline__ int limit_forces(C &c, const int R, const int (&lrow)[3], const float (&lsgn)[3], const S6 (&mrj)[3], float (&qs)[3]) {
+  WTileL &T = *c.T;
+  const int lane = c.lane;
+  const bool row = lane < R;
+  // ---- z_m = M_jj^-1 f_j and Y_m = M_jj^-1 M_jr through M's own factor; a row lane keeps its hinge's Y_m
+  S6 ym[3], yr = zero6();
+  float zm[3];
+#pragma unroll
+  for (int s = 0; s < 3; s++) if (slot_on(c, s)) T.X4[opq(c.sdof[s])] = make_float4(qs[s], mrj[s].a0, mrj[s].a1, mrj[s].a2);
+  DM_SYNC();
+  solve4(c, T.Lm, T.dinv_m);
+#pragma unroll
+  for (int s = 0; s < 3; s++) {
+    const float4 x = slot_on(c, s) ? T.X4[opq(c.sdof[s])] : make_float4(0.f, 0.f, 0.f, 0.f);
+    zm[s] = x.x; ym[s].a0 = x.y; ym[s].a1 = x.z; ym[s].a2 = x.w;
+  }
+  const int rdof = row ? (int)T.r_dof[lane] : 0;
+  if (row) { const float4 x = T.X4[rdof]; yr.a0 = x.y; yr.a1 = x.z; yr.a2 = x.w; }
+  DM_SYNC();
+#pragma unroll
+  for (int s = 0; s < 3; s++) if (slot_on(c, s)) T.X4[opq(c.sdof[s])] = make_float4(mrj[s].l0, mrj[s].l1, mrj[s].l2, 0.f);
+  DM_SYNC();
+  solve4(c, T.Lm, T.dinv_m);
+#pragma unroll
+  for (int s = 0; s < 3; s++) {
+    const float4 x = slot_on(c, s) ? T.X4[opq(c.sdof[s])] : make_float4(0.f, 0.f, 0.f, 0.f);
+    ym[s].l0 = x.x; ym[s].l1 = x.y; ym[s].l2 = x.z;
+  }
+  if (row) { const float4 x = T.X4[rdof]; yr.l0 = x.x; yr.l1 = x.y; yr.l2 = x.z; }
+  DM_SYNC();
+  // ---- S_m = L L', x_r = S_m^-1 (b_r - M_rj z_m), the hinges' smooth acceleration a_s = z_m - Y_m x_r (gravity: zero on the hinges)
+  float Sm[6][6], br[6], id[6], xr[6];
+  schur(c, mrj, ym, zm, Sm, br);
+  chol6(Sm, id);
+  chol6_forward(Sm, id, br, xr);
+  chol6_backward(Sm, id, xr);
+  float sq = 0.f;
+#pragma unroll
+  for (int s = 0; s < 3; s++) {
+    if (slot_on(c, s)) {
+      float a = zm[s];
+#pragma unroll
+      for (int k = 0; k < 6; k++) a -= comp(ym[s], k) * xr[k];
+      T.X4[opq(c.sdof[s])].x = a;
+      sq += qs[s] * a;
+    }
+  }
+  float scale2 = wave_sum(sq);  // qfrc_smooth . qacc_smooth: the scale of the solver's stopping test
+#pragma unroll
+  for (int k = 0; k < 6; k++) scale2 += br[k] * xr[k];
+  DM_SYNC();
+  const float sg = row ? T.r_sgn[lane] : 0.f;
+  if (row) T.r_y0[lane] += sg * T.X4[rdof].x;  // y0 = J a_s - aref
+  // ---- the rank-6 part of G: u_i = s_i L^-1 Y_m[f_i], G_ik = u_i . u_k
+  const int gtri = lane * (lane + 1) / 2;  // G is symmetric: row `lane` keeps its columns r2 <= lane
+  {
+    float yv[6], u[6];
+#pragma unroll
+    for (int k = 0; k < 6; k++) yv[k] = sg * comp(yr, k);
+    chol6_forward(Sm, id, yv, u);
+    for (int r2 = 0; r2 < R; r2++) {
+      float gv = 0.f;
+#pragma unroll
+      for (int k = 0; k < 6; k++) gv += u[k] * rl_f(u[k], r2);
+      if (row && r2 <= lane) T.G[gtri + r2] = gv;
+    }
+  }
+  // ---- columns: a row's column is its rank among the rows of its block (M_jj^-1 is block diagonal)
+  for (int k = lane; k < NBLK * LCOL; k += 64) (&T.rowof[0][0])[k] = 255;
+  const int myb = row ? (int)T.r_blk[lane] : -1;
+  int mycol = 0, ncol = 0;
+  for (int b = 0; b < NBLK; b++) {
+    const unsigned long long mb = __ballot(myb == b);
+    if (myb == b) mycol = __popcll(mb & ((1ull << lane) - 1ull));
+    ncol = max(ncol, (int)__popcll(mb));
+  }
+  DM_SYNC();
+  if (row) T.rowof[myb][mycol] = (unsigned char)lane;  // (mycol < NSTEP <= LCOL: one row per hinge)
+  DM_SYNC();
+#pragma unroll 1
+  for (int cb = 0; cb < ncol; cb += 4) {
+    for (int f = lane; f < ND; f += 64) T.X4[f] = make_float4(0.f, 0.f, 0.f, 0.f);
+    DM_SYNC();
+    if (row) { const int col = mycol - cb; if (col >= 0 && col < 4) (&T.X4[rdof].x)[col] = sg; }
+    DM_SYNC();
+    solve4(c, T.Lm, T.dinv_m);
+    if (row) {
+      const float4 y = T.X4[rdof];
+#pragma unroll
+      for (int q2 = 0; q2 < 4; q2++) {
+        const float av = sg * (q2 == 0 ? y.x : (q2 == 1 ? y.y : (q2 == 2 ? y.z : y.w)));
+        const int r2 = cb + q2 < LCOL ? (int)T.rowof[myb][cb + q2] : 255;
+        if (r2 <= lane) T.G[gtri + r2] += av;  // (255 = no such row)
+      }
+    }
+    DM_SYNC();
+  }
+  // ---- solve, then qfrc_constraint = s f on the hinges
+  int iters;
+  if (R <= 8) iters = limits_newton<8>(c.T, lane, R, scale2);
+  else if (R <= 16) iters = limits_newton<16>(c.T, lane, R, scale2);
+  else if (R <= 32) iters = limits_newton<32>(c.T, lane, R, scale2);
+  else iters = limits_newton<RMAX>(c.T, lane, R, scale2);
+#pragma unroll
+  for (int s = 0; s < 3; s++) if (lrow[s] >= 0) qs[s] += lsgn[s] * T.r_f[lrow[s]];
+  DM_SYNC();
+  return iters;
+}
+
+// ------------------------------------------------------------------------------------------------ stage 2
+template <bool LIMITS, class C>
+__device__ __forceinline__ void stage2(C &c, float act_reg, float ctrl_reg, float &act_out, int &nlim_out, int &iters_out) {
+  auto &T = *c.T;
   const BallModel FFE_GLOBAL &M = model(c);
   const int lane = c.lane;
   const float h = M.h;
@@ -159,6 +527,51 @@ __device__ __forceinline__ void stage2(C &c, float act_reg, float ctrl_reg, floa
 #pragma unroll
   for (int s = 0; s < 3; s++) mrj[s] = slot_on(c, s) ? ld6(T.F[opq(c.sdof[s])]) : zero6();
   DM_SYNC();  // (Q / V have been read: X4 lies over them)
+  if constexpr (LIMITS) {
+    // ---- joint-limit rows (mj: mj_instantiateLimit, margin 0): sign, D, aref per slot, exactly as ball_env.hip's stage 2; one row
+    //      per instantiated limit in (slot, lane) order; beyond RMAX the rows are dropped for this substep and the env is flagged
+    float lsgn[3];
+    int lrow[3] = {-1, -1, -1};
+    int R = 0;
+#pragma unroll
+    for (int s = 0; s < 3; s++) {
+      float lD = 0.f, laref = 0.f;
+      lsgn[s] = 0.f;
+      if (slot_on(c, s) && M.s_limited[s][lane]) {
+        const float dlo = c.q[s] - M.s_lo[s][lane], dhi = M.s_hi[s][lane] - c.q[s];
+        float dist = 0.f;
+        if (dlo < 0.f) { lsgn[s] = 1.f; dist = dlo; }
+        else if (dhi < 0.f) { lsgn[s] = -1.f; dist = dhi; }
+        if (lsgn[s] != 0.f) {
+          float si_[5];
+#pragma unroll
+          for (int q2 = 0; q2 < 5; q2++) si_[q2] = M.j_solimp[q2];
+          const float imp = impedance(si_, fabsf(dist));
+          lD = frcp(fmaxf(1e-15f, (1.f - imp) * M.s_invw[s][lane] * frcp(imp)));
+          laref = -M.s_B[s][lane] * (lsgn[s] * c.v[s]) - M.s_K[s][lane] * imp * dist;
+        }
+      }
+      const bool on = lsgn[s] != 0.f;
+      const unsigned long long bal = __ballot(on);
+      const int idx = R + __popcll(bal & ((1ull << lane) - 1ull));
+      if (on && idx < RMAX) {
+        lrow[s] = idx;
+        T.r_sgn[idx] = lsgn[s]; T.r_D[idx] = lD; T.r_y0[idx] = -laref;
+        T.r_dof[idx] = (unsigned char)c.sdof[s]; T.r_blk[idx] = (unsigned char)M.d_blk[c.sdof[s]];
+      }
+      R += __popcll(bal);
+    }
+    if (R > RMAX) { R = RMAX; c.overflow |= 2; }
+    nlim_out = R;
+    iters_out = 0;
+    if (R > 0) {  // wave-uniform: a substep without a row pays the ballots only
+      DM_SYNC();
+      iters_out = limit_forces(c, R, lrow, lsgn, mrj, qs);
+      // (read again rather than kept in registers across the solver's call: 18 fewer live values there)
+#pragma unroll
+      for (int s = 0; s < 3; s++) mrj[s] = slot_on(c, s) ? ld6(T.F[opq(c.sdof[s])]) : zero6();
+    }
+  }
 #pragma unroll
   for (int s = 0; s < 3; s++) if (slot_on(c, s)) T.X4[opq(c.sdof[s])] = make_float4(qs[s], mrj[s].a0, mrj[s].a1, mrj[s].a2);
   DM_SYNC();
@@ -179,71 +592,16 @@ __device__ __forceinline__ void stage2(C &c, float act_reg, float ctrl_reg, floa
     y[s].l0 = x.x; y[s].l1 = x.y; y[s].l2 = x.z;
   }
   DM_SYNC();
+  if constexpr (!LIMITS) {
 #pragma unroll
-  for (int s = 0; s < 3; s++) if (slot_on(c, s)) st6(T.Y[opq(c.sdof[s])], y[s]);  // kept for the constraint rows of step 3 (rank-6 term of G)
-  // ---- Schur complement S = M_rr - M_rj Y and right-hand side f_r - M_rj z: wave sums of the lanes' own hinges
-  auto comp = [](const S6 &v, int k) { return k == 0 ? v.a0 : (k == 1 ? v.a1 : (k == 2 ? v.a2 : (k == 3 ? v.l0 : (k == 4 ? v.l1 : v.l2)))); };
-  float Sm[6][6], br[6];
-  {
-    // M_rr from the tree's spatial inertia: column k = I e_k
-#pragma unroll
-    for (int k = 0; k < 6; k++) {
-      const S6 e = {k == 0 ? 1.f : 0.f, k == 1 ? 1.f : 0.f, k == 2 ? 1.f : 0.f, k == 3 ? 1.f : 0.f, k == 4 ? 1.f : 0.f, k == 5 ? 1.f : 0.f};
-      const S6 col = mul_inert(c.Itree, e);
-#pragma unroll
-      for (int r = 0; r < 6; r++) Sm[r][k] = comp(col, r);
-    }
-#pragma unroll
-    for (int a = 0; a < 6; a++) {
-#pragma unroll
-      for (int b = 0; b <= a; b++) {
-        float p = 0.f;
-#pragma unroll
-        for (int s = 0; s < 3; s++) p += comp(mrj[s], a) * comp(y[s], b);
-        Sm[a][b] -= wave_sum(p);
-      }
-      float p = 0.f;
-#pragma unroll
-      for (int s = 0; s < 3; s++) p += comp(mrj[s], a) * z[s];
-      br[a] = -comp(c.Ftot, a) - wave_sum(p);
-    }
+    for (int s = 0; s < 3; s++) if (slot_on(c, s)) st6(T.Y[opq(c.sdof[s])], y[s]);  // (the limits kernel reads its rows' Y_m from the solve instead)
   }
-  // ---- 6 x 6 Cholesky S = L L' (lower triangle, in registers, uniform), x_r = S^-1 b_r
-  float xr[6];
-  {
-    float id[6];
-#pragma unroll
-    for (int j = 0; j < 6; j++) {
-      float d = Sm[j][j];
-#pragma unroll
-      for (int k = 0; k < j; k++) d -= Sm[j][k] * Sm[j][k];
-      const float r = __builtin_amdgcn_rsqf(d);
-      const float ir = r * (1.5f - 0.5f * d * r * r);  // 1 / sqrt(d), one Newton step
-      id[j] = ir;
-      Sm[j][j] = d * ir;
-#pragma unroll
-      for (int i = j + 1; i < 6; i++) {
-        float e = Sm[i][j];
-#pragma unroll
-        for (int k = 0; k < j; k++) e -= Sm[i][k] * Sm[j][k];
-        Sm[i][j] = e * ir;
-      }
-    }
-#pragma unroll
-    for (int i = 0; i < 6; i++) {  // L w = b
-      float w = br[i];
-#pragma unroll
-      for (int k = 0; k < i; k++) w -= Sm[i][k] * xr[k];
-      xr[i] = w * id[i];
-    }
-#pragma unroll
-    for (int i = 5; i >= 0; i--) {  // L' x = w
-      float w = xr[i];
-#pragma unroll
-      for (int k = i + 1; k < 6; k++) w -= Sm[k][i] * xr[k];
-      xr[i] = w * id[i];
-    }
-  }
+  // ---- Schur complement S = M_rr - M_rj Y and right-hand side f_r - M_rj z; 6 x 6 Cholesky S = L L', x_r = S^-1 b_r
+  float Sm[6][6], br[6], id[6], xr[6];
+  schur(c, mrj, y, z, Sm, br);
+  chol6(Sm, id);
+  chol6_forward(Sm, id, br, xr);
+  chol6_backward(Sm, id, xr);
   // ---- back substitution of the hinges, integration (mj: mj_Euler, implicit in the joint damping)
 #pragma unroll
   for (int s = 0; s < 3; s++) {
@@ -271,16 +629,15 @@ __device__ __forceinline__ void stage2(C &c, float act_reg, float ctrl_reg, floa
   }
 }
 
-// ------------------------------------------------------------------------------------------------ kernel
-__global__ __launch_bounds__(64, 2) void walk_step_kernel(const WalkModel *__restrict__ Wp, int flags, WState *__restrict__ states,
-                                                         const float *__restrict__ ctrl, int batch, int nphys) {
+// ------------------------------------------------------------------------------------------------ kernels
+template <bool LIMITS, class Tile>
+__device__ __forceinline__ void walk_substeps(Tile &T, const WalkModel *__restrict__ Wp, int flags, WState *__restrict__ states,
+                                              const float *__restrict__ ctrl, int nphys) {
   const int env = blockIdx.x, lane = threadIdx.x;
-  if (env >= batch) return;
-  __shared__ WTile T;
   const BallModel &M = Wp->b;
   WState &S = states[env];
-  Ctx c;
-  c.M = &Wp->b; c.X = (const WalkExtra FFE_GLOBAL *)&Wp->x; c.T = &T; c.lane = lane; c.flags = flags;
+  CtxT<Tile> c;
+  c.M = &Wp->b; c.X = (const WalkExtra FFE_GLOBAL *)&Wp->x; c.T = &T; c.lane = lane; c.flags = flags; c.overflow = 0;
   c.lpack = M.l_pack[lane]; c.xh = M.x_on[lane];
 #pragma unroll
   for (int s = 0; s < 3; s++) c.sdof[s] = M.s_dof[s][lane];
@@ -291,11 +648,12 @@ __global__ __launch_bounds__(64, 2) void walk_step_kernel(const WalkModel *__res
   c.pos[0] = S.pos[0]; c.pos[1] = S.pos[1]; c.pos[2] = S.pos[2];
   float act_reg = lane < NU ? S.act[lane] : 0.f;
   const float ctrl_reg = lane < NU ? ctrl[(size_t)env * NU + lane] : 0.f;
+  int nlim = 0, iters = 0;
 #pragma unroll 1
   for (int s = 0; s < nphys; s++) {
     stage1(c);
     float act_new;
-    stage2(c, act_reg, ctrl_reg, act_new);
+    stage2<LIMITS>(c, act_reg, ctrl_reg, act_new, nlim, iters);
     act_reg = act_new;
   }
 #pragma unroll
@@ -306,7 +664,24 @@ __global__ __launch_bounds__(64, 2) void walk_step_kernel(const WalkModel *__res
     S.vlin[0] = c.vw.x; S.vlin[1] = c.vw.y; S.vlin[2] = c.vw.z;
     S.wb[0] = c.wb.x; S.wb[1] = c.wb.y; S.wb[2] = c.wb.z;
     S.pos[0] = c.pos[0]; S.pos[1] = c.pos[1]; S.pos[2] = c.pos[2];
+    if constexpr (LIMITS) { S.nlim = nlim; S.iters = iters; S.step_bits = c.overflow; }
   }
+}
+
+// smooth dynamics alone (FFE_NO_CONTACT | FFE_NO_LIMIT)
+__global__ __launch_bounds__(64, 2) void walk_step_kernel(const WalkModel *__restrict__ Wp, int flags, WState *__restrict__ states,
+                                                         const float *__restrict__ ctrl, int batch, int nphys) {
+  if ((int)blockIdx.x >= batch) return;
+  __shared__ WTile T;
+  walk_substeps<false>(T, Wp, flags, states, ctrl, nphys);
+}
+
+// smooth dynamics + joint limits (FFE_NO_CONTACT | FFE_WALK_JOINT_LIMITS)
+__global__ __launch_bounds__(64, 2) void walk_limits_kernel(const WalkModel *__restrict__ Wp, int flags, WState *__restrict__ states,
+                                                           const float *__restrict__ ctrl, int batch, int nphys) {
+  if ((int)blockIdx.x >= batch) return;
+  __shared__ WTileL T;
+  walk_substeps<true>(T, Wp, flags, states, ctrl, nphys);
 }
 
 // mj: mj_normalizeQuat as the position stage applies it (float32, a null quaternion becomes the identity)
@@ -323,7 +698,7 @@ __global__ void walk_init_states(WState *states, const WalkModel *Wp, int batch)
   if (t == 0) {
     for (int k = 0; k < 3; k++) { S.pos[k] = (double)Wp->x.qpos0[k]; S.vlin[k] = 0.f; S.wb[k] = 0.f; }
     store_quat(S, Wp->x.qpos0[3], Wp->x.qpos0[4], Wp->x.qpos0[5], Wp->x.qpos0[6]);
-    S.pad[0] = S.pad[1] = 0;
+    S.nlim = S.iters = S.step_bits = S.pad = 0;
   }
 }
 __global__ void walk_get_state_kernel(const WState *states, double *qpos, double *qvel, int batch) {
@@ -342,6 +717,19 @@ __global__ void walk_set_state_kernel(WState *states, const double *qpos, const 
   if (t < 3) { S.pos[t] = qp[t]; S.vlin[t] = (float)qv[t]; S.wb[t] = (float)qv[3 + t]; }
   if (t == 0) store_quat(S, qp[3], qp[4], qp[5], qp[6]);
 }
+// limits handle: task state {0, 0, 0, 0, limit rows of the last substep, 0, solver iterations of the last substep, overflow bits of the
+// last launch}, reals zero; validity {overflow bits of the last launch, 0, 0, 0}
+__global__ void walk_limits_report_kernel(const WState *states, int *ints, double *reals, int *info, int batch) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= batch) return;
+  const WState &S = states[i];
+  if (ints) {
+    int *o = ints + (size_t)i * 8;
+    o[0] = o[1] = o[2] = o[3] = o[5] = 0; o[4] = S.nlim; o[6] = S.iters; o[7] = S.step_bits;
+    for (int k = 0; k < 8; k++) reals[(size_t)i * 8 + k] = 0.0;
+  }
+  if (info) *reinterpret_cast<int4 *>(info + (size_t)i * 4) = make_int4(S.step_bits, 0, 0, 0);
+}
 __global__ void walk_act_kernel(WState *states, double *act, int batch, int set) {
   const int env = blockIdx.x, t = threadIdx.x;
   if (env >= batch || t >= NU) return;
@@ -353,6 +741,7 @@ __global__ void walk_act_kernel(WState *states, double *act, int batch, int set)
 // Bare physics is all that is built: reset, step, forced episodes and the timers are refused.
 struct WalkEnv final : ffe::EnvBackend {
   int flags = 0;
+  bool limits = false;  // FFE_WALK_JOINT_LIMITS: walk_limits_kernel steps this handle
   WalkHost host;
   WalkModel *model_dev = nullptr;
   WState *states = nullptr;
@@ -378,7 +767,8 @@ struct WalkEnv final : ffe::EnvBackend {
   void launch(const float *ctrl, float *, float *, float *, int32_t *, void *stream, int mode, int nphys, const uint8_t *) override {  // ctrl[B][59]
     if (mode != 2) refuse("ffe_reset / ffe_reset_envs / ffe_step");
     if (!ctrl || nphys <= 0) throw std::runtime_error("walk physics: null control buffer or no steps");
-    hipLaunchKernelGGL(walk_step_kernel, dim3(batch), dim3(64), 0, (hipStream_t)stream, model_dev, flags, states, ctrl, batch, nphys);
+    if (limits) hipLaunchKernelGGL(walk_limits_kernel, dim3(batch), dim3(64), 0, (hipStream_t)stream, model_dev, flags, states, ctrl, batch, nphys);
+    else hipLaunchKernelGGL(walk_step_kernel, dim3(batch), dim3(64), 0, (hipStream_t)stream, model_dev, flags, states, ctrl, batch, nphys);
     HIP_OK(hipGetLastError());
   }
   void get_state(double *qpos, double *qvel, void *stream) override {  // qpos[B][109], qvel[B][108]: MuJoCo's free-joint layout
@@ -397,23 +787,38 @@ struct WalkEnv final : ffe::EnvBackend {
     hipLaunchKernelGGL(walk_act_kernel, dim3(batch), dim3(64), 0, (hipStream_t)stream, states, const_cast<double *>(act), batch, 1);
     HIP_OK(hipGetLastError());
   }
-  void get_task_state(int32_t *ints, double *reals, void *stream) override {  // int32[B][8] and float64[B][8]: zeros
+  void get_task_state(int32_t *ints, double *reals, void *stream) override {  // int32[B][8] and float64[B][8]: zeros on a plain handle
+    if (limits) {
+      hipLaunchKernelGGL(walk_limits_report_kernel, dim3((batch + 63) / 64), dim3(64), 0, (hipStream_t)stream, states, ints, reals, (int *)nullptr, batch);
+      HIP_OK(hipGetLastError());
+      return;
+    }
     HIP_OK(hipMemsetAsync(ints, 0, sizeof(int32_t) * 8 * (size_t)batch, (hipStream_t)stream));
     HIP_OK(hipMemsetAsync(reals, 0, sizeof(double) * 8 * (size_t)batch, (hipStream_t)stream));
   }
-  void get_validity(int32_t *info, void *stream) override {  // int32[B][4]: zeros
+  void get_validity(int32_t *info, void *stream) override {  // int32[B][4]: zeros on a plain handle
+    if (limits) {
+      hipLaunchKernelGGL(walk_limits_report_kernel, dim3((batch + 63) / 64), dim3(64), 0, (hipStream_t)stream, states, (int *)nullptr, (double *)nullptr, info, batch);
+      HIP_OK(hipGetLastError());
+      return;
+    }
     HIP_OK(hipMemsetAsync(info, 0, sizeof(int32_t) * 4 * (size_t)batch, (hipStream_t)stream));
   }
 };
 
 std::unique_ptr<ffe::EnvBackend> walk_create(const void *blob, size_t blob_size, int physics_flags, int batch, int device) {
   if (!blob || batch <= 0) throw std::runtime_error("ffe_create_walk_physics: bad arguments");
-  if ((physics_flags & (BF_NO_CONTACT | BF_NO_LIMIT)) != (BF_NO_CONTACT | BF_NO_LIMIT))
-    throw std::runtime_error("ffe_create_walk_physics: floor contacts and joint limits are not built yet: physics_flags must contain FFE_NO_CONTACT | FFE_NO_LIMIT");
+  const bool limits = (physics_flags & BF_WALK_JOINT_LIMITS) != 0, no_limit = (physics_flags & BF_NO_LIMIT) != 0;
+  if (!(physics_flags & BF_NO_CONTACT) || limits == no_limit) {
+    // without the new bit the text is the one the C ABI contract pins; with it the text names the bit
+    if (!limits) throw std::runtime_error("ffe_create_walk_physics: floor contacts and joint limits are not built yet: physics_flags must contain FFE_NO_CONTACT | FFE_NO_LIMIT");
+    throw std::runtime_error("ffe_create_walk_physics: floor contacts and joint limits are not built yet as a step kernel: FFE_WALK_JOINT_LIMITS needs "
+                             "FFE_NO_CONTACT and excludes FFE_NO_LIMIT");
+  }
   std::unique_ptr<WalkEnv> e(new WalkEnv());  // frees the device allocations made so far if a later step throws
   Blob b(blob, blob_size);
   e->host = build_walk_model(b);
-  e->device = device; e->batch = batch; e->flags = physics_flags;
+  e->device = device; e->batch = batch; e->flags = physics_flags; e->limits = limits;
   e->host.m.b.nsub = 10;  // ffe_spec's figure: the reference's control step of 2 ms over the model's 0.2 ms (nothing here steps by it)
   HIP_OK(hipMalloc((void **)&e->model_dev, sizeof(WalkModel)));
   HIP_OK(hipMemcpy(e->model_dev, &e->host.m, sizeof(WalkModel), hipMemcpyHostToDevice));

@@ -66,13 +66,14 @@ def walk_imitation(ref_path=None, random_state=None, terminal_com_dist: float = 
     Built so far: the compiled model (`assets/fly_walk.ffmb`: free root, floor plane, Walking
     configuration), the snippet layout and walker features (`tasks/walking.py`), the DeepMimic reward maths (`tasks/rewards.py`), the
     task layer on the device (`tasks/walk_tracker.py`: features, reward, termination, observation columns), the free-root smooth
-    dynamics on the device (`batched_env.BatchedWalkPhysics`: `ffe_physics_step` with constraints off) and the float64 CPU restatement
-    of the whole task that the tests check against (test infrastructure, outside this package).  Missing: joint limits, floor
-    contacts, sensors and the episode protocol of the step kernel.  This package has no CPU path: the factory fails instead of
-    returning a slow environment."""
-    raise NotImplementedError("walk_imitation: model, reference layout, reward maths, oracle, the device task layer (WalkTracker) and the "
-                              "free-root smooth dynamics (BatchedWalkPhysics) exist; joint limits, floor contacts, sensors and the episode "
-                              "protocol of the HIP step kernel are not built yet - see DESIGN.md section 12")
+    dynamics on the device (`batched_env.BatchedWalkPhysics`: `ffe_physics_step` with constraints off, or with `joint_limits=True`
+    with the joint limits of the 102 hinges on) and the float64 CPU restatement of the whole task that the tests check against (test
+    infrastructure, outside this package).  Missing: joint limits inside a step kernel (they exist as an opt-in of the bare physics
+    only), floor contacts, sensors and the episode protocol of the step kernel.  This package has no CPU path: the factory fails
+    instead of returning a slow environment."""
+    raise NotImplementedError("walk_imitation: model, reference layout, reward maths, oracle, the device task layer (WalkTracker), the "
+                              "free-root smooth dynamics and, opt-in, their joint limits (BatchedWalkPhysics) exist; floor contacts, sensors "
+                              "and the episode protocol of the HIP step kernel are not built yet - see DESIGN.md section 12")
 
 
 def vision_guided_flight(*args, **kwargs):

@@ -23,7 +23,8 @@
  *         flight        ffe_get_act, ffe_set_act
  *         walk_on_ball  ffe_force_next_episode ("no per-episode randomness")
  *         walk physics  ffe_reset, ffe_reset_envs, ffe_step, ffe_force_next_episode, ffe_time_steps, ffe_time_kernel
- *                       ("... not available on a walk physics handle"); ffe_get_task_state / ffe_get_validity zero-fill.
+ *                       ("... not available on a walk physics handle"); ffe_get_task_state / ffe_get_validity zero-fill
+ *                       (a FFE_WALK_JOINT_LIMITS handle: see ffe_create_walk_physics).
  *   -2  a HIP call failed (text: the call and hipGetErrorString).  For historical reasons also walk_on_ball's NULL-buffer
  *       checks of ffe_step / ffe_reset ("walk_on_ball: null output buffer" / "null action buffer").
  *   Since the calls moved into csrc/capi.hip every -1 / -2 on a non-NULL handle sets ffe_last_error(h) (NULL-argument -1s and some
@@ -46,7 +47,11 @@ enum { FFE_STEP_FIRST = 0, FFE_STEP_MID = 1, FFE_STEP_LAST = 2 }; /* dm_env.Step
 /* physics switches (tests / BASELINE config 2 "constraints off"); 0 = everything on */
 enum {
   FFE_NO_FLUID = 1, FFE_NO_LIMIT = 2, FFE_NO_DAMPER = 4, FFE_NO_SPRING = 8, FFE_NO_GRAVITY = 16, FFE_NO_ACTUATION = 32,
-  FFE_NO_CONTACT = 64, FFE_NO_NOSLIP = 128, FFE_NO_ADHESION = 256 /* walk_on_ball only */
+  FFE_NO_CONTACT = 64, FFE_NO_NOSLIP = 128, FFE_NO_ADHESION = 256 /* walk_on_ball only */,
+  /* ffe_create_walk_physics only: joint limits on (the second step kernel of csrc/walk_env.hip).  An opt-in bit and provisional: it
+   * exists because plain FFE_NO_CONTACT is a pinned refusal of that create call while floor contacts are missing; when the step
+   * kernel lands it folds into "FFE_NO_LIMIT absent". */
+  FFE_WALK_JOINT_LIMITS = 512
 };
 
 /* Task inputs of fly_envs.flight_imitation (vnl_ray/fly_envs.py:29-72).  All host pointers, float64,
@@ -122,19 +127,30 @@ int ffe_create_flight(const void *model_blob, size_t blob_size, const ffe_flight
 int ffe_create_walk_on_ball(const void *model_blob, size_t blob_size, const ffe_ball_task *task, int batch, int device,
                             ffe_handle *out);
 /* The walking fly of fly_envs.walk_imitation (fly_envs.py:75-122; flybody_amd/assets/fly_walk.ffmb: free thorax, 6 + 102 dofs, 59
- * filtered actuators) as bare physics: smooth dynamics on the device, constraints off ("dynamics only", as ffe_physics_step offers for
- * the other two tasks).  Joint limits, floor contacts, sensors and the episode protocol are not built yet. */
+ * filtered actuators) as bare physics: smooth dynamics on the device with constraints off ("dynamics only", as ffe_physics_step offers
+ * for the other two tasks), or with the joint limits of its 102 hinges on (FFE_WALK_JOINT_LIMITS).  Floor contacts, sensors and the
+ * episode protocol are not built yet. */
 typedef struct {
-  int32_t physics_flags; /* FFE_NO_*; must contain FFE_NO_CONTACT | FFE_NO_LIMIT in this build */
+  /* FFE_NO_CONTACT and exactly one of FFE_NO_LIMIT (smooth dynamics alone) or FFE_WALK_JOINT_LIMITS (joint limits on: up to 48 limit
+   * rows per env and substep), plus any of the force switches FFE_NO_FLUID / _DAMPER / _SPRING / _GRAVITY / _ACTUATION; every other
+   * set is refused (the text names FFE_WALK_JOINT_LIMITS when that bit was passed) */
+  int32_t physics_flags;
 } ffe_walk_physics_task;
 /* The handle starts at the blob's qpos0 with zero velocity and zero activation and works with ffe_spec (nq 109, nv 108, nu 59,
  * action_dim 59, obs_dim 0, nsub 10, every observation offset -1) / ffe_action_bounds / ffe_physics_step (ctrl[B][59], clamped to
- * ctrlrange) / ffe_get_state / ffe_set_state / ffe_get_act / ffe_set_act / ffe_get_task_state (zeros) / ffe_get_validity (zeros) /
+ * ctrlrange) / ffe_get_state / ffe_set_state / ffe_get_act / ffe_set_act / ffe_get_task_state / ffe_get_validity (zeros on a plain handle) /
  * ffe_last_error / ffe_destroy.  State layout (MuJoCo's): qpos[109] = root position 3 (float64 on the device too), root quaternion
  * 4, the 102 hinges; qvel[108] = root linear velocity in the world frame 3, root angular velocity in the body frame 3, the hinges.
  * ffe_set_state normalises the quaternion as the position stage does.  Refused with rc < 0 and a text (ffe_last_error): flags
- * lacking FFE_NO_CONTACT | FFE_NO_LIMIT, a blob that is not the walk model; on such a handle ffe_reset, ffe_reset_envs, ffe_step,
- * ffe_time_steps, ffe_time_kernel and ffe_force_next_episode. */
+ * other than the sets named above (both limit bits together included), a blob that is not the walk model; on either kind of handle
+ * ffe_reset, ffe_reset_envs, ffe_step, ffe_time_steps, ffe_time_kernel and ffe_force_next_episode.
+ * A handle created with FFE_WALK_JOINT_LIMITS reports instead of the zeros (there is no episode protocol, so nothing is sticky):
+ *   ffe_get_validity    column 0 = the overflow bits of the last ffe_physics_step call: bit value 2 = some substep instantiated more
+ *                       joint limits than the kernel carries rows (48; walk_on_ball's bit for the same cause) - the rows that did not
+ *                       fit were dropped for that substep; columns 1-3 zero
+ *   ffe_get_task_state  int 4 = limit rows instantiated in the last substep, int 6 = solver iterations of the last substep, int 7 =
+ *                       the same overflow bits; every other int and every real zero
+ * and all of them are zero until the first ffe_physics_step. */
 int ffe_create_walk_physics(const void *model_blob, size_t blob_size, const ffe_walk_physics_task *task, int batch, int device,
                             ffe_handle *out);
 /* physics.data.act (actuator activations, [B][nu] float64 device buffers) of a walk_on_ball or walk physics handle */
