@@ -386,6 +386,22 @@ __device__ __forceinline__ const DevModel FFE_CONST &model(const Ctx &c) {
   asm volatile("" : "+s"(m));
   return *m;
 }
+// The same for what a stage derives from the lane id and the flag word.  Every stage addresses the tile by lane (lane * 24 + &T.cdof,
+// lane * 28 + &T.lT, ...) and tests flag bits; left alone, the compiler forms all of these addresses, compare masks and decoded bits
+// once, ahead of the substep loop, runs out of registers there and parks them in scratch - to fetch each back, a memory round trip,
+// right in front of the ds_read / ds_write that needs it.  A stage therefore takes the lane id and the flags through an empty asm: the
+// values are the same, but nothing derived from them can leave the stage, and an address is one v_mad_u32_u24 where it is used.
+// (The mask gives the id its range back: multiplies by a row size stay 24-bit.)
+__device__ __forceinline__ int stage_lane(const Ctx &c) {
+  int l = c.lane;
+  asm volatile("" : "+v"(l));
+  return l & (kWave - 1);
+}
+__device__ __forceinline__ int stage_flags(const Ctx &c) {
+  int f = c.flags;
+  asm volatile("" : "+s"(f));
+  return f;
+}
 
 // One workgroup = one wavefront, and a wavefront's LDS operations execute in issue order, so making one lane's LDS
 // write visible to another lane needs no hardware wait at all - only the compiler must not reorder across the point.
@@ -683,18 +699,19 @@ template <int MC>
 __device__ __forceinline__ void flight_collide(Ctx &c) {
   const DevModel FFE_CONST &M = model(c);
   Tile &T = c.T;
+  const int lane = stage_lane(c);
   c.nct = 0;
-  if (M.ncg == 0 || (c.flags & FFE_NO_CONTACT)) return;
+  if (M.ncg == 0 || (stage_flags(c) & FFE_NO_CONTACT)) return;
   CollA &A = coll_a(T);
   CollB<MC> &B = coll_b<MC>(T);
-  if (c.lane < kNSD) { float *o = A.sdc[c.lane]; o[0] = c.sd_nx; o[1] = c.sd_ny; o[2] = c.sd_nz; o[3] = __int_as_float(c.sd_pid); o[4] = c.sd_t; }
+  if (lane < kNSD) { float *o = A.sdc[lane]; o[0] = c.sd_nx; o[1] = c.sd_ny; o[2] = c.sd_nz; o[3] = __int_as_float(c.sd_pid); o[4] = c.sd_t; }
   SYNC();
 #ifdef FFE_TRACE
   const unsigned long long tr_c0 = __builtin_amdgcn_s_memrealtime();
 #endif
-  int r = __builtin_amdgcn_readfirstlane(flight_collide_a<MC>(&T, c.Mp, c.lane, c.sd_cnt, c.sd_pid));
+  int r = __builtin_amdgcn_readfirstlane(flight_collide_a<MC>(&T, c.Mp, lane, c.sd_cnt, c.sd_pid));
   if (r & 0x40000000) {
-    r = __builtin_amdgcn_readfirstlane(flight_collide_b<MC>(&T, c.Mp, c.lane, r));
+    r = __builtin_amdgcn_readfirstlane(flight_collide_b<MC>(&T, c.Mp, lane, r));
     c.nrare++;
   }
 #ifdef FFE_TRACE
@@ -703,9 +720,9 @@ __device__ __forceinline__ void flight_collide(Ctx &c) {
   c.nct = r & 0xff;
   c.ct_ovf |= (r >> 8) & 0xff;
   c.sd_cnt = r >> 16;
-  if (c.lane < kNSD) { const float *o = A.sdn[c.lane]; c.sd_nx = o[0]; c.sd_ny = o[1]; c.sd_nz = o[2]; c.sd_pid = __float_as_int(o[3]); c.sd_t = o[4]; }
-  if (c.lane < MC) {
-    const float *o = B.rec[c.lane];
+  if (lane < kNSD) { const float *o = A.sdn[lane]; c.sd_nx = o[0]; c.sd_ny = o[1]; c.sd_nz = o[2]; c.sd_pid = __float_as_int(o[3]); c.sd_t = o[4]; }
+  if (lane < MC) {
+    const float *o = B.rec[lane];
     c.ct_nx = o[0]; c.ct_ny = o[1]; c.ct_nz = o[2]; c.ct_px = o[3]; c.ct_py = o[4]; c.ct_pz = o[5]; c.ct_dist = o[6]; c.ct_incl = o[7]; c.ct_invw = o[8];
     c.ct_l1 = __float_as_int(o[9]); c.ct_l2 = __float_as_int(o[10]); c.ct_pid = __float_as_int(o[11]);
   }
@@ -717,7 +734,7 @@ __device__ __forceinline__ void flight_collide(Ctx &c) {
 __device__ __forceinline__ void stage1(Ctx &c) {
   const DevModel FFE_CONST &M = model(c);
   Tile &T = c.T;
-  const int lane = c.lane;
+  const int lane = stage_lane(c), flags = stage_flags(c);
   const bool is_link = lane < M.nlink, is_dof = lane < M.nv;
   const int l_dofadr = M.l_dofadr[lane], l_dofnum = M.l_dofnum[lane], l_sub = M.l_sub[lane];
   const int d_link = M.d_link[lane], d_kind = M.d_kind[lane];
@@ -889,12 +906,12 @@ __device__ __forceinline__ void stage1(Ctx &c) {
       const int a = (int)(((it < 4 ? anc_lo : anc_hi) >> (8 * (it & 3))) & 0xffu);
       if (a != 0xff) cacc = cacc + ld6(T.la[a]);
     }
-    if (!(c.flags & FFE_NO_GRAVITY)) { cacc.l0 -= M.gx; cacc.l1 -= M.gy; cacc.l2 -= M.gz; }
+    if (!(flags & FFE_NO_GRAVITY)) { cacc.l0 -= M.gx; cacc.l1 -= M.gy; cacc.l2 -= M.gz; }
     const I10 cin2 = ld10(T.cinert[lane]);
     const S6 cvel2 = ld6(T.lb[lane]);
     frc = mul_inert(cin2, cacc) + cross_force(cvel2, mul_inert(cin2, cvel2));
   }
-  if (!(c.flags & FFE_NO_FLUID)) {
+  if (!(flags & FFE_NO_FLUID)) {
     // mj_passive fluid forces, evaluated in link coordinates: (w_b, v_b) = link angular velocity / origin velocity
     const int ll = is_link ? lane : 0;
     const V3 xp2 = {T.xpos[ll][0], T.xpos[ll][1], T.xpos[ll][2]};
@@ -953,9 +970,9 @@ __device__ __forceinline__ void stage1(Ctx &c) {
     float bias = dot6(cd2, ld6(T.la[d_link]));
     float f = -bias;
     if (d_kind == 2) {
-      if (!(c.flags & FFE_NO_SPRING)) f -= M.d_stiff[lane] * (T.qpos[M.d_qadr[lane]] - M.d_sref[lane]);
+      if (!(flags & FFE_NO_SPRING)) f -= M.d_stiff[lane] * (T.qpos[M.d_qadr[lane]] - M.d_sref[lane]);
     }
-    if (!(c.flags & FFE_NO_DAMPER)) f -= M.d_damp[lane] * T.qvel[lane];
+    if (!(flags & FFE_NO_DAMPER)) f -= M.d_damp[lane] * T.qvel[lane];
     c.f_smooth_nb = f;
     st6(T.buf[lane], mul_inert(ld10(T.crb[d_link]), cd2));
   }
@@ -981,7 +998,7 @@ template <bool DUAL>
 __device__ __forceinline__ void bfactor(Ctx &c, float add0, float add1) {
   const DevModel FFE_CONST &M = model(c);
   Tile &T = c.T;
-  const int lane = c.lane;
+  const int lane = stage_lane(c);
   const int nv = M.nv;
   const int d_madr = c.la_pack & 0x3ff;
   STAMP(6);
@@ -1096,7 +1113,7 @@ template <int MODE>
 __device__ __forceinline__ float2 bsolve(Ctx &c, float rhs, float rhs_b = 0.f) {
   const DevModel FFE_CONST &M = *c.Mp;  // (three uniform scalars only: no need to launder the table pointer here)
   Tile &T = c.T;
-  const int lane = c.lane;
+  const int lane = stage_lane(c);
   const int nv = M.nv, nroot = M.nroot, nbr = M.nbr_steps;
   const bool is_dof = lane < nv, branch = is_dof && lane >= nroot;
   const int d_madr = c.la_pack & 0x3ff, dep = (c.la_pack >> 10) & 0x3f, d_ndesc = c.la_pack >> 16;
@@ -1195,7 +1212,7 @@ __device__ __forceinline__ V3 stage2(Ctx &c, float qfrc_act, bool integrate, boo
                      unsigned long long &hi_mask, unsigned long long &in_lo, unsigned long long &in_hi, int &iters_out) {
   const DevModel FFE_CONST &M = model(c);
   Tile &T = c.T;
-  const int lane = c.lane;
+  const int lane = stage_lane(c), flags = stage_flags(c);
   // the factor / solve index words are stage-2 business only: re-read here, they are not carried through stage 1
   c.la_pack = (unsigned)M.d_madr[lane] | ((unsigned)M.d_depth[lane] << 10) | ((unsigned)M.d_ndesc[lane] << 16);
   c.seq0 = M.br_seq[lane]; c.seq1 = M.br_seq[kWave + lane]; c.seq2 = M.br_seq[2 * kWave + lane]; c.seq3 = M.br_seq[3 * kWave + lane];
@@ -1209,7 +1226,7 @@ __device__ __forceinline__ V3 stage2(Ctx &c, float qfrc_act, bool integrate, boo
   // ---- mj_instantiateLimit / mj_makeImpedance / mj_referenceConstraint for this lane's hinge
   bool ex_lo = false, ex_hi = false;
   float D_lo = 0.f, D_hi = 0.f, ar_lo = 0.f, ar_hi = 0.f;
-  if (is_dof && d_kind == 2 && M.d_limited[lane] && !(c.flags & FFE_NO_LIMIT)) {
+  if (is_dof && d_kind == 2 && M.d_limited[lane] && !(flags & FFE_NO_LIMIT)) {
     float margin = M.d_margin[lane];
     float dist_lo = qp - M.d_lo[lane], dist_hi = M.d_hi[lane] - qp;
     float dmin = M.d_solimp[lane], dmax = M.d_solimp[kLanePad + lane], width = M.d_solimp[2 * kLanePad + lane],
@@ -1240,7 +1257,7 @@ __device__ __forceinline__ V3 stage2(Ctx &c, float qfrc_act, bool integrate, boo
   bool act_lo = ex_lo && !((in_lo >> lane) & 1ULL), act_hi = ex_hi && !((in_hi >> lane) & 1ULL);
   float a = 0.f, ae = 0.f, fc = 0.f;
   int iters = 0;
-  const bool want_euler = integrate && !(c.flags & FFE_NO_DAMPER);
+  const bool want_euler = integrate && !(flags & FFE_NO_DAMPER);
   const float hB = (is_dof && want_euler) ? h * M.d_damp[lane] : 0.f;
   // ---- contact rows of this position stage (mj: mj_makeConstraint for condim-1 contacts: one frictionless row each,
   //      J = n . (jacp of geom2's body - jacp of geom1's at the contact point), mj_makeImpedance, mj_referenceConstraint).  The row is
@@ -1458,7 +1475,7 @@ __device__ __forceinline__ V3 stage2(Ctx &c, float qfrc_act, bool integrate, boo
   V3 accel;
   {
     V3 ao = {__shfl(a, 0), __shfl(a, 1), __shfl(a, 2)};
-    if (!(c.flags & FFE_NO_GRAVITY)) { ao.x -= M.gx; ao.y -= M.gy; ao.z -= M.gz; }
+    if (!(flags & FFE_NO_GRAVITY)) { ao.x -= M.gx; ao.y -= M.gy; ao.z -= M.gz; }
     accel = mtv(ldm(T.xmat[0]), ao);
   }
   if (!integrate) return accel;
@@ -1513,8 +1530,8 @@ __device__ __forceinline__ float actuation_base(Ctx &c, float ctrl) {
 __device__ __forceinline__ float actuation(Ctx &c, float abase) {
   const DevModel FFE_CONST &M = model(c);
   Tile &T = c.T;
-  const int lane = c.lane;
-  if (c.flags & FFE_NO_ACTUATION) return 0.f;
+  const int lane = stage_lane(c), flags = stage_flags(c);
+  if (flags & FFE_NO_ACTUATION) return 0.f;
   if (lane < M.nu) {
     // phase 1: every table read of this actuator is issued before anything waits (independent addresses)
     int tq[kMaxWrap], td[kMaxWrap];
@@ -1693,18 +1710,33 @@ __global__ __launch_bounds__(kWave, FFE_WAVES_PER_SIMD) void flight_step_kernel(
   int iters = 0;
   // the stage-1 carry-over block of the previous launch (2.4 KB) depends on nothing the prologue computes: its loads are issued
   // here, ahead of the prologue's chain of dependent table reads, and land in LDS when the physics loop starts
+  // They go to their LDS home (T.cdof, T.buf, the root frame, the CoM: nothing in the prologue touches these) with the state's own
+  // vectors below, whose loads were issued after them: in registers over the prologue they crossed its function call and were spilled.
   const bool have_saved = !do_reset && S.s1_valid != 0 && !DBG(c, DBG_NO_CARRY);
   constexpr int kCarry = (kMaxDof * 6 + kWave - 1) / kWave;
-  float pre_c[kCarry], pre_b[kCarry], pre_f = 0.f, pre_m = 0.f;
+  float pre_c[kCarry], pre_b[kCarry], pre_m = 0.f;
   if (have_saved) {
 #pragma unroll
     for (int k = 0; k < kCarry; k++) {
       const int e = lane + k * kWave;
       pre_c[k] = e < kMaxDof * 6 ? S.s1_cdof[e] : 0.f; pre_b[k] = e < kMaxDof * 6 ? S.s1_buf[e] : 0.f;
     }
-    pre_f = S.s1_f[lane];
+    c.f_smooth_nb = S.s1_f[lane];  // (a lane's own value, one register that lives through the loop anyway: it needs no LDS home)
     pre_m = lane < 12 ? S.s1_misc[lane] : 0.f;
   }
+  // EVERY prologue branch that does not reset must call this once, after its own tile writes and before its last SYNC: the loop's
+  // s == 0 pass reads T.cdof / T.buf / T.xmat[0] / the CoM without asking who wrote them.
+  auto stash_carry = [&]() {
+    if (have_saved) {
+#pragma unroll
+      for (int k = 0; k < kCarry; k++) {
+        const int e = lane + k * kWave;
+        if (e < kMaxDof * 6) { (&T.cdof[0][0])[e] = pre_c[k]; (&T.buf[0][0])[e] = pre_b[k]; }
+      }
+      if (lane < 9) T.xmat[0][lane] = pre_m;
+      else if (lane < 12) T.sens[lane] = pre_m;  // CoM (see set_com)
+    }
+  };
 
   // ---- prepare: either start a new episode or load the env's state and run the task pre-step
   unsigned long long episode = S.episode;
@@ -1746,6 +1778,7 @@ __global__ __launch_bounds__(kWave, FFE_WAVES_PER_SIMD) void flight_step_kernel(
     SYNC();
   } else if (phys_only) {
     if (lane < kMaxDof + 4) { T.qpos[lane] = S.qpos[lane]; T.qvel[lane] = S.qvel[lane]; }
+    stash_carry();
     if (lane < 13) T.ghost[lane] = lane == 3 ? 1.0 : 0.0;
     ctrl_reg = lane < M.nu ? act[(size_t)env * M.nu + lane] : 0.f;
     SYNC();
@@ -1763,6 +1796,7 @@ __global__ __launch_bounds__(kWave, FFE_WAVES_PER_SIMD) void flight_step_kernel(
     const size_t row = (size_t)traj_row0 + step_counter;
     const double gh = lane < 7 ? K.ref_qpos[row * 7 + lane] : (lane < 13 ? K.ref_qvel[row * 6 + (lane - 7)] : 0.0);
     if (lane < kMaxDof + 4) { T.qpos[lane] = S.qpos[lane]; T.qvel[lane] = S.qvel[lane]; }
+    stash_carry();
     // acme CanonicalSpecWrapper folded in (ref: train_dmpo_ray.py:128-129; tasks/task_utils.py:53-76 canonical2real)
     auto to_real = [&](float v, int k) -> float {
       if (!(v == v)) v = 0.f;  // NaN scrub
@@ -1822,13 +1856,9 @@ __global__ __launch_bounds__(kWave, FFE_WAVES_PER_SIMD) void flight_step_kernel(
   const int nst = do_reset ? 1 : nsub;
 #pragma unroll 1
   for (int s = 0; s <= nst; s++) {
+    const int lane = stage_lane(c);  // (what the loop's own glue derives from the lane id stays in the loop, too)
     if (s == 0 && have_saved) {
-#pragma unroll
-      for (int k = 0; k < kCarry; k++) {
-        const int e = lane + k * kWave;
-        if (e < kMaxDof * 6) { (&T.cdof[0][0])[e] = pre_c[k]; (&T.buf[0][0])[e] = pre_b[k]; }
-      }
-      c.f_smooth_nb = pre_f;
+      // the carried-over stage-1 results are in the tile already (stash_carry)
       if (lane < MC) {  // the contacts of that position stage
         const float *o = ct_f_row(SX, lane);
         c.ct_nx = o[0]; c.ct_ny = o[1]; c.ct_nz = o[2]; c.ct_px = o[3]; c.ct_py = o[4]; c.ct_pz = o[5]; c.ct_dist = o[6]; c.ct_incl = o[7]; c.ct_invw = o[8];
@@ -1836,8 +1866,6 @@ __global__ __launch_bounds__(kWave, FFE_WAVES_PER_SIMD) void flight_step_kernel(
         c.ct_l1 = oi[0]; c.ct_l2 = oi[1]; c.ct_pid = oi[2];
       }
       c.nct = S.nct;
-      if (lane < 9) T.xmat[0][lane] = pre_m;
-      else if (lane < 12) T.sens[lane] = pre_m;  // CoM (see set_com)
       SYNC();
     } else if (!DBG(c, DBG_SKIP_STAGE1) || s == 0) { stage1(c); flight_collide<MC>(c); STAMP(16); }
     if (lane < 6 && (do_reset || s > 0)) {
