@@ -1,5 +1,5 @@
-// leg_dyn.hpp - the leg code both fly step kernels run: per-lane helpers, the block factorisation and the triangular solves of the
-// joint-space inertia, and - as the text fragment leg_stage1.inc, included into the body of each kernel's stage 1 - the dynamics half
+// leg_dyn.hpp - the leg code both fly step kernels run: per-lane helpers, the constraint impedance, the block factorisation and the
+// triangular solves of the joint-space inertia, and - as the text fragment leg_stage1.inc, included into the body of each kernel's stage 1 - the dynamics half
 // of stage 1 (kinematics, velocities / bias accelerations, body forces, subtree sums, smooth joint forces, inertia assembly,
 // factorisation).  Written once, compiled per translation unit:
 //   ball_env.hip  FREE_ROOT = false: the thorax is welded to the world (walk_on_ball);
@@ -50,6 +50,23 @@ __device__ __forceinline__ const BallModel FFE_GLOBAL &model(const C &c) {
   ModelPtr m = (ModelPtr)c.M;
   asm volatile("" : "+s"(m));
   return *m;
+}
+
+// ------------------------------------------------------------------------------------------------ impedance
+// mj: getimpedance (margin folded into `x` by the caller: x = |pos - margin|)
+__device__ __forceinline__ float impedance(const float *si, float x) {
+  float d0 = fminf(fmaxf(si[0], 1e-4f), 0.9999f), d1 = fminf(fmaxf(si[1], 1e-4f), 0.9999f);
+  const float width = fmaxf(0.f, si[2]), mid = fminf(fmaxf(si[3], 1e-4f), 0.9999f), power = fmaxf(1.f, si[4]);
+  if (d0 == d1 || width <= 1e-15f) return 0.5f * (d0 + d1);
+  x = x * frcp(width);
+  if (x >= 1.f) return d1;
+  if (x <= 0.f) return d0;
+  float y;
+  if (power == 1.f) y = x;
+  else if (power == 2.f) y = x <= mid ? x * x * frcp(mid) : 1.f - (1.f - x) * (1.f - x) * frcp(1.f - mid);
+  else if (x <= mid) y = powf(x, power) / powf(mid, power - 1.f);
+  else y = 1.f - powf(1.f - x, power) / powf(1.f - mid, power - 1.f);
+  return d0 + y * (d1 - d0);
 }
 
 // ------------------------------------------------------------------------------------------------ block factorisation

@@ -22,7 +22,8 @@
 //            x_r = S_m^-1 (b_r - M_rj z_m), a_s = z_m - Y_m x_r on the hinges;
 //   G        G_ik = s_i s_k [(M_jj^-1)_{f_i f_k} + (L^-1 Y_m[f_i]) . (L^-1 Y_m[f_k])]: the block part four columns per block solve, rows
 //            of different blocks sharing a column; the rank-6 part from each row lane's own 6-vector, the others' by v_readlane;
-//   solve    the dual Newton in row space of ball_env.hip, scalar rows only (`limits_newton`, out of line, a leaf);
+//   solve    the dual Newton in row space that the tethered kernel runs, scalar rows only (row_newton.hpp, `row_newton<RB, ScalarRows>`,
+//            out of line, a leaf);
 //   forces   qfrc_constraint = s f on the hinge right-hand side of the Euler solve; the root's is unchanged (J_r = 0): the root
 //            feels a limit through M_rj alone.
 // A substep that instantiates no row skips all of it by a wave-uniform branch.
@@ -37,6 +38,7 @@
 #include "walk_env.hpp"
 #include "walk_model.hpp"
 #include "leg_dyn.hpp"
+#include "row_newton.hpp"
 
 namespace ffw {
 using namespace dm;
@@ -87,8 +89,9 @@ struct alignas(16) WTileL {
   };
   union {
     struct { float dadd[NDP]; float Mq[NMMAX]; };
-    float G[RMAX * (RMAX + 1) / 2];     // G = J M^-1 J' over the limit rows, lower triangle packed by rows (lane r owns row r); the
-  };                                    // Newton transposes its factor through the same floats once G sits in registers
+    float G[RMAX * (RMAX + 1) / 2];     // G = J M^-1 J' over the limit rows, lower triangle packed by rows (lane r owns row r)
+    float S[RMAX * (RMAX + 1) / 2];     // the Newton transposes its factor through the same floats once G sits in registers
+  };
   union {
     float F[NDP][6];
     float lk[NL][12];
@@ -224,148 +227,6 @@ __device__ __forceinline__ void chol6_backward(const float (&Sm)[6][6], const fl
 }
 
 // ------------------------------------------------------------------------------------------------ joint-limit rows
-// mj: getimpedance with margin 0 (x = |dist|), as ball_env.hip
-__device__ __forceinline__ float impedance(const float *si, float x) {
-  float d0 = fminf(fmaxf(si[0], 1e-4f), 0.9999f), d1 = fminf(fmaxf(si[1], 1e-4f), 0.9999f);
-  const float width = fmaxf(0.f, si[2]), mid = fminf(fmaxf(si[3], 1e-4f), 0.9999f), power = fmaxf(1.f, si[4]);
-  if (d0 == d1 || width <= 1e-15f) return 0.5f * (d0 + d1);
-  x = x * frcp(width);
-  if (x >= 1.f) return d1;
-  if (x <= 0.f) return d0;
-  float y;
-  if (power == 1.f) y = x;
-  else if (power == 2.f) y = x <= mid ? x * x * frcp(mid) : 1.f - (1.f - x) * (1.f - x) * frcp(1.f - mid);
-  else if (x <= mid) y = powf(x, power) / powf(mid, power - 1.f);
-  else y = 1.f - powf(1.f - x, power) / powf(1.f - mid, power - 1.f);
-  return d0 + y * (d1 - d0);
-}
-
-constexpr int kMaxNewton = 20;
-constexpr float kNewtonTol2 = 1e-8f;  // stop when |grad| <= 1e-4 |force scale| in the M^-1 metric (ball_env.hip's figure)
-constexpr int kLsIter = 10;
-constexpr float kLsTol = 1e-2f;       // |phi'(alpha)| <= tol |phi'(0)|: an inexact line search, the Newton loop converges the rest
-
-// mj: mj_fwdConstraint in the space of the limit rows: the dense Newton of ball_env.hip (see the comment block of its stage 2)
-// specialised to scalar rows.  With y = y0 + G lambda the force law is f(y) = -D min(0, y) per row; the Newton step is
-// d = -(I + W G)^-1 (lambda - f), W = diag(D on the rows with y < 0), solved as d = -e + L u, (I + L G L) u = L G e, L = sqrt(W),
-// followed by an exact line search on the convex piecewise-quadratic cost.  Lane = row, R <= RB rows: the lane's row of G and of
-// S = I + L G L in registers, the other lanes' scalars by v_readlane.  Starts from lambda = 0 (no warm start: a limit row comes and
-// goes with its hinge).  Reads T.G, T.r_y0, T.r_D; leaves the forces in T.r_f.  A real call and a leaf: the loop then has the whole
-// register file to itself.
-template <int RB>
-__device__ __noinline__ int limits_newton(WTileL *Tp, const int lane, const int R, const float scale2) {
-  WTileL &T = *Tp;
-  int iters = 0;
-  f2 Gp[RB / 2], Sp[RB / 2];
-  auto G_ = [&](int j) -> float { return (j & 1) ? Gp[j >> 1].y : Gp[j >> 1].x; };
-  auto S_ = [&](int j) -> float { return (j & 1) ? Sp[j >> 1].y : Sp[j >> 1].x; };
-  auto setS = [&](int j, float v) { if (j & 1) Sp[j >> 1].y = v; else Sp[j >> 1].x = v; };
-  auto gload = [&](int j) -> float { return (lane < R && j < R) ? T.G[j <= lane ? lane * (lane + 1) / 2 + j : j * (j + 1) / 2 + lane] : 0.f; };
-#pragma unroll
-  for (int m = 0; m < RB / 2; m++) Gp[m] = f2{gload(2 * m), gload(2 * m + 1)};
-  const float y0v = lane < R ? T.r_y0[lane] : 0.f;
-  const float D = lane < R ? T.r_D[lane] : 0.f;
-  DM_SYNC();  // G sits in registers: its floats carry the factor's transpose from here on
-  auto gdot = [&](float vreg) {  // (G v)[lane], v given as one value per lane
-    f2 acc = f2{0.f, 0.f};
-#pragma unroll
-    for (int m = 0; m < RB / 2; m++) acc = __builtin_elementwise_fma(Gp[m], f2{rl_f(vreg, 2 * m), rl_f(vreg, 2 * m + 1)}, acc);  // G = 0 beyond the R live rows
-    return acc.x + acc.y;
-  };
-  auto eval = [&](float y) { return y < 0.f ? -D * y : 0.f; };
-  float lam = 0.f, yv = y0v, fv = 0.f;
-  bool fresh = false;  // fv belongs to the current yv
-#pragma unroll 1
-  for (int it = 0; it < kMaxNewton; it++) {
-    fresh = true;
-    fv = eval(yv);
-    const float Ld = (yv < 0.f && D > 0.f) ? fsqrt(D) : 0.f;
-    const float ev = lam - fv;
-    const float pv = gdot(ev);
-    const float gn2 = wave_sum(pv * ev);
-    if (gn2 <= kNewtonTol2 * scale2 + 1e-30f) break;
-    iters++;
-#pragma unroll
-    for (int j = 0; j < RB; j++) {
-      if (j < R) setS(j, (j == lane ? 1.f : 0.f) + Ld * G_(j) * rl_f(Ld, j));
-      else setS(j, j == lane ? 1.f : 0.f);
-    }
-    float w = Ld * pv;  // rhs = L p
-    // Cholesky of S (row per lane) as S = Lt D Lt', Lt unit lower triangular: S_(k) ends as Lt[lane][k] below the diagonal and 0 on
-    // and above it, so that the substitutions are one unconditional FMA per step; ipp = 1 / D[lane]
-    float ipp = 1.f;
-#pragma unroll
-    for (int k = 0; k < RB; k++) {
-      if (k < R) {
-        const float ip = __builtin_amdgcn_rsqf(rl_f(S_(k), k));
-        const float lik = S_(k) * ip;
-        if ((k & 1) == 0) Sp[k >> 1].y -= lik * rl_f(lik, k + 1);  // the pair partner of an even pivot column
-        const f2 nl = f2{-lik, -lik};
-#pragma unroll
-        for (int m = (k >> 1) + 1; m < RB / 2; m++)  // rows / columns beyond R are identity: no-ops
-          Sp[m] = __builtin_elementwise_fma(nl, f2{rl_f(lik, 2 * m), rl_f(lik, 2 * m + 1)}, Sp[m]);
-        setS(k, lane > k ? lik * ip : 0.f);
-        ipp = lane == k ? ip * ip : ipp;
-      }
-    }
-#pragma unroll
-    for (int k = 0; k < RB; k++)  // forward substitution Lt z = w
-      if (k < R) w -= S_(k) * rl_f(w, k);
-    w *= ipp;
-    // transpose through LDS (this lane's column of Lt; the strict lower triangle packed by rows, row i at i (i - 1) / 2), then the
-    // backward substitution Lt' u = D^-1 z
-    if (lane < R) {
-      const int tri = lane * (lane - 1) / 2;
-#pragma unroll
-      for (int j = 0; j < RB; j++) if (j < lane) T.G[tri + j] = S_(j);
-    }
-    DM_SYNC();
-#pragma unroll
-    for (int m = 0; m < RB / 2; m++) Sp[m] = f2{0.f, 0.f};
-    if (lane < R) {
-#pragma unroll
-      for (int k = 0; k < RB; k++) if (k < R && k > lane) setS(k, T.G[k * (k - 1) / 2 + lane]);
-    }
-    DM_SYNC();
-#pragma unroll
-    for (int k = RB - 1; k >= 0; k--)
-      if (k < R) w -= S_(k) * rl_f(w, k);
-    const float dl = lane < R ? -ev + Ld * w : 0.f;  // d = -e + L u
-    const float jdv = gdot(dl);
-    const float c1s = wave_sum(dl * jdv);
-    const float d0 = wave_sum(ev * jdv);  // phi'(0) = (lambda - f(y)) . G d
-    // exact line search on the convex phi(alpha): root of phi'(alpha) = phi'(0) + alpha c1 - sum_rows (f(y + alpha jd) - f(y)) jd
-    auto dphi = [&](float al) { return d0 + al * c1s + wave_sum((fv - eval(yv + al * jdv)) * jdv); };
-    float alpha = 0.f;
-    {
-      if (!(d0 < 0.f)) break;  // not a descent direction any more: converged to rounding
-      float lo = 0.f, hi = 1.f, dlo = d0, dhi = dphi(1.f);
-      int guard = 0;
-      while (dhi < 0.f && fabsf(dhi) > kLsTol * fabsf(d0) && guard++ < 8) { lo = hi; dlo = dhi; hi *= 2.f; dhi = dphi(hi); }
-      if (dhi < 0.f || fabsf(dhi) <= kLsTol * fabsf(d0)) alpha = hi;  // full (or doubled) Newton step: |phi'| already small
-      else {
-#pragma unroll 1
-        for (int ls = 0; ls < kLsIter; ls++) {
-          float mid = lo - dlo * (hi - lo) / (dhi - dlo);
-          if (!(mid > lo + 0.05f * (hi - lo)) || !(mid < hi - 0.05f * (hi - lo))) mid = 0.5f * (lo + hi);
-          const float dm_ = dphi(mid);
-          if (dm_ < 0.f) { lo = mid; dlo = dm_; } else { hi = mid; dhi = dm_; }
-          if (fabsf(dm_) <= kLsTol * fabsf(d0) || hi - lo <= 1e-6f * hi) break;
-        }
-        alpha = (dhi - dlo) != 0.f ? lo - dlo * (hi - lo) / (dhi - dlo) : hi;
-        if (!(alpha >= lo) || !(alpha <= hi)) alpha = 0.5f * (lo + hi);
-      }
-    }
-    lam += alpha * dl;
-    yv += alpha * jdv;  // y = y0 + G lambda stays current without another product
-    fresh = false;
-  }
-  if (!fresh) fv = eval(yv);  // forces at the solution
-  if (lane < R) T.r_f[lane] = fv;
-  DM_SYNC();
-  return iters;
-}
-
 // The constraint block of a substep with R > 0 limit rows (rows already in T.r_sgn / r_D / r_dof / r_blk, -aref in T.r_y0): adds the
 // hinges' constraint forces to `qs`.  Returns the solver's iterations.
 template <class C>
@@ -467,11 +328,11 @@ __device__ __forceinline__ int limit_forces(C &c, const int R, const int (&lrow)
     DM_SYNC();
   }
   // ---- solve, then qfrc_constraint = s f on the hinges
-  int iters;
-  if (R <= 8) iters = limits_newton<8>(c.T, lane, R, scale2);
-  else if (R <= 16) iters = limits_newton<16>(c.T, lane, R, scale2);
-  else if (R <= 32) iters = limits_newton<32>(c.T, lane, R, scale2);
-  else iters = limits_newton<RMAX>(c.T, lane, R, scale2);
+  int iters;  // (ScalarRows reads no model table and ignores the contact-row count, the noslip sweeps and the warm-start flag)
+  if (R <= 8) iters = row_newton<8, ScalarRows>(c.T, nullptr, lane, R, 0, scale2, 0, 0);
+  else if (R <= 16) iters = row_newton<16, ScalarRows>(c.T, nullptr, lane, R, 0, scale2, 0, 0);
+  else if (R <= 32) iters = row_newton<32, ScalarRows>(c.T, nullptr, lane, R, 0, scale2, 0, 0);
+  else iters = row_newton<RMAX, ScalarRows>(c.T, nullptr, lane, R, 0, scale2, 0, 0);
 #pragma unroll
   for (int s = 0; s < 3; s++) if (lrow[s] >= 0) qs[s] += lsgn[s] * T.r_f[lrow[s]];
   DM_SYNC();

@@ -22,7 +22,7 @@ def test_create_walk_physics_is_declared_and_exported():
     assert "ffe_create_walk_physics" in _capi.SYMBOLS
     build.build()
     assert hasattr(_capi.lib(), "ffe_create_walk_physics")
-    assert "walk_env.hip" in build.SOURCES and {"leg_dyn.hpp", "leg_stage1.inc", "walk_model.hpp", "walk_env.hpp"} <= set(build.HEADERS)
+    assert "walk_env.hip" in build.SOURCES and {"leg_dyn.hpp", "leg_stage1.inc", "row_newton.hpp", "walk_model.hpp", "walk_env.hpp"} <= set(build.HEADERS)
 
 
 def test_free_root_kernel_meets_its_resource_targets():
@@ -53,8 +53,13 @@ def test_the_step_kernels_live_in_separate_translation_units():
     ball, walk = open(os.path.join(csrc, "ball_env.hip")).read(), open(os.path.join(csrc, "walk_env.hip")).read()
     assert "ball_step_kernel" in ball and "walk_step_kernel" not in ball and "FREE_ROOT = false" in ball
     assert "walk_step_kernel" in walk and "ball_step_kernel" not in walk and "FREE_ROOT = true" in walk
-    for src in (ball, walk):  # both compile the same leg code
-        assert '#include "leg_dyn.hpp"' in src and '#include "leg_stage1.inc"' in src
+    for src in (ball, walk):  # both compile the same leg code and the same constraint solve
+        assert '#include "leg_dyn.hpp"' in src and '#include "leg_stage1.inc"' in src and '#include "row_newton.hpp"' in src
+        assert "row_newton<" in src
+    for name in sorted(os.listdir(csrc)):  # and no source defines a Newton of its own
+        if name.endswith(".hip"):
+            src = open(os.path.join(csrc, name)).read()
+            assert "dense_newton(" not in src and "limits_newton(" not in src, name
 
 
 @pytest.fixture(scope="module")
