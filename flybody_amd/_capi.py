@@ -66,6 +66,42 @@ class Spec(C.Structure):
                                  "off_world_zaxis", "off_ref_displacement", "off_ref_root_quat", "n_obs_joints", "n_ref")]
 
 
+class LibHandle:
+    """Owns one handle of the library: `_h` (a `c_void_p`, None once closed) on `_L`.  A family names its symbols - `_destroy`, `_last_error` -
+    and the prefix its error texts carry."""
+
+    _destroy = _last_error = None
+    _error_prefix = ""
+    _h = None
+    _OWN = object()
+
+    def _check(self, rc, h=_OWN, prefix=None):
+        """Raises the family's text for a call that returned `rc` != 0 on handle `h` (default: this object's; None: a create function)."""
+        if rc != 0:
+            text = getattr(self._L, self._last_error)(self._h if h is LibHandle._OWN else h).decode()
+            raise RuntimeError((self._error_prefix if prefix is None else prefix) + text)
+
+    def close(self):
+        if self._h:
+            getattr(self._L, self._destroy)(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # noqa: BLE001
+            pass
+
+
+def device_view(torch, device, ptr, shape, typestr):
+    """torch tensor over library-owned device memory (no copy), via the CUDA array interface"""
+
+    class _Mem:
+        __cuda_array_interface__ = {"shape": tuple(shape), "typestr": typestr, "data": (int(ptr), False), "version": 2, "strides": None}
+
+    return torch.as_tensor(_Mem(), device=device)
+
+
 _lib = None
 
 

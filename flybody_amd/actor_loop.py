@@ -36,7 +36,10 @@ def _step_bits_arg(step_bits, batch_size: int, device):
     raise ValueError(f"step_bits must have shape ({batch_size},) or be the contiguous ({batch_size}, 4) validity buffer")
 
 
-class NStepTransitionWriter:
+_device_view = _capi.device_view
+
+
+class NStepTransitionWriter(_capi.LibHandle):
     """Device-resident batched n-step transition adder (`ffe_nstep_*`, flybody_amd/csrc/nstep.hip): what the reference's
     actors do one env at a time through `acme.adders.reverb.NStepTransitionAdder(n_step=50, discount=...)`
     (`agents/ray_distributed_dmpo.py:514-521`, `agents/actors.py:91-101`), for B envs per call, into a replay ring in HBM.
@@ -49,6 +52,8 @@ class NStepTransitionWriter:
     validity buffer) is then required, and `transitions(with_taint=True)` returns a sixth tensor, uint8 [N], 1 where the transition
     spans an env-step whose physics was truncated - or the step after one, because a launch's last position stage drives the first
     substep of the next (include/flybody_env.h, ffe_nstep_observe_flagged).  Off (the default), everything is as without it."""
+
+    _destroy, _last_error = "ffe_nstep_destroy", "ffe_nstep_last_error"
 
     def __init__(self, batch_size: int, obs_dim: int, act_dim: int, *, n_step: int = 50, discount: float = 0.99, capacity: int = 1 << 20,
                  device: int = 0, track_validity: bool = False):
@@ -68,8 +73,7 @@ class NStepTransitionWriter:
         self.device = torch.device("cuda", device)
         h = C.c_void_p()
         create = self._L.ffe_nstep_create_tracked if track_validity else self._L.ffe_nstep_create
-        if create(batch_size, obs_dim, act_dim, n_step, float(discount), capacity, device, C.byref(h)) != 0:
-            raise RuntimeError("ffe_nstep_create: " + self._L.ffe_nstep_last_error(None).decode())
+        self._check(create(batch_size, obs_dim, act_dim, n_step, float(discount), capacity, device, C.byref(h)), None, "ffe_nstep_create: ")
         self._h = h
         ptr = [C.c_void_p() for _ in range(6)]
         assert self._L.ffe_nstep_buffers(self._h, *[C.byref(p) for p in ptr]) == 0
@@ -77,8 +81,7 @@ class NStepTransitionWriter:
         self._taint_ptr = None
         if track_validity:
             tp = C.c_void_p()
-            if self._L.ffe_nstep_taint_buffer(self._h, C.byref(tp)) != 0:
-                raise RuntimeError("ffe_nstep_taint_buffer: " + self._L.ffe_nstep_last_error(self._h).decode())
+            self._check(self._L.ffe_nstep_taint_buffer(self._h, C.byref(tp)), prefix="ffe_nstep_taint_buffer: ")
             self._taint_ptr = tp.value
 
     def observe(self, action, timestep, flat_observation, step_bits=None):
@@ -106,31 +109,20 @@ class NStepTransitionWriter:
         else:
             rc = self._L.ffe_nstep_observe(self._h, action.data_ptr(), st.data_ptr(), timestep.reward.data_ptr(), timestep.discount.data_ptr(),
                                            flat_observation.data_ptr(), stream)
-        if rc != 0:
-            raise RuntimeError("ffe_nstep_observe: " + self._L.ffe_nstep_last_error(self._h).decode())
+        self._check(rc, prefix="ffe_nstep_observe: ")
 
     def num_written(self) -> int:
         """Transitions written since creation (synchronises)."""
-        import numpy as np
-
         t = self._t
         t.cuda.synchronize(self.device)
-        out = np.zeros(1, dtype=np.uint64)
         # 8 bytes device -> host through a torch view of the counter
         cnt = self._view(self._ptr[5], (1,), t.int64)
         return int(cnt.cpu()[0])
 
     def _view(self, ptr, shape, dtype):
-        """torch tensor over library-owned device memory (no copy), via the CUDA array interface."""
+        """`_capi.device_view` on the writer's device, by torch dtype"""
         t = self._t
-        itemsize = {t.float32: 4, t.int64: 8, t.uint8: 1}[dtype]
-        typestr = {t.float32: "<f4", t.int64: "<i8", t.uint8: "|u1"}[dtype]
-
-        class _Mem:
-            __cuda_array_interface__ = {"shape": tuple(shape), "typestr": typestr, "data": (int(ptr), False), "version": 2, "strides": None}
-
-        del itemsize
-        return t.as_tensor(_Mem(), device=self.device)
+        return _device_view(t, self.device, ptr, shape, {t.float32: "<f4", t.int64: "<i8", t.uint8: "|u1"}[dtype])
 
     def transitions(self, with_taint: bool = False):
         """(obs [N,O], action [N,A], n_step_return [N], discount [N], next_obs [N,O]) views of the N = min(written, capacity) filled slots.
@@ -149,22 +141,11 @@ class NStepTransitionWriter:
             return o, a, r, d, o2, self._view(self._taint_ptr, (self.capacity,), t.uint8)[:n]
         return o, a, r, d, o2
 
-    def close(self):
-        if getattr(self, "_h", None):
-            self._L.ffe_nstep_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
 
 ReplaySample = collections.namedtuple("ReplaySample", ["obs", "action", "n_step_return", "discount", "next_obs", "taint", "index"])
 
 
-class ReplaySampler:
+class ReplaySampler(_capi.LibHandle):
     """Uniform minibatches from one or several writers' replay rings, drawn and gathered on the device (`ffe_sampler_*`,
     flybody_amd/csrc/replay.hip): the read side of the table the reference builds at `agents/ray_distributed_dmpo.py:85-113`,
     `reverb.Table(sampler=Uniform(), remover=Fifo(), max_size=..., rate_limiter=MinSize(min_replay_size) | SampleToInsertRatio(...))`,
@@ -185,6 +166,8 @@ class ReplaySampler:
 
     `skip_tainted` (tracked writers only): a draw that hits a tainted row is redrawn, up to eight tries; the eighth is kept and
     counted in `info()["tainted_kept"]`."""
+
+    _destroy, _last_error = "ffe_sampler_destroy", "ffe_sampler_last_error"
 
     def __init__(self, writers, batch_size: int = 256, *, seed: int = 0, min_size: int = 1, skip_tainted: bool = False):
         if isinstance(writers, NStepTransitionWriter):
@@ -223,9 +206,8 @@ class ReplaySampler:
         self.obs_dim, self.act_dim, self.device = w0.obs_dim, w0.act_dim, w0.device
         handles = (C.c_void_p * len(writers))(*[w._h.value for w in writers])
         h = C.c_void_p()
-        if self._L.ffe_sampler_create(handles, len(writers), self.batch_size, self.seed, self.min_size, 1 if skip_tainted else 0, self.device.index,
-                                      C.byref(h)) != 0:
-            raise RuntimeError(self._L.ffe_sampler_last_error(None).decode())
+        self._check(self._L.ffe_sampler_create(handles, len(writers), self.batch_size, self.seed, self.min_size, 1 if skip_tainted else 0, self.device.index,
+                                               C.byref(h)), None)
         self._h = h
         K, dev = self.batch_size, self.device
         self._out = ReplaySample(torch.zeros(K, self.obs_dim, device=dev), torch.zeros(K, self.act_dim, device=dev), torch.zeros(K, device=dev),
@@ -249,8 +231,7 @@ class ReplaySampler:
         o = self._out
         rc = self._L.ffe_sampler_sample(self._h, o.obs.data_ptr(), o.action.data_ptr(), o.n_step_return.data_ptr(), o.discount.data_ptr(), o.next_obs.data_ptr(),
                                         o.taint.data_ptr() if o.taint is not None else None, o.index.data_ptr(), C.c_void_p(cur.cuda_stream))
-        if rc != 0:
-            raise RuntimeError(self._L.ffe_sampler_last_error(self._h).decode())
+        self._check(rc)
         return o
 
     def info(self) -> dict:
@@ -261,26 +242,6 @@ class ReplaySampler:
         self._t.cuda.synchronize(self.device)
         v = self._info.tolist()
         return {"ready": bool(v[0]), "total": v[1], "call": v[2], "tainted_kept": v[3], "samples_drawn": v[4]}
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._L.ffe_sampler_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-def _device_view(torch, device, ptr, shape, typestr):
-    """torch tensor over library-owned device memory (no copy), via the CUDA array interface"""
-
-    class _Mem:
-        __cuda_array_interface__ = {"shape": tuple(shape), "typestr": typestr, "data": (int(ptr), False), "version": 2, "strides": None}
-
-    return torch.as_tensor(_Mem(), device=device)
 
 
 def record_dtype():
@@ -353,7 +314,7 @@ def summarize(records, last=None, by_tag=False, num_tags=None):
     return {k: np.array([row[k] for row in rows], dtype=np.int64 if k in ints else np.float64) for k in keys}
 
 
-class EpisodeLog:
+class EpisodeLog(_capi.LibHandle):
     """One record per finished episode, written on the device (`ffe_eplog_*`, flybody_amd/csrc/episode_log.hip): what the reference's
     `EnvironmentLoop` logs per episode and its evaluator keeps in `self._stats` (`agents/ray_distributed_dmpo.py:401-440`), for B envs
     per call.  `observe(timestep)` is one launch on torch's current stream with no host read (capturable into a HIP graph): per env a
@@ -362,6 +323,8 @@ class EpisodeLog:
 
     `one_shot=True`: only envs armed by `arm(mask)` emit, and an env disarms on its LAST - every armed env contributes exactly its next
     finished episode; `info()["armed_left"]` counts the ones still running (`BatchedEvaluator` polls it)."""
+
+    _destroy, _last_error = "ffe_eplog_destroy", "ffe_eplog_last_error"
 
     def __init__(self, batch_size: int, *, capacity: int = 1 << 16, device: int = 0, one_shot: bool = False):
         if not isinstance(one_shot, bool):
@@ -382,8 +345,7 @@ class EpisodeLog:
         self.batch_size, self.capacity, self.one_shot = int(batch_size), int(capacity), one_shot
         self.device = torch.device("cuda", int(device))
         h = C.c_void_p()
-        if self._L.ffe_eplog_create(self.batch_size, self.capacity, 1 if one_shot else 0, int(device), C.byref(h)) != 0:
-            raise RuntimeError(self._L.ffe_eplog_last_error(None).decode())
+        self._check(self._L.ffe_eplog_create(self.batch_size, self.capacity, 1 if one_shot else 0, int(device), C.byref(h)), None)
         self._h = h
         rec, info = C.c_void_p(), C.c_void_p()
         assert self._L.ffe_eplog_buffers(self._h, C.byref(rec), C.byref(info)) == 0
@@ -391,7 +353,7 @@ class EpisodeLog:
         self._info = _device_view(torch, self.device, info.value, (4,), "<i8")
 
     def _check_open(self):
-        if not getattr(self, "_h", None):
+        if not self._h:
             raise RuntimeError("the episode log is closed")
 
     def _stream(self):
@@ -425,8 +387,7 @@ class EpisodeLog:
             tag_ptr, stride = tags.data_ptr(), max(1, int(tags.stride(0)))
         rc = self._L.ffe_eplog_observe(self._h, st.data_ptr(), rew.data_ptr(), disc.data_ptr(), validity.data_ptr() if validity is not None else None,
                                        tag_ptr, stride, self._stream())
-        if rc != 0:
-            raise RuntimeError(self._L.ffe_eplog_last_error(self._h).decode())
+        self._check(rc)
 
     def arm(self, mask=None):
         """One-shot logs: envs with `mask[i] != 0` (bool / uint8 [B] on the log's device; None = all) emit their next finished episode.
@@ -442,8 +403,7 @@ class EpisodeLog:
             if not mask.is_cuda or mask.device != self.device or tuple(mask.shape) != (self.batch_size,) or not mask.is_contiguous():
                 raise ValueError(f"mask must be contiguous, of shape ({self.batch_size},), on the log's device {self.device}")
             m = mask.view(t.uint8) if mask.dtype == t.bool else mask
-        if self._L.ffe_eplog_arm(self._h, m.data_ptr() if m is not None else None, self._stream()) != 0:
-            raise RuntimeError(self._L.ffe_eplog_last_error(self._h).decode())
+        self._check(self._L.ffe_eplog_arm(self._h, m.data_ptr() if m is not None else None, self._stream()))
 
     def info(self) -> dict:
         """`written` (records since creation), `calls` (observe calls), `armed_left` (one-shot: armed envs still in their episode).
@@ -465,16 +425,8 @@ class EpisodeLog:
         return summarize(self.records(), last=last, by_tag=by_tag, num_tags=num_tags)
 
     def close(self):
-        if getattr(self, "_h", None):
-            self._L.ffe_eplog_destroy(self._h)
-            self._h = None
-            self._records = self._info = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        super().close()
+        self._records = self._info = None
 
 
 class BatchedEvaluator:

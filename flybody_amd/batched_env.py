@@ -55,9 +55,12 @@ def time_limit_control_steps(time_limit: float, physics_timestep: float, nsub: i
     return n
 
 
-class EnvHandle:
-    """One handle of the C ABI (include/flybody_env.h) and what every kind of handle shares: `_h`, `_L`, `device`, error checking, the
-    stream, the spec and the raw state accessors.  `get_act` / `set_act` exist on every kind; the library refuses them on a flight handle."""
+class EnvHandle(_capi.LibHandle):
+    """One env handle of the C ABI (include/flybody_env.h) and what every kind of handle shares: `_h`, `_L`, `device`, error checking and
+    `close` (`_capi.LibHandle`), the stream, the spec and the raw state accessors.  `get_act` / `set_act` exist on every kind; the library
+    refuses them on a flight handle."""
+
+    _destroy, _last_error, _error_prefix = "ffe_destroy", "ffe_last_error", "flybody_env: "
 
     def _open(self, batch_size: int, device: int):
         """Binds the library and the device; the subclass then creates its handle and passes it to `_adopt`."""
@@ -72,8 +75,7 @@ class EnvHandle:
 
     def _adopt(self, what: str, rc: int, h):
         """Takes the handle a create function returned and reads its spec and action bounds."""
-        if rc != 0:
-            raise RuntimeError(what + ": " + self._L.ffe_last_error(None).decode())
+        self._check(rc, None, what + ": ")
         self._h = h
         self.spec = _capi.Spec()
         self._check(self._L.ffe_spec(self._h, C.byref(self.spec)))
@@ -81,23 +83,8 @@ class EnvHandle:
         self._check(self._L.ffe_action_bounds(self._h, amin, amax))
         self._action_min, self._action_max = np.array(amin[:], dtype=np.float32), np.array(amax[:], dtype=np.float32)
 
-    def _check(self, rc):
-        if rc != 0:
-            raise RuntimeError("flybody_env: " + self._L.ffe_last_error(self._h).decode())
-
     def _stream(self):
         return C.c_void_p(self._torch.cuda.current_stream(self.device).cuda_stream)
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._L.ffe_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def raw_action_bounds(self):
         """(minimum, maximum) of the un-wrapped action spec (`fruitfly.py:496-526`)."""

@@ -10,55 +10,34 @@
 #include "walk_env.hpp"
 
 using ffe::EnvBackend;
+using ffe::need;
 using ffe::Refused;
 
 struct ffe_env {
   std::unique_ptr<EnvBackend> be;
+  int device = 0;
   std::string err;
 };
 
 static thread_local std::string g_err;  // of the create functions
 
-// a bad argument is a refusal with a text
-static void need(bool ok, const char *text) {
-  if (!ok) throw Refused(text);
-}
-
-// Every call on a handle: on the handle's device, -1 when the backend (or `body` itself) refuses, -2 on any other failure; both leave
-// the text in the handle.  Only a NULL handle has nowhere to put one.
+// Every call on a handle goes through the handle layer (handle.hpp): on the handle's device, -1 when the backend (or `body` itself)
+// refuses, -2 on any other failure, the text in the handle.  A NULL handle has nowhere to put one, and this family writes none.
 template <class F>
 static int on_handle(ffe_handle h, F &&body) {
-  if (!h) return -1;
-  ffe::DeviceGuard guard(h->be->device);
-  try {
-    body(*h->be);
-  } catch (const Refused &e) {
-    h->err = e.what();
-    return -1;
-  } catch (const std::exception &e) {
-    h->err = e.what();
-    return -2;
-  }
-  return 0;
+  return ffe::on_handle(h, "", nullptr, [&](ffe_env &e) { body(*e.be); });
 }
 
 // Every create: `make` runs on `device`; whatever it throws is a refusal (-1) with the text in ffe_last_error(NULL).
 template <class F>
 static int create(const char *who, bool args_ok, int device, ffe_handle *out, F &&make) {
-  if (!out) return -1;
-  *out = nullptr;
-  try {
+  return ffe::create(out, nullptr, g_err, [&](ffe_env &e) {
     if (!args_ok) throw Refused(std::string(who) + ": bad arguments");
     ffe::check_device(device, who);
     ffe::DeviceGuard guard(device);
-    std::unique_ptr<ffe_env> h(new ffe_env());
-    h->be = make();
-    *out = h.release();
-  } catch (const std::exception &e) {
-    g_err = e.what();
-    return -1;
-  }
-  return 0;
+    e.device = device;
+    e.be = make();
+  });
 }
 
 static int launch_step(ffe_handle h, const float *act, float *obs, float *rew, float *disc, int32_t *st, void *stream, int mode,
@@ -91,12 +70,7 @@ int ffe_create_walk_physics(const void *model_blob, size_t blob_size, const ffe_
                 [&] { return ffw::walk_create(model_blob, blob_size, task->physics_flags, batch, device); });
 }
 
-int ffe_destroy(ffe_handle h) {
-  if (!h) return -1;
-  ffe::DeviceGuard guard(h->be->device);
-  delete h;
-  return 0;
-}
+int ffe_destroy(ffe_handle h) { return ffe::destroy(h, "", nullptr); }
 
 int ffe_spec(ffe_handle h, ffe_spec_t *s) {
   return on_handle(h, [&](EnvBackend &be) { need(s, "ffe_spec: null spec"); be.spec(*s); });

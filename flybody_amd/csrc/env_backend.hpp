@@ -1,8 +1,6 @@
 // env_backend.hpp - host-only: the interface between the C ABI (capi.hip) and the three kinds of env handle - flight (fly_env.hip),
-// walk_on_ball (ball_env.hip), free-root walk physics (walk_env.hip) - and the host helpers every handle in csrc/ shares.
-//
-// Errors travel as exceptions and become the ABI's codes in one place (capi.hip): `Refused` = -1, the call was refused or its arguments
-// were bad and nothing was launched; every other std::exception (HIP_OK throws std::runtime_error) = -2.
+// walk_on_ball (ball_env.hip), free-root walk physics (walk_env.hip).  A backend throws (`Refused`, HIP_OK: handle.hpp); capi.hip turns
+// that into the ABI's codes through the handle layer every family shares.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -12,38 +10,9 @@
 #include <string>
 
 #include "../../include/flybody_env.h"
-
-#define HIP_OK(expr)                                                                              \
-  do {                                                                                            \
-    hipError_t _e = (expr);                                                                       \
-    if (_e != hipSuccess) throw std::runtime_error(std::string(#expr) + ": " + hipGetErrorString(_e)); \
-  } while (0)
+#include "handle.hpp"
 
 namespace ffe {
-
-struct Refused : std::runtime_error {
-  using std::runtime_error::runtime_error;
-};
-
-// Every entry point runs on the handle's device and leaves the caller's current device untouched.
-struct DeviceGuard {
-  int prev = -1;
-  bool switched = false;
-  explicit DeviceGuard(int device) {
-    if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-    if (prev != device) { switched = (hipSetDevice(device) == hipSuccess); }
-  }
-  ~DeviceGuard() { if (switched && prev >= 0) (void)hipSetDevice(prev); }
-  DeviceGuard(const DeviceGuard &) = delete;
-  DeviceGuard &operator=(const DeviceGuard &) = delete;
-};
-
-// `who`: the create function, for the text
-inline void check_device(int device, const char *who) {
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) throw Refused("no HIP device: the MI355X path has no CPU fallback");
-  if (device < 0 || device >= ndev) throw Refused(std::string(who) + ": no such device");
-}
 
 // ffe_time_kernel: events around the step kernel alone.  A launch calls start() before the step kernel, stop() right after it and
 // collect() once everything else of the launch (the launch-order kernel) is queued; all three do nothing unless armed.

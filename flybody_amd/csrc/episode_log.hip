@@ -21,7 +21,8 @@
 #include <memory>
 #include <string>
 
-#include "env_backend.hpp"
+#include "../../include/flybody_env.h"
+#include "handle.hpp"
 
 namespace ffl {
 
@@ -130,93 +131,69 @@ struct ffe_eplog {
   ffl::Record *records = nullptr;
   unsigned long long *info = nullptr;  // [4]
   unsigned int *ticket = nullptr;
+  ffe::DeviceBuffers mem{"ffe_eplog_create"};
   std::string err;
 };
 
-static thread_local std::string g_lerr;
+static thread_local std::string g_lerr;  // of ffe_eplog_create and of calls on a NULL handle
 
-namespace {
-void free_all(ffe_eplog *p) {
-  (void)hipFree(p->ep_ret); (void)hipFree(p->ep_len); (void)hipFree(p->armed); (void)hipFree(p->records); (void)hipFree(p->info); (void)hipFree(p->ticket);
-}
-}  // namespace
+using ffe::need;
+using ffe::Refused;
 
 extern "C" {
 
 int ffe_eplog_create(int batch, long long capacity, int flags, int device, ffe_eplog_handle *out) {
-  if (!out) { g_lerr = "ffe_eplog_create: null out"; return -1; }
-  *out = nullptr;
-  auto fail = [&](const std::string &text) { g_lerr = "ffe_eplog_create: " + text; return -1; };
-  if (batch <= 0) return fail("batch " + std::to_string(batch) + " is below 1");
-  if (flags & ~FFE_EPLOG_ONE_SHOT) return fail("unknown flags " + std::to_string(flags));
-  // one call can emit a record for every env; in a smaller ring two records of the same launch would share a slot
-  if (capacity < batch)
-    return fail("capacity " + std::to_string(capacity) + " is below batch = " + std::to_string(batch) + ", the records one call can write: they would share slots of the ring");
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || device < 0 || device >= ndev) return fail("no such HIP device: the MI355X path has no CPU fallback");
-  ffe::DeviceGuard guard(device);
-  std::unique_ptr<ffe_eplog> p(new ffe_eplog());
-  p->device = device; p->batch = batch; p->flags = flags; p->capacity = capacity;
-  const size_t B = (size_t)batch;
-  bool ok = hipMalloc((void **)&p->ep_ret, B * sizeof(float)) == hipSuccess && hipMalloc((void **)&p->ep_len, B * sizeof(int)) == hipSuccess &&
-            hipMalloc((void **)&p->armed, B) == hipSuccess && hipMalloc((void **)&p->records, (size_t)capacity * sizeof(ffl::Record)) == hipSuccess &&
-            hipMalloc((void **)&p->info, 4 * sizeof(unsigned long long)) == hipSuccess && hipMalloc((void **)&p->ticket, sizeof(unsigned int)) == hipSuccess;
-  if (ok)
-    ok = hipMemset(p->ep_ret, 0, B * sizeof(float)) == hipSuccess && hipMemset(p->ep_len, 0, B * sizeof(int)) == hipSuccess &&
-         hipMemset(p->armed, 0, B) == hipSuccess && hipMemset(p->records, 0, (size_t)capacity * sizeof(ffl::Record)) == hipSuccess &&
-         hipMemset(p->info, 0, 4 * sizeof(unsigned long long)) == hipSuccess && hipMemset(p->ticket, 0, sizeof(unsigned int)) == hipSuccess &&
-         hipDeviceSynchronize() == hipSuccess;
-  if (!ok) { free_all(p.get()); return fail("out of device memory"); }
-  *out = p.release();
-  return 0;
+  return ffe::create(out, "ffe_eplog_create: null out", g_lerr, [&](ffe_eplog &p) {
+    auto must = [](bool ok, const std::string &text) { if (!ok) throw Refused("ffe_eplog_create: " + text); };
+    must(batch > 0, "batch " + std::to_string(batch) + " is below 1");
+    must(!(flags & ~FFE_EPLOG_ONE_SHOT), "unknown flags " + std::to_string(flags));
+    // one call can emit a record for every env; in a smaller ring two records of the same launch would share a slot
+    must(capacity >= batch,
+         "capacity " + std::to_string(capacity) + " is below batch = " + std::to_string(batch) + ", the records one call can write: they would share slots of the ring");
+    ffe::check_device(device, "ffe_eplog_create", true);
+    ffe::DeviceGuard guard(device);
+    p.device = device; p.batch = batch; p.flags = flags; p.capacity = capacity;
+    const size_t B = (size_t)batch;
+    p.ep_ret = p.mem.zeroed<float>(B); p.ep_len = p.mem.zeroed<int>(B); p.armed = p.mem.zeroed<unsigned char>(B);
+    p.records = p.mem.zeroed<ffl::Record>((size_t)capacity); p.info = p.mem.zeroed<unsigned long long>(4); p.ticket = p.mem.zeroed<unsigned int>(1);
+    p.mem.ready();
+  });
 }
 
 int ffe_eplog_arm(ffe_eplog_handle h, const uint8_t *mask_dev, void *stream) {
-  if (!h) { g_lerr = "ffe_eplog_arm: null handle"; return -1; }
-  if (!(h->flags & FFE_EPLOG_ONE_SHOT)) { h->err = "ffe_eplog_arm: the log was not created one-shot (FFE_EPLOG_ONE_SHOT): a plain log records every episode"; return -1; }
-  ffe::DeviceGuard guard(h->device);
-  hipLaunchKernelGGL(ffl::episode_log_arm_kernel, dim3(1), dim3(256), 0, static_cast<hipStream_t>(stream), mask_dev, h->armed, h->info, h->batch);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) { h->err = std::string("ffe_eplog_arm: ") + hipGetErrorString(e); return -2; }
-  return 0;
+  return ffe::on_handle(h, "ffe_eplog_arm", &g_lerr, [&](ffe_eplog &p) {
+    need(p.flags & FFE_EPLOG_ONE_SHOT, "ffe_eplog_arm: the log was not created one-shot (FFE_EPLOG_ONE_SHOT): a plain log records every episode");
+    hipLaunchKernelGGL(ffl::episode_log_arm_kernel, dim3(1), dim3(256), 0, static_cast<hipStream_t>(stream), mask_dev, p.armed, p.info, p.batch);
+    ffe::launched("ffe_eplog_arm");
+  });
 }
 
 int ffe_eplog_observe(ffe_eplog_handle h, const int32_t *step_type_dev, const float *reward_dev, const float *discount_dev, const int32_t *info_dev,
                       const int32_t *tag_dev, int tag_stride_ints, void *stream) {
-  if (!h) { g_lerr = "ffe_eplog_observe: null handle"; return -1; }
-  if (!step_type_dev || !reward_dev || !discount_dev) { h->err = "ffe_eplog_observe: a null input (only info_dev and tag_dev may be NULL)"; return -1; }
-  if (tag_dev && tag_stride_ints < 1) { h->err = "ffe_eplog_observe: tag_stride_ints " + std::to_string(tag_stride_ints) + " is below 1"; return -1; }
-  ffe::DeviceGuard guard(h->device);
-  const dim3 grid((h->batch + 255) / 256), block(256);
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  if (h->flags & FFE_EPLOG_ONE_SHOT)
-    hipLaunchKernelGGL(ffl::episode_log_kernel<true>, grid, block, 0, s, step_type_dev, reward_dev, discount_dev, info_dev, tag_dev, (long long)tag_stride_ints, h->ep_ret,
-                       h->ep_len, h->armed, h->records, (unsigned long long)h->capacity, h->info, h->ticket, h->batch);
-  else
-    hipLaunchKernelGGL(ffl::episode_log_kernel<false>, grid, block, 0, s, step_type_dev, reward_dev, discount_dev, info_dev, tag_dev, (long long)tag_stride_ints, h->ep_ret,
-                       h->ep_len, h->armed, h->records, (unsigned long long)h->capacity, h->info, h->ticket, h->batch);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) { h->err = std::string("ffe_eplog_observe: ") + hipGetErrorString(e); return -2; }
-  return 0;
+  return ffe::on_handle(h, "ffe_eplog_observe", &g_lerr, [&](ffe_eplog &p) {
+    need(step_type_dev && reward_dev && discount_dev, "ffe_eplog_observe: a null input (only info_dev and tag_dev may be NULL)");
+    if (tag_dev && tag_stride_ints < 1) throw Refused("ffe_eplog_observe: tag_stride_ints " + std::to_string(tag_stride_ints) + " is below 1");
+    const dim3 grid((p.batch + 255) / 256), block(256);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (p.flags & FFE_EPLOG_ONE_SHOT)
+      hipLaunchKernelGGL(ffl::episode_log_kernel<true>, grid, block, 0, s, step_type_dev, reward_dev, discount_dev, info_dev, tag_dev, (long long)tag_stride_ints, p.ep_ret,
+                         p.ep_len, p.armed, p.records, (unsigned long long)p.capacity, p.info, p.ticket, p.batch);
+    else
+      hipLaunchKernelGGL(ffl::episode_log_kernel<false>, grid, block, 0, s, step_type_dev, reward_dev, discount_dev, info_dev, tag_dev, (long long)tag_stride_ints, p.ep_ret,
+                         p.ep_len, p.armed, p.records, (unsigned long long)p.capacity, p.info, p.ticket, p.batch);
+    ffe::launched("ffe_eplog_observe");
+  });
 }
 
 int ffe_eplog_buffers(ffe_eplog_handle h, void **records_dev, long long **info_dev) {
-  if (!h) { g_lerr = "ffe_eplog_buffers: null handle"; return -1; }
-  if (!records_dev || !info_dev) { h->err = "ffe_eplog_buffers: a null output pointer"; return -1; }
-  *records_dev = h->records;
-  *info_dev = reinterpret_cast<long long *>(h->info);
-  return 0;
+  return ffe::on_handle(h, "ffe_eplog_buffers", &g_lerr, [&](ffe_eplog &p) {
+    need(records_dev && info_dev, "ffe_eplog_buffers: a null output pointer");
+    *records_dev = p.records;
+    *info_dev = reinterpret_cast<long long *>(p.info);
+  });
 }
 
-int ffe_eplog_destroy(ffe_eplog_handle h) {
-  if (!h) { g_lerr = "ffe_eplog_destroy: null handle"; return -1; }
-  {
-    ffe::DeviceGuard guard(h->device);
-    free_all(h);
-  }
-  delete h;
-  return 0;
-}
+int ffe_eplog_destroy(ffe_eplog_handle h) { return ffe::destroy(h, "ffe_eplog_destroy", &g_lerr); }
 
 const char *ffe_eplog_last_error(ffe_eplog_handle h) { return h ? h->err.c_str() : g_lerr.c_str(); }
 

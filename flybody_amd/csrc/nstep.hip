@@ -29,7 +29,8 @@
 #include <stdexcept>
 #include <string>
 
-#include "env_backend.hpp"
+#include "../../include/flybody_env.h"
+#include "handle.hpp"
 #include "nstep_ring.hpp"
 
 namespace ffn {
@@ -253,54 +254,61 @@ __global__ void validity_stats_kernel(const int *__restrict__ st, const int *__r
 
 }  // namespace ffn
 
+using ffe::need;
+using ffe::Refused;
 using ffn::Handle;
 
-static thread_local std::string g_nerr;
+static thread_local std::string g_nerr;  // of the create functions and of calls on a NULL handle
 
-extern "C" {
+// what the handle layer (handle.hpp) works on
+static Handle *inner(ffe_nstep_handle p) { return p ? &p->h : nullptr; }
 
 static int nstep_create(int batch, int obs_dim, int act_dim, int n_step, float discount, long long capacity, int device, bool tracked, ffe_nstep_handle *out) {
-  if (!out) return -1;
-  *out = nullptr;
-  if (batch <= 0 || obs_dim <= 0 || act_dim <= 0 || n_step <= 0 || capacity <= 0) { g_nerr = "ffe_nstep_create: bad arguments"; return -1; }
-  // one call can write batch x n_step rows (every env on LAST with a full ring); in a smaller ring two transitions of the same launch
-  // would share a slot, and a row's five arrays are stored by different waves: a torn row
-  if (capacity < (long long)batch * n_step) {
-    g_nerr = "ffe_nstep_create: capacity " + std::to_string(capacity) + " is below batch x n_step = " + std::to_string((long long)batch * n_step) +
-             ", the rows one call can write: they would share slots of the ring";
-    return -1;
-  }
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || device < 0 || device >= ndev) { g_nerr = "no such HIP device: the MI355X path has no CPU fallback"; return -1; }
-  ffe::DeviceGuard guard(device);
-  std::unique_ptr<ffe_nstep> p(new ffe_nstep());
-  Handle &H = p->h;
-  H.device = device;
-  ffn::Dev &D = H.d;
-  D.batch = batch; D.obs_dim = obs_dim; D.act_dim = act_dim; D.n_step = n_step; D.gamma = discount; D.capacity = capacity;
-  bool ok = true;
-  auto alloc = [&](size_t bytes) -> void * {
-    void *q = nullptr;
-    if (hipMalloc(&q, bytes) != hipSuccess) { ok = false; return nullptr; }
-    (void)hipMemset(q, 0, bytes);
-    H.allocs[H.nalloc++] = q;
-    return q;
-  };
-  const size_t B = (size_t)batch, n = (size_t)n_step, O = (size_t)obs_dim, A = (size_t)act_dim, C = (size_t)capacity;
-  D.r_obs = (float *)alloc(B * n * O * 4); D.r_act = (float *)alloc(B * n * A * 4); D.r_rew = (float *)alloc(B * n * 4); D.r_disc = (float *)alloc(B * n * 4);
-  D.last_obs = (float *)alloc(B * O * 4); D.head = (int *)alloc(B * 4); D.count = (int *)alloc(B * 4);
-  D.t_obs = (float *)alloc(C * O * 4); D.t_act = (float *)alloc(C * A * 4); D.t_ret = (float *)alloc(C * 4); D.t_disc = (float *)alloc(C * 4);
-  D.t_next = (float *)alloc(C * O * 4); D.written = (unsigned long long *)alloc(8);
-  if (tracked) { D.r_mark = (unsigned char *)alloc(B * n); D.prev_bits = (int *)alloc(B * 4); D.t_taint = (unsigned char *)alloc(C); }
-  (void)hipDeviceSynchronize();
-  if (!ok) {
-    for (int k = 0; k < H.nalloc; k++) (void)hipFree(H.allocs[k]);
-    g_nerr = "ffe_nstep_create: out of device memory";
-    return -1;
-  }
-  *out = p.release();
-  return 0;
+  return ffe::create(out, "ffe_nstep_create: null out", g_nerr, [&](ffe_nstep &p) {
+    need(batch > 0 && obs_dim > 0 && act_dim > 0 && n_step > 0 && capacity > 0, "ffe_nstep_create: bad arguments");
+    // one call can write batch x n_step rows (every env on LAST with a full ring); in a smaller ring two transitions of the same launch
+    // would share a slot, and a row's five arrays are stored by different waves: a torn row
+    if (capacity < (long long)batch * n_step)
+      throw Refused("ffe_nstep_create: capacity " + std::to_string(capacity) + " is below batch x n_step = " + std::to_string((long long)batch * n_step) +
+                    ", the rows one call can write: they would share slots of the ring");
+    ffe::check_device(device, "ffe_nstep_create", true);
+    ffe::DeviceGuard guard(device);
+    Handle &H = p.h;
+    H.device = device;
+    ffn::Dev &D = H.d;
+    D.batch = batch; D.obs_dim = obs_dim; D.act_dim = act_dim; D.n_step = n_step; D.gamma = discount; D.capacity = capacity;
+    ffe::DeviceBuffers &M = H.mem;
+    const size_t B = (size_t)batch, n = (size_t)n_step, O = (size_t)obs_dim, A = (size_t)act_dim, C = (size_t)capacity;
+    D.r_obs = M.zeroed<float>(B * n * O); D.r_act = M.zeroed<float>(B * n * A); D.r_rew = M.zeroed<float>(B * n); D.r_disc = M.zeroed<float>(B * n);
+    D.last_obs = M.zeroed<float>(B * O); D.head = M.zeroed<int>(B); D.count = M.zeroed<int>(B);
+    D.t_obs = M.zeroed<float>(C * O); D.t_act = M.zeroed<float>(C * A); D.t_ret = M.zeroed<float>(C); D.t_disc = M.zeroed<float>(C);
+    D.t_next = M.zeroed<float>(C * O); D.written = M.zeroed<unsigned long long>(1);
+    if (tracked) { D.r_mark = M.zeroed<unsigned char>(B * n); D.prev_bits = M.zeroed<int>(B); D.t_taint = M.zeroed<unsigned char>(C); }
+    M.ready();
+  });
 }
+
+// a tracked writer always runs the tracking kernel: fed through ffe_nstep_observe its bits are zero
+static int nstep_observe(const char *who, bool flagged, ffe_nstep_handle p, const float *action_dev, const int32_t *step_type_dev, const float *reward_dev,
+                         const float *discount_dev, const float *obs_dev, const int32_t *step_bits_dev, int stride_ints, void *stream) {
+  return ffe::on_handle(inner(p), who, &g_nerr, [&](Handle &H) {
+    if (flagged) {
+      need(H.d.t_taint, "ffe_nstep_observe_flagged: the writer was created without validity tracking (ffe_nstep_create_tracked)");
+      need(step_bits_dev && stride_ints >= 1, "ffe_nstep_observe_flagged: null step_bits_dev or stride_ints < 1");
+    }
+    if (!step_type_dev || !reward_dev || !discount_dev || !obs_dev || !action_dev) throw Refused(std::string(who) + ": a null input");
+    const dim3 grid((H.d.batch + ffn::kEnvsPerBlock - 1) / ffn::kEnvsPerBlock), block(64 * ffn::kEnvsPerBlock);
+    if (H.d.t_taint)
+      hipLaunchKernelGGL(ffn::nstep_observe_kernel<true>, grid, block, 0, static_cast<hipStream_t>(stream), H.d, action_dev, step_type_dev, reward_dev, discount_dev,
+                         obs_dev, step_bits_dev, stride_ints);
+    else
+      hipLaunchKernelGGL(ffn::nstep_observe_kernel<false>, grid, block, 0, static_cast<hipStream_t>(stream), H.d, action_dev, step_type_dev, reward_dev, discount_dev,
+                         obs_dev, static_cast<const int32_t *>(nullptr), 0);
+    ffe::launched(who);
+  });
+}
+
+extern "C" {
 
 int ffe_nstep_create(int batch, int obs_dim, int act_dim, int n_step, float discount, long long capacity, int device, ffe_nstep_handle *out) {
   return nstep_create(batch, obs_dim, act_dim, n_step, discount, capacity, device, false, out);
@@ -310,63 +318,44 @@ int ffe_nstep_create_tracked(int batch, int obs_dim, int act_dim, int n_step, fl
 }
 
 int ffe_nstep_destroy(ffe_nstep_handle p) {
-  if (!p) return -1;
-  ffe::DeviceGuard guard(p->h.device);
-  for (int k = 0; k < p->h.nalloc; k++) (void)hipFree(p->h.allocs[k]);
-  delete p;
-  return 0;
-}
-
-// a tracked writer always runs the tracking kernel: fed through ffe_nstep_observe its bits are zero
-static int nstep_observe(ffe_nstep_handle p, const float *action_dev, const int32_t *step_type_dev, const float *reward_dev, const float *discount_dev,
-                         const float *obs_dev, const int32_t *step_bits_dev, int stride_ints, void *stream) {
-  if (!p || !step_type_dev || !reward_dev || !discount_dev || !obs_dev || !action_dev) return -1;
-  ffe::DeviceGuard guard(p->h.device);
-  const dim3 grid((p->h.d.batch + ffn::kEnvsPerBlock - 1) / ffn::kEnvsPerBlock), block(64 * ffn::kEnvsPerBlock);
-  if (p->h.d.t_taint)
-    hipLaunchKernelGGL(ffn::nstep_observe_kernel<true>, grid, block, 0, static_cast<hipStream_t>(stream), p->h.d, action_dev, step_type_dev, reward_dev, discount_dev,
-                       obs_dev, step_bits_dev, stride_ints);
-  else
-    hipLaunchKernelGGL(ffn::nstep_observe_kernel<false>, grid, block, 0, static_cast<hipStream_t>(stream), p->h.d, action_dev, step_type_dev, reward_dev, discount_dev,
-                       obs_dev, static_cast<const int32_t *>(nullptr), 0);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) { p->h.err = hipGetErrorString(e); return -2; }
+  if (!p) return ffe::on_handle(inner(p), "ffe_nstep_destroy", &g_nerr, [](Handle &) {});
+  delete p;  // (the buffers free themselves, on their device)
   return 0;
 }
 
 int ffe_nstep_observe(ffe_nstep_handle p, const float *action_dev, const int32_t *step_type_dev, const float *reward_dev, const float *discount_dev,
                       const float *obs_dev, void *stream) {
-  return nstep_observe(p, action_dev, step_type_dev, reward_dev, discount_dev, obs_dev, nullptr, 0, stream);
+  return nstep_observe("ffe_nstep_observe", false, p, action_dev, step_type_dev, reward_dev, discount_dev, obs_dev, nullptr, 0, stream);
 }
 
 int ffe_nstep_observe_flagged(ffe_nstep_handle p, const float *action_dev, const int32_t *step_type_dev, const float *reward_dev, const float *discount_dev,
                               const float *obs_dev, const int32_t *step_bits_dev, int stride_ints, void *stream) {
-  if (!p) return -1;
-  if (!p->h.d.t_taint) { p->h.err = "ffe_nstep_observe_flagged: the writer was created without validity tracking (ffe_nstep_create_tracked)"; return -1; }
-  if (!step_bits_dev || stride_ints < 1) { p->h.err = "ffe_nstep_observe_flagged: null step_bits_dev or stride_ints < 1"; return -1; }
-  return nstep_observe(p, action_dev, step_type_dev, reward_dev, discount_dev, obs_dev, step_bits_dev, stride_ints, stream);
+  return nstep_observe("ffe_nstep_observe_flagged", true, p, action_dev, step_type_dev, reward_dev, discount_dev, obs_dev, step_bits_dev, stride_ints, stream);
 }
 
 int ffe_nstep_taint_buffer(ffe_nstep_handle p, uint8_t **taint) {
-  if (!p || !taint) return -1;
-  if (!p->h.d.t_taint) { p->h.err = "ffe_nstep_taint_buffer: the writer was created without validity tracking (ffe_nstep_create_tracked)"; return -1; }
-  *taint = p->h.d.t_taint;
-  return 0;
+  return ffe::on_handle(inner(p), "ffe_nstep_taint_buffer", &g_nerr, [&](Handle &H) {
+    need(taint, "ffe_nstep_taint_buffer: null taint");
+    need(H.d.t_taint, "ffe_nstep_taint_buffer: the writer was created without validity tracking (ffe_nstep_create_tracked)");
+    *taint = H.d.t_taint;
+  });
 }
 
 int ffe_nstep_buffers(ffe_nstep_handle p, float **obs, float **act, float **ret, float **disc, float **next_obs, unsigned long long **written_dev) {
-  if (!p) return -1;
-  const ffn::Dev &D = p->h.d;
-  if (obs) *obs = D.t_obs;
-  if (act) *act = D.t_act;
-  if (ret) *ret = D.t_ret;
-  if (disc) *disc = D.t_disc;
-  if (next_obs) *next_obs = D.t_next;
-  if (written_dev) *written_dev = D.written;
-  return 0;
+  return ffe::on_handle(inner(p), "ffe_nstep_buffers", &g_nerr, [&](Handle &H) {
+    const ffn::Dev &D = H.d;
+    if (obs) *obs = D.t_obs;
+    if (act) *act = D.t_act;
+    if (ret) *ret = D.t_ret;
+    if (disc) *disc = D.t_disc;
+    if (next_obs) *next_obs = D.t_next;
+    if (written_dev) *written_dev = D.written;
+  });
 }
 
 const char *ffe_nstep_last_error(ffe_nstep_handle p) { return p ? p->h.err.c_str() : g_nerr.c_str(); }
+
+// the three launchers without a handle: -1 bad arguments, -2 the launch was not accepted, no text
 
 int ffe_pack_timestep(const float *obs_dev, const float *reward_dev, const float *discount_dev, const int32_t *step_type_dev, float *packed_dev,
                       int batch, int obs_dim, void *stream) {
@@ -374,7 +363,7 @@ int ffe_pack_timestep(const float *obs_dev, const float *reward_dev, const float
   const long long total = (long long)batch * (obs_dim + 3);
   hipLaunchKernelGGL(ffn::pack_timestep_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream), obs_dev, reward_dev,
                      discount_dev, step_type_dev, packed_dev, batch, obs_dim);
-  return hipGetLastError() == hipSuccess ? 0 : -2;
+  return ffe::launch_error() ? -2 : 0;
 }
 
 int ffe_episode_stats(const int32_t *step_type_dev, const float *reward_dev, float *episode_return_dev, long long *episode_length_dev,
@@ -382,13 +371,13 @@ int ffe_episode_stats(const int32_t *step_type_dev, const float *reward_dev, flo
   if (!step_type_dev || !reward_dev || !episode_return_dev || !episode_length_dev || !totals_i64_dev || !total_return_dev || batch <= 0) return -1;
   hipLaunchKernelGGL(ffn::episode_stats_kernel, dim3((batch + 255) / 256), dim3(256), 0, static_cast<hipStream_t>(stream), step_type_dev, reward_dev,
                      episode_return_dev, episode_length_dev, totals_i64_dev, total_return_dev, batch);
-  return hipGetLastError() == hipSuccess ? 0 : -2;
+  return ffe::launch_error() ? -2 : 0;
 }
 
 int ffe_validity_stats(const int32_t *step_type_dev, const int32_t *info_dev, long long *totals_dev, int batch, void *stream) {
   if (!step_type_dev || !info_dev || !totals_dev || batch <= 0 || (reinterpret_cast<uintptr_t>(info_dev) & 15)) return -1;
   hipLaunchKernelGGL(ffn::validity_stats_kernel, dim3((batch + 255) / 256), dim3(256), 0, static_cast<hipStream_t>(stream), step_type_dev, info_dev, totals_dev, batch);
-  return hipGetLastError() == hipSuccess ? 0 : -2;
+  return ffe::launch_error() ? -2 : 0;
 }
 
 }  // extern "C"

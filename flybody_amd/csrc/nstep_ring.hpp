@@ -4,6 +4,8 @@
 
 #include <string>
 
+#include "handle.hpp"
+
 namespace ffn {
 
 struct Dev {
@@ -26,8 +28,7 @@ struct Dev {
 struct Handle {
   Dev d{};
   int device = 0;
-  void *allocs[20] = {nullptr};
-  int nalloc = 0;
+  ffe::DeviceBuffers mem{"ffe_nstep_create"};
   std::string err;
 };
 

@@ -24,7 +24,8 @@
 #include <memory>
 #include <string>
 
-#include "env_backend.hpp"
+#include "../../include/flybody_env.h"
+#include "handle.hpp"
 #include "nstep_ring.hpp"
 
 namespace ffs {
@@ -195,98 +196,82 @@ struct ffe_sampler {
   ffs::Ctrl *ctrl = nullptr;
   ffs::State *state = nullptr;
   long long *info = nullptr;
+  ffe::DeviceBuffers mem{"ffe_sampler_create"};
   std::string err;
 };
 
-static thread_local std::string g_serr;
+static thread_local std::string g_serr;  // of ffe_sampler_create and of calls on a NULL handle
+
+using ffe::need;
 
 extern "C" {
 
 int ffe_sampler_create(const ffe_nstep_handle *writers, int n_writers, int batch, uint64_t seed, long long min_size, int flags, int device,
                        ffe_sampler_handle *out) {
-  if (!out) { g_serr = "ffe_sampler_create: null out"; return -1; }
-  *out = nullptr;
-  auto fail = [&](const std::string &text) { g_serr = "ffe_sampler_create: " + text; return -1; };
-  if (!writers) return fail("null writers");
-  if (n_writers < 1 || n_writers > ffs::kMaxRings) return fail("n_writers " + std::to_string(n_writers) + " is outside 1 .. 8");
-  if (batch < 1 || batch > (1 << 20)) return fail("batch " + std::to_string(batch) + " is outside 1 .. 2^20");
-  if (min_size < 1) return fail("min_size " + std::to_string(min_size) + " is below 1");
-  if (flags & ~FFE_SAMPLE_SKIP_TAINTED) return fail("unknown flags " + std::to_string(flags));
-  ffs::Ring host[ffs::kMaxRings];
-  bool tracked = true;
-  for (int r = 0; r < n_writers; r++) {
-    if (!writers[r]) return fail("writer " + std::to_string(r) + " is null");
-    const ffn::Handle &W = writers[r]->h;
-    const ffn::Dev &D = W.d;
-    if (W.device != device) return fail("writer " + std::to_string(r) + " is on device " + std::to_string(W.device) + ", the sampler on " + std::to_string(device));
-    if (D.obs_dim != writers[0]->h.d.obs_dim || D.act_dim != writers[0]->h.d.act_dim)
-      return fail("writer " + std::to_string(r) + " has rows of (" + std::to_string(D.obs_dim) + ", " + std::to_string(D.act_dim) + "), writer 0 of (" +
-                  std::to_string(writers[0]->h.d.obs_dim) + ", " + std::to_string(writers[0]->h.d.act_dim) + "): obs_dim and act_dim must be equal");
-    if (D.capacity >= (1LL << 40)) return fail("writer " + std::to_string(r) + " has a capacity of 2^40 or more: index packs the slot into 40 bits");
-    tracked = tracked && D.t_taint != nullptr;
-    host[r] = ffs::Ring{D.t_obs, D.t_act, D.t_ret, D.t_disc, D.t_next, D.t_taint, D.written, (unsigned long long)D.capacity};
-  }
-  if ((flags & FFE_SAMPLE_SKIP_TAINTED) && !tracked) return fail("FFE_SAMPLE_SKIP_TAINTED needs every writer created with validity tracking (ffe_nstep_create_tracked)");
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || device < 0 || device >= ndev) return fail("no such HIP device: the MI355X path has no CPU fallback");
-  ffe::DeviceGuard guard(device);
-  std::unique_ptr<ffe_sampler> p(new ffe_sampler());
-  p->device = device; p->n_rings = n_writers; p->batch = batch; p->flags = flags; p->tracked = tracked;
-  p->obs_dim = writers[0]->h.d.obs_dim; p->act_dim = writers[0]->h.d.act_dim;
-  p->seed = seed; p->min_size = (unsigned long long)min_size;
-  bool ok = hipMalloc((void **)&p->rings, sizeof(host)) == hipSuccess && hipMalloc((void **)&p->ctrl, sizeof(ffs::Ctrl)) == hipSuccess &&
-            hipMalloc((void **)&p->state, sizeof(ffs::State)) == hipSuccess && hipMalloc((void **)&p->info, 8 * sizeof(long long)) == hipSuccess;
-  if (ok) {
-    for (int r = n_writers; r < ffs::kMaxRings; r++) host[r] = ffs::Ring{};
-    ok = hipMemcpy(p->rings, host, sizeof(host), hipMemcpyHostToDevice) == hipSuccess && hipMemset(p->ctrl, 0, sizeof(ffs::Ctrl)) == hipSuccess &&
-         hipMemset(p->state, 0, sizeof(ffs::State)) == hipSuccess && hipMemset(p->info, 0, 8 * sizeof(long long)) == hipSuccess &&
-         hipDeviceSynchronize() == hipSuccess;
-  }
-  if (!ok) { (void)hipFree(p->rings); (void)hipFree(p->ctrl); (void)hipFree(p->state); (void)hipFree(p->info); }
-  if (!ok) return fail("out of device memory");
-  *out = p.release();
-  return 0;
+  return ffe::create(out, "ffe_sampler_create: null out", g_serr, [&](ffe_sampler &s) {
+    auto must = [](bool ok, const std::string &text) { if (!ok) throw ffe::Refused("ffe_sampler_create: " + text); };
+    must(writers, "null writers");
+    must(n_writers >= 1 && n_writers <= ffs::kMaxRings, "n_writers " + std::to_string(n_writers) + " is outside 1 .. 8");
+    must(batch >= 1 && batch <= (1 << 20), "batch " + std::to_string(batch) + " is outside 1 .. 2^20");
+    must(min_size >= 1, "min_size " + std::to_string(min_size) + " is below 1");
+    must(!(flags & ~FFE_SAMPLE_SKIP_TAINTED), "unknown flags " + std::to_string(flags));
+    ffs::Ring host[ffs::kMaxRings] = {};
+    bool tracked = true;
+    for (int r = 0; r < n_writers; r++) {
+      must(writers[r], "writer " + std::to_string(r) + " is null");
+      const ffn::Handle &W = writers[r]->h;
+      const ffn::Dev &D = W.d, &D0 = writers[0]->h.d;
+      must(W.device == device, "writer " + std::to_string(r) + " is on device " + std::to_string(W.device) + ", the sampler on " + std::to_string(device));
+      must(D.obs_dim == D0.obs_dim && D.act_dim == D0.act_dim,
+           "writer " + std::to_string(r) + " has rows of (" + std::to_string(D.obs_dim) + ", " + std::to_string(D.act_dim) + "), writer 0 of (" +
+               std::to_string(D0.obs_dim) + ", " + std::to_string(D0.act_dim) + "): obs_dim and act_dim must be equal");
+      must(D.capacity < (1LL << 40), "writer " + std::to_string(r) + " has a capacity of 2^40 or more: index packs the slot into 40 bits");
+      tracked = tracked && D.t_taint != nullptr;
+      host[r] = ffs::Ring{D.t_obs, D.t_act, D.t_ret, D.t_disc, D.t_next, D.t_taint, D.written, (unsigned long long)D.capacity};
+    }
+    must(!(flags & FFE_SAMPLE_SKIP_TAINTED) || tracked, "FFE_SAMPLE_SKIP_TAINTED needs every writer created with validity tracking (ffe_nstep_create_tracked)");
+    ffe::check_device(device, "ffe_sampler_create", true);
+    ffe::DeviceGuard guard(device);
+    s.device = device; s.n_rings = n_writers; s.batch = batch; s.flags = flags; s.tracked = tracked;
+    s.obs_dim = writers[0]->h.d.obs_dim; s.act_dim = writers[0]->h.d.act_dim;
+    s.seed = seed; s.min_size = (unsigned long long)min_size;
+    s.rings = s.mem.zeroed<ffs::Ring>(ffs::kMaxRings); s.ctrl = s.mem.zeroed<ffs::Ctrl>(1);
+    s.state = s.mem.zeroed<ffs::State>(1); s.info = s.mem.zeroed<long long>(8);
+    must(hipMemcpy(s.rings, host, sizeof(host), hipMemcpyHostToDevice) == hipSuccess, "out of device memory");
+    s.mem.ready();
+  });
 }
 
 int ffe_sampler_sample(ffe_sampler_handle s, float *obs_dev, float *act_dev, float *ret_dev, float *disc_dev, float *next_obs_dev, uint8_t *taint_dev,
                        int64_t *index_dev, void *stream) {
-  if (!s) { g_serr = "ffe_sampler_sample: null handle"; return -1; }
-  if (!obs_dev || !act_dev || !ret_dev || !disc_dev || !next_obs_dev) { s->err = "ffe_sampler_sample: a null output (only taint_dev and index_dev may be NULL)"; return -1; }
-  if (taint_dev && !s->tracked) { s->err = "ffe_sampler_sample: taint_dev needs every writer created with validity tracking (ffe_nstep_create_tracked)"; return -1; }
-  ffe::DeviceGuard guard(s->device);
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  hipLaunchKernelGGL(ffs::sampler_prologue_kernel, dim3(1), dim3(64), 0, st, s->rings, s->n_rings, s->seed, s->min_size, (unsigned long long)s->batch, s->state,
-                     s->ctrl, s->info);
-  hipError_t e = hipGetLastError();
-  if (e == hipSuccess) {
-    const dim3 grid((s->batch + ffs::kRowsPerBlock - 1) / ffs::kRowsPerBlock), block(64 * ffs::kRowsPerBlock);
+  const char *who = "ffe_sampler_sample";
+  return ffe::on_handle(s, who, &g_serr, [&](ffe_sampler &S) {
+    need(obs_dev && act_dev && ret_dev && disc_dev && next_obs_dev, "ffe_sampler_sample: a null output (only taint_dev and index_dev may be NULL)");
+    need(!taint_dev || S.tracked, "ffe_sampler_sample: taint_dev needs every writer created with validity tracking (ffe_nstep_create_tracked)");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    hipLaunchKernelGGL(ffs::sampler_prologue_kernel, dim3(1), dim3(64), 0, st, S.rings, S.n_rings, S.seed, S.min_size, (unsigned long long)S.batch, S.state,
+                       S.ctrl, S.info);
+    ffe::launched(who);
+    const dim3 grid((S.batch + ffs::kRowsPerBlock - 1) / ffs::kRowsPerBlock), block(64 * ffs::kRowsPerBlock);
     long long *index = reinterpret_cast<long long *>(index_dev);
-    if (s->flags & FFE_SAMPLE_SKIP_TAINTED)
-      hipLaunchKernelGGL(ffs::sampler_gather_kernel<true>, grid, block, 0, st, s->rings, s->n_rings, s->ctrl, s->batch, s->obs_dim, s->act_dim, obs_dev, act_dev,
-                         ret_dev, disc_dev, next_obs_dev, taint_dev, index, s->info);
+    if (S.flags & FFE_SAMPLE_SKIP_TAINTED)
+      hipLaunchKernelGGL(ffs::sampler_gather_kernel<true>, grid, block, 0, st, S.rings, S.n_rings, S.ctrl, S.batch, S.obs_dim, S.act_dim, obs_dev, act_dev,
+                         ret_dev, disc_dev, next_obs_dev, taint_dev, index, S.info);
     else
-      hipLaunchKernelGGL(ffs::sampler_gather_kernel<false>, grid, block, 0, st, s->rings, s->n_rings, s->ctrl, s->batch, s->obs_dim, s->act_dim, obs_dev, act_dev,
-                         ret_dev, disc_dev, next_obs_dev, taint_dev, index, s->info);
-    e = hipGetLastError();
-  }
-  if (e != hipSuccess) { s->err = std::string("ffe_sampler_sample: ") + hipGetErrorString(e); return -2; }
-  return 0;
+      hipLaunchKernelGGL(ffs::sampler_gather_kernel<false>, grid, block, 0, st, S.rings, S.n_rings, S.ctrl, S.batch, S.obs_dim, S.act_dim, obs_dev, act_dev,
+                         ret_dev, disc_dev, next_obs_dev, taint_dev, index, S.info);
+    ffe::launched(who);
+  });
 }
 
 int ffe_sampler_info(ffe_sampler_handle s, long long **info_dev) {
-  if (!s) { g_serr = "ffe_sampler_info: null handle"; return -1; }
-  if (!info_dev) { s->err = "ffe_sampler_info: null info_dev"; return -1; }
-  *info_dev = s->info;
-  return 0;
+  return ffe::on_handle(s, "ffe_sampler_info", &g_serr, [&](ffe_sampler &S) {
+    need(info_dev, "ffe_sampler_info: null info_dev");
+    *info_dev = S.info;
+  });
 }
 
-int ffe_sampler_destroy(ffe_sampler_handle s) {
-  if (!s) { g_serr = "ffe_sampler_destroy: null handle"; return -1; }
-  ffe::DeviceGuard guard(s->device);
-  (void)hipFree(s->rings); (void)hipFree(s->ctrl); (void)hipFree(s->state); (void)hipFree(s->info);
-  delete s;
-  return 0;
-}
+int ffe_sampler_destroy(ffe_sampler_handle s) { return ffe::destroy(s, "ffe_sampler_destroy", &g_serr); }
 
 const char *ffe_sampler_last_error(ffe_sampler_handle s) { return s ? s->err.c_str() : g_serr.c_str(); }
 

@@ -7,7 +7,8 @@
 #include <memory>
 #include <string>
 
-#include "env_backend.hpp"
+#include "../../include/flybody_env.h"
+#include "handle.hpp"
 #include "walk_task.hpp"
 
 namespace wt {
@@ -59,129 +60,105 @@ struct ffe_walktask {
   wt::Packed<double> pd;
   wt::Tables<float> tf;
   wt::Tables<double> td;
-  void *arena = nullptr;
+  ffe::DeviceBuffers mem{"ffe_walktask_create"};  // the arena
   std::string err;
 };
 
-static thread_local std::string g_werr;
+static thread_local std::string g_werr;  // of ffe_walktask_create and of calls on a NULL handle
 
-namespace {
-int launched(ffe_walktask *h, const char *who) {
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) { h->err = std::string(who) + ": " + hipGetErrorString(e); return -2; }
-  return 0;
-}
-}  // namespace
+using ffe::need;
+using ffe::Refused;
 
 extern "C" {
 
 int ffe_walktask_create(const void *model_blob, size_t blob_size, const ffe_walk_task *task, int flags, int device, ffe_walktask_handle *out) {
-  if (!out) { g_werr = "ffe_walktask_create: a null required pointer (out)"; return -1; }
-  *out = nullptr;
-  auto fail = [&](const std::string &text) { g_werr = "ffe_walktask_create: " + text; return -1; };
-  if (flags & ~FFE_WALKTASK_FLOAT64) return fail("unknown flags " + std::to_string(flags));
-  std::unique_ptr<ffe_walktask> p(new ffe_walktask());
-  p->device = device; p->f64 = (flags & FFE_WALKTASK_FLOAT64) != 0;
-  std::string e;
-  const bool built = p->f64 ? p->pd.build(model_blob, blob_size, task, e) : p->pf.build(model_blob, blob_size, task, e);
-  if (!built) { g_werr = e; return -1; }
-  const int nbody = p->f64 ? p->pd.tab.nbody : p->pf.tab.nbody, njnt = p->f64 ? p->pd.tab.njnt : p->pf.tab.njnt;
-  if (nbody > wt::kMaxBody || njnt > wt::kMaxJnt)
-    return fail("the model has " + std::to_string(nbody) + " bodies and " + std::to_string(njnt) + " joints, above the kernels' capacity of " +
-                std::to_string(wt::kMaxBody) + " and " + std::to_string(wt::kMaxJnt));
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || device < 0 || device >= ndev) return fail("no such HIP device: the MI355X path has no CPU fallback");
-  ffe::DeviceGuard guard(device);
-  const std::vector<unsigned char> &arena = p->f64 ? p->pd.arena : p->pf.arena;
-  if (hipMalloc(&p->arena, arena.size()) != hipSuccess) return fail("out of device memory");
-  if (hipMemcpy(p->arena, arena.data(), arena.size(), hipMemcpyHostToDevice) != hipSuccess || hipDeviceSynchronize() != hipSuccess) {
-    (void)hipFree(p->arena);
-    return fail("the upload of the tables failed");
-  }
-  if (p->f64) p->td = p->pd.rebase(p->arena); else p->tf = p->pf.rebase(p->arena);
-  *out = p.release();
-  return 0;
+  return ffe::create(out, "ffe_walktask_create: a null required pointer (out)", g_werr, [&](ffe_walktask &p) {
+    auto must = [](bool ok, const std::string &text) { if (!ok) throw Refused("ffe_walktask_create: " + text); };
+    must(!(flags & ~FFE_WALKTASK_FLOAT64), "unknown flags " + std::to_string(flags));
+    p.device = device; p.f64 = (flags & FFE_WALKTASK_FLOAT64) != 0;
+    std::string e;
+    if (!(p.f64 ? p.pd.build(model_blob, blob_size, task, e) : p.pf.build(model_blob, blob_size, task, e))) throw Refused(e);
+    const int nbody = p.f64 ? p.pd.tab.nbody : p.pf.tab.nbody, njnt = p.f64 ? p.pd.tab.njnt : p.pf.tab.njnt;
+    must(nbody <= wt::kMaxBody && njnt <= wt::kMaxJnt, "the model has " + std::to_string(nbody) + " bodies and " + std::to_string(njnt) +
+                                                           " joints, above the kernels' capacity of " + std::to_string(wt::kMaxBody) + " and " + std::to_string(wt::kMaxJnt));
+    ffe::check_device(device, "ffe_walktask_create", true);
+    ffe::DeviceGuard guard(device);
+    const std::vector<unsigned char> &arena = p.f64 ? p.pd.arena : p.pf.arena;
+    unsigned char *dev = p.mem.zeroed<unsigned char>(arena.size());
+    must(hipMemcpy(dev, arena.data(), arena.size(), hipMemcpyHostToDevice) == hipSuccess && hipDeviceSynchronize() == hipSuccess, "the upload of the tables failed");
+    if (p.f64) p.td = p.pd.rebase(dev); else p.tf = p.pf.rebase(dev);
+  });
 }
 
 int ffe_walktask_features(ffe_walktask_handle h, const double *qpos_dev, const double *qvel_dev, int n, double *com_dev, void *qvel_out_dev,
                           void *root2site_dev, void *joint_quat_dev, void *stream) {
-  if (!h) { g_werr = "ffe_walktask_features: null handle"; return -1; }
-  if (!qpos_dev || (qvel_out_dev && !qvel_dev)) { h->err = "ffe_walktask_features: a null required pointer (qpos_dev; qvel_dev when qvel_out_dev is given)"; return -1; }
-  if (n < 0) { h->err = "ffe_walktask_features: n " + std::to_string(n) + " is negative"; return -1; }
-  if (n == 0) return 0;
-  ffe::DeviceGuard guard(h->device);
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  if (h->f64)
-    hipLaunchKernelGGL(wt::walk_features_kernel<double>, dim3(n), dim3(64), 0, s, h->td, qpos_dev, qvel_dev, com_dev, (double *)qvel_out_dev,
-                       (double *)root2site_dev, (double *)joint_quat_dev);
-  else
-    hipLaunchKernelGGL(wt::walk_features_kernel<float>, dim3(n), dim3(64), 0, s, h->tf, qpos_dev, qvel_dev, com_dev, (float *)qvel_out_dev,
-                       (float *)root2site_dev, (float *)joint_quat_dev);
-  return launched(h, "ffe_walktask_features");
+  return ffe::on_handle(h, "ffe_walktask_features", &g_werr, [&](ffe_walktask &p) {
+    need(qpos_dev && (!qvel_out_dev || qvel_dev), "ffe_walktask_features: a null required pointer (qpos_dev; qvel_dev when qvel_out_dev is given)");
+    if (n < 0) throw Refused("ffe_walktask_features: n " + std::to_string(n) + " is negative");
+    if (n == 0) return;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (p.f64)
+      hipLaunchKernelGGL(wt::walk_features_kernel<double>, dim3(n), dim3(64), 0, s, p.td, qpos_dev, qvel_dev, com_dev, (double *)qvel_out_dev,
+                         (double *)root2site_dev, (double *)joint_quat_dev);
+    else
+      hipLaunchKernelGGL(wt::walk_features_kernel<float>, dim3(n), dim3(64), 0, s, p.tf, qpos_dev, qvel_dev, com_dev, (float *)qvel_out_dev,
+                         (float *)root2site_dev, (float *)joint_quat_dev);
+    ffe::launched("ffe_walktask_features");
+  });
 }
 
 int ffe_walktask_evaluate(ffe_walktask_handle h, const double *qpos_dev, const double *qvel_dev, const int32_t *clip_dev, const int32_t *step_dev,
                           int n, void *factors_dev, void *reward_dev, int32_t *term_bits_dev, void *obs_dev, int obs_stride, void *stream) {
-  if (!h) { g_werr = "ffe_walktask_evaluate: null handle"; return -1; }
-  const int ntraj = h->f64 ? h->td.ntraj : h->tf.ntraj, obs_dim = h->f64 ? h->td.obs_dim : h->tf.obs_dim;
-  if (ntraj <= 0) { h->err = "ffe_walktask_evaluate: the handle was created without reference clips"; return -1; }
-  if (!qpos_dev || !qvel_dev || !clip_dev || !step_dev) { h->err = "ffe_walktask_evaluate: a null required pointer (qpos_dev, qvel_dev, clip_dev, step_dev)"; return -1; }
-  if (n < 0) { h->err = "ffe_walktask_evaluate: n " + std::to_string(n) + " is negative"; return -1; }
-  if (obs_dev && obs_stride < obs_dim) {
-    h->err = "ffe_walktask_evaluate: obs_stride " + std::to_string(obs_stride) + " is below the observation row of " + std::to_string(obs_dim);
-    return -1;
-  }
-  if (n == 0) return 0;
-  ffe::DeviceGuard guard(h->device);
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  if (h->f64)
-    hipLaunchKernelGGL(wt::walk_evaluate_kernel<double>, dim3(n), dim3(64), 0, s, h->td, qpos_dev, qvel_dev, clip_dev, step_dev, (double *)factors_dev,
-                       (double *)reward_dev, term_bits_dev, (double *)obs_dev, (long long)obs_stride);
-  else
-    hipLaunchKernelGGL(wt::walk_evaluate_kernel<float>, dim3(n), dim3(64), 0, s, h->tf, qpos_dev, qvel_dev, clip_dev, step_dev, (float *)factors_dev,
-                       (float *)reward_dev, term_bits_dev, (float *)obs_dev, (long long)obs_stride);
-  return launched(h, "ffe_walktask_evaluate");
+  return ffe::on_handle(h, "ffe_walktask_evaluate", &g_werr, [&](ffe_walktask &p) {
+    const int ntraj = p.f64 ? p.td.ntraj : p.tf.ntraj, obs_dim = p.f64 ? p.td.obs_dim : p.tf.obs_dim;
+    need(ntraj > 0, "ffe_walktask_evaluate: the handle was created without reference clips");
+    need(qpos_dev && qvel_dev && clip_dev && step_dev, "ffe_walktask_evaluate: a null required pointer (qpos_dev, qvel_dev, clip_dev, step_dev)");
+    if (n < 0) throw Refused("ffe_walktask_evaluate: n " + std::to_string(n) + " is negative");
+    if (obs_dev && obs_stride < obs_dim)
+      throw Refused("ffe_walktask_evaluate: obs_stride " + std::to_string(obs_stride) + " is below the observation row of " + std::to_string(obs_dim));
+    if (n == 0) return;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (p.f64)
+      hipLaunchKernelGGL(wt::walk_evaluate_kernel<double>, dim3(n), dim3(64), 0, s, p.td, qpos_dev, qvel_dev, clip_dev, step_dev, (double *)factors_dev,
+                         (double *)reward_dev, term_bits_dev, (double *)obs_dev, (long long)obs_stride);
+    else
+      hipLaunchKernelGGL(wt::walk_evaluate_kernel<float>, dim3(n), dim3(64), 0, s, p.tf, qpos_dev, qvel_dev, clip_dev, step_dev, (float *)factors_dev,
+                         (float *)reward_dev, term_bits_dev, (float *)obs_dev, (long long)obs_stride);
+    ffe::launched("ffe_walktask_evaluate");
+  });
 }
 
 int ffe_walktask_reference_pose(ffe_walktask_handle h, const int32_t *clip_dev, const int32_t *step_dev, int n, double *qpos_dev, double *qvel_dev,
                                 void *stream) {
-  if (!h) { g_werr = "ffe_walktask_reference_pose: null handle"; return -1; }
-  if ((h->f64 ? h->td.ntraj : h->tf.ntraj) <= 0) { h->err = "ffe_walktask_reference_pose: the handle was created without reference clips"; return -1; }
-  if (!clip_dev || !step_dev) { h->err = "ffe_walktask_reference_pose: a null required pointer (clip_dev, step_dev)"; return -1; }
-  if (n < 0) { h->err = "ffe_walktask_reference_pose: n " + std::to_string(n) + " is negative"; return -1; }
-  if (n == 0) return 0;
-  ffe::DeviceGuard guard(h->device);
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  if (h->f64)
-    hipLaunchKernelGGL(wt::walk_reference_pose_kernel<double>, dim3(n), dim3(64), 0, s, h->td, clip_dev, step_dev, qpos_dev, qvel_dev);
-  else
-    hipLaunchKernelGGL(wt::walk_reference_pose_kernel<float>, dim3(n), dim3(64), 0, s, h->tf, clip_dev, step_dev, qpos_dev, qvel_dev);
-  return launched(h, "ffe_walktask_reference_pose");
+  return ffe::on_handle(h, "ffe_walktask_reference_pose", &g_werr, [&](ffe_walktask &p) {
+    need((p.f64 ? p.td.ntraj : p.tf.ntraj) > 0, "ffe_walktask_reference_pose: the handle was created without reference clips");
+    need(clip_dev && step_dev, "ffe_walktask_reference_pose: a null required pointer (clip_dev, step_dev)");
+    if (n < 0) throw Refused("ffe_walktask_reference_pose: n " + std::to_string(n) + " is negative");
+    if (n == 0) return;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (p.f64)
+      hipLaunchKernelGGL(wt::walk_reference_pose_kernel<double>, dim3(n), dim3(64), 0, s, p.td, clip_dev, step_dev, qpos_dev, qvel_dev);
+    else
+      hipLaunchKernelGGL(wt::walk_reference_pose_kernel<float>, dim3(n), dim3(64), 0, s, p.tf, clip_dev, step_dev, qpos_dev, qvel_dev);
+    ffe::launched("ffe_walktask_reference_pose");
+  });
 }
 
 int ffe_walktask_info(ffe_walktask_handle h, int32_t *dims, int32_t *episode_steps) {
-  if (!h) { g_werr = "ffe_walktask_info: null handle"; return -1; }
-  if (!dims) { h->err = "ffe_walktask_info: a null required pointer (dims)"; return -1; }
-  auto fill = [&](const auto &t, const std::vector<int> &ep) {
-    const int v[16] = {t.nq, t.nv, t.J, t.S, t.ntraj, t.future, t.obs_dim, t.off_app, t.off_jpos, t.off_jvel, t.off_disp, t.off_rquat, t.off_zaxis,
-                       t.nappend, t.nobsj, h->f64 ? 1 : 0};
-    for (int k = 0; k < 16; k++) dims[k] = v[k];
-    if (episode_steps)
-      for (size_t c = 0; c < ep.size(); c++) episode_steps[c] = ep[c];
-  };
-  if (h->f64) fill(h->td, h->pd.ep_steps); else fill(h->tf, h->pf.ep_steps);
-  return 0;
+  return ffe::on_handle(h, "ffe_walktask_info", &g_werr, [&](ffe_walktask &p) {
+    need(dims, "ffe_walktask_info: a null required pointer (dims)");
+    auto fill = [&](const auto &t, const std::vector<int> &ep) {
+      const int v[16] = {t.nq, t.nv, t.J, t.S, t.ntraj, t.future, t.obs_dim, t.off_app, t.off_jpos, t.off_jvel, t.off_disp, t.off_rquat, t.off_zaxis,
+                         t.nappend, t.nobsj, p.f64 ? 1 : 0};
+      for (int k = 0; k < 16; k++) dims[k] = v[k];
+      if (episode_steps)
+        for (size_t c = 0; c < ep.size(); c++) episode_steps[c] = ep[c];
+    };
+    if (p.f64) fill(p.td, p.pd.ep_steps); else fill(p.tf, p.pf.ep_steps);
+  });
 }
 
-int ffe_walktask_destroy(ffe_walktask_handle h) {
-  if (!h) { g_werr = "ffe_walktask_destroy: null handle"; return -1; }
-  {
-    ffe::DeviceGuard guard(h->device);
-    (void)hipFree(h->arena);
-  }
-  delete h;
-  return 0;
-}
+int ffe_walktask_destroy(ffe_walktask_handle h) { return ffe::destroy(h, "ffe_walktask_destroy", &g_werr); }
 
 const char *ffe_walktask_last_error(ffe_walktask_handle h) { return h ? h->err.c_str() : g_werr.c_str(); }
 

@@ -77,9 +77,11 @@ def obs_layout(dims) -> dict:
             "ref_displacement": (dims[10], 3 * F1), "ref_root_quat": (dims[11], 4 * F1), "world_zaxis": (dims[12], 3)}
 
 
-class WalkTracker:
+class WalkTracker(_capi.LibHandle):
     """Scores batches of device-resident states against reference clips.  `refs`: a `WalkRefSet` (None: `features` only);
     `dtype` "float32" (the product path) or "float64" (featurisation); tensors go in and come out on `cuda:device`."""
+
+    _destroy, _last_error = "ffe_walktask_destroy", "ffe_walktask_last_error"
 
     def __init__(self, refs, view: WalkModelView | None = None, *, joints=None, sites=None, future_steps=64, terminal_com_dist=0.3,
                  time_limit=10.0, control_timestep=2e-3, weights=(20, 1, 1, 1), std=None, inference_mode=False, dtype="float32", device=0,
@@ -100,10 +102,7 @@ class WalkTracker:
         with open(blob_path, "rb") as f:
             blob = f.read()
         h = C.c_void_p()
-        self._h = None
-        rc = self._L.ffe_walktask_create(blob, len(blob), C.byref(task), int(dtype == "float64"), device, C.byref(h))
-        if rc != 0:
-            raise RuntimeError(self._L.ffe_walktask_last_error(None).decode())
+        self._check(self._L.ffe_walktask_create(blob, len(blob), C.byref(task), int(dtype == "float64"), device, C.byref(h)), None)
         self._h = h
         dims = (C.c_int32 * 16)()
         ep = (C.c_int32 * max(1, task.ntraj))()
@@ -114,10 +113,6 @@ class WalkTracker:
         self.obs_layout = obs_layout(self.dims)
 
     # ---------------------------------------------------------------------------------------------- plumbing
-    def _check(self, rc):
-        if rc != 0:
-            raise RuntimeError(self._L.ffe_walktask_last_error(self._h).decode())
-
     def _stream(self):
         return C.c_void_p(self._torch.cuda.current_stream(self.device).cuda_stream)
 
@@ -179,13 +174,6 @@ class WalkTracker:
         return out
 
     def close(self):
-        if self._h is not None:
+        if self._h:
             self._torch.cuda.synchronize(self.device)
-            self._L.ffe_walktask_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:  # noqa: BLE001
-            pass
+        super().close()

@@ -29,6 +29,15 @@
  *       checks of ffe_step / ffe_reset ("walk_on_ball: null output buffer" / "null action buffer").
  *   Since the calls moved into csrc/capi.hip every -1 / -2 on a non-NULL handle sets ffe_last_error(h) (NULL-argument -1s and some
  *   -2 paths used to leave it stale), and a HIP failure inside a flight handle's ffe_force_next_episode is -2 (it was -1).
+ *
+ * The other four handle families (ffe_nstep_*, ffe_sampler_*, ffe_eplog_*, ffe_walktask_*) use the same codes through the same layer
+ * (csrc/handle.hpp): -1 refused with a text, -2 a launch or HIP call failed ("<function>: <hipGetErrorString>"), the text in the
+ * family's last_error(h); a create function's text and "<function>: null handle" for a call on a NULL handle are in last_error(NULL).
+ * Since the families moved onto that layer their return codes and texts are as before, with these additions to ffe_nstep_*, which
+ * used to leave ffe_nstep_last_error stale or empty there: a NULL handle ("ffe_nstep_observe: null handle"), a NULL argument
+ * ("ffe_nstep_create: null out", "ffe_nstep_observe: a null input", "ffe_nstep_taint_buffer: null taint") have a text; the -2 text
+ * starts with the function's name; the device refusal reads "ffe_nstep_create: no such HIP device: ..." (it had no prefix).
+ * ffe_pack_timestep, ffe_episode_stats and ffe_validity_stats have no handle and no text: -1 bad arguments, -2 launch refused.
  */
 #ifndef FLYBODY_ENV_H_
 #define FLYBODY_ENV_H_

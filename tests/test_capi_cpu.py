@@ -113,13 +113,29 @@ def test_env_entry_points_live_in_capi_hip():
 def test_python_handles_share_one_base():
     import inspect
 
+    from flybody_amd._capi import LibHandle
     from flybody_amd.batched_env import BatchedBallEnv, BatchedFlyEnv, BatchedWalkPhysics, EnvHandle
 
     assert inspect.getmro(BatchedFlyEnv)[1] is EnvHandle and inspect.getmro(BatchedWalkPhysics)[1] is EnvHandle
-    assert inspect.getmro(BatchedBallEnv)[1] is BatchedFlyEnv
-    for name in ("_check", "_stream", "close", "__del__", "raw_action_bounds", "get_state", "set_state", "physics_step", "get_task_state",
-                 "get_act", "set_act"):
-        owners = [c for c in (EnvHandle, BatchedFlyEnv, BatchedBallEnv, BatchedWalkPhysics) if name in vars(c)]
-        assert owners == [EnvHandle], (name, owners)
+    assert inspect.getmro(BatchedBallEnv)[1] is BatchedFlyEnv and inspect.getmro(EnvHandle)[1] is LibHandle
+    owns_handle = ("_check", "close", "__del__")  # what every handle family shares, envs or not
+    for name in owns_handle + ("_stream", "raw_action_bounds", "get_state", "set_state", "physics_step", "get_task_state", "get_act", "set_act"):
+        owners = [c for c in (LibHandle, EnvHandle, BatchedFlyEnv, BatchedBallEnv, BatchedWalkPhysics) if name in vars(c)]
+        assert owners == [LibHandle if name in owns_handle else EnvHandle], (name, owners)
         assert getattr(BatchedWalkPhysics, name) is getattr(BatchedFlyEnv, name) is getattr(BatchedBallEnv, name)
     assert (BatchedFlyEnv.task_kind, BatchedBallEnv.task_kind, BatchedWalkPhysics.task_kind) == ("flight_imitation", "walk_on_ball", "walk_physics")
+
+
+def test_every_handle_family_shares_the_owning_base():
+    """`close`, `__del__` and `_check` exist once, in `_capi.LibHandle`; a family may extend `close` (the tracker synchronises first, the
+    log drops its views) and names its own destroy / last_error symbols, which the library exports."""
+    from flybody_amd import _capi
+    from flybody_amd.actor_loop import EpisodeLog, NStepTransitionWriter, ReplaySampler
+    from flybody_amd.batched_env import EnvHandle
+    from flybody_amd.tasks.walk_tracker import WalkTracker
+
+    for cls in (NStepTransitionWriter, ReplaySampler, EpisodeLog, WalkTracker, EnvHandle):
+        assert issubclass(cls, _capi.LibHandle)
+        assert "__del__" not in vars(cls) and "_check" not in vars(cls), cls
+        assert cls._destroy in _capi.SYMBOLS and cls._last_error in _capi.SYMBOLS, cls
+    assert [c.__name__ for c in (NStepTransitionWriter, ReplaySampler, EpisodeLog, WalkTracker, EnvHandle) if "close" in vars(c)] == ["EpisodeLog", "WalkTracker"]
