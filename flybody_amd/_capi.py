@@ -43,10 +43,6 @@ class BallTask(C.Structure):
                 ("physics_flags", C.c_int32), ("canonical_actions", C.c_int32), ("clip_actions", C.c_int32)]
 
 
-class WalkPhysicsTask(C.Structure):
-    _fields_ = [("physics_flags", C.c_int32)]
-
-
 class WalkTask(C.Structure):
     _fields_ = [
         ("n_joints", C.c_int32), ("joints", C.POINTER(C.c_int32)), ("n_sites", C.c_int32), ("sites", C.POINTER(C.c_int32)),
@@ -57,6 +53,12 @@ class WalkTask(C.Structure):
         ("n_overrides", C.c_int32), ("override_qadr", C.POINTER(C.c_int32)), ("override_val", C.POINTER(C.c_double)),
         ("inference_mode", C.c_int32),
     ]
+
+
+class WalkPhysicsTask(C.Structure):
+    """Everything behind `physics_flags` is read only with FFE_WALK_EPISODES (zeros otherwise)."""
+    _fields_ = [("physics_flags", C.c_int32), ("task", C.POINTER(WalkTask)), ("seed", C.c_uint64), ("env_id_base", C.c_uint64),
+                ("time_limit_steps", C.c_int32), ("pad_first_obs", C.c_int32), ("canonical_actions", C.c_int32), ("clip_actions", C.c_int32)]
 
 
 class Spec(C.Structure):

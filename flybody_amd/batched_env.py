@@ -25,6 +25,7 @@ BALL_BLOB = os.path.join(_ASSETS, "fly_ball.ffmb")
 WALK_BLOB = os.path.join(_ASSETS, "fly_walk.ffmb")
 FFE_NO_LIMIT, FFE_NO_CONTACT = 2, 64  # include/flybody_env.h
 FFE_WALK_JOINT_LIMITS = 512  # ffe_create_walk_physics only: joint limits on (provisional opt-in, see the header)
+FFE_WALK_EPISODES = 1024  # ffe_create_walk_physics only: the walk_imitation environment with the floor off (provisional opt-in)
 
 
 # `env.validity()`: four int32 [B] views of one [B, 4] device buffer (include/flybody_env.h, ffe_get_validity)
@@ -383,11 +384,78 @@ class BatchedBallEnv(BatchedFlyEnv):
         raise NotImplementedError("walk_on_ball has no reference trajectories")
 
 
+class BatchedWalkEnv(BatchedFlyEnv):
+    """B independent `walk_imitation` environments (`fly_envs.py:75-122`) on one MI355X **with the floor off**: the free-root walking
+    fly (10 physics substeps with joint limits and filtered actuators per control step), the thorax IMU, the DeepMimic reward against
+    a reference clip, termination and auto-reset, all on the device.  Without floor contacts the fly falls freely (or floats with
+    FFE_NO_GRAVITY in `physics_flags`); force and touch read zero.  The float64 oracle does the same with contacts switched off, so
+    every row can be compared with it.  Same dm_env surface and hooks as `BatchedBallEnv`; one `step()` is five launches (DESIGN.md
+    section 12, step 4b).
+
+    `refs`: a `tasks.walking.WalkRefSet`; `view`: the `WalkModelView` that names the tracked joints and sites (None: the default
+    one).  `get_state` / `set_state` / `get_act` / `set_act` / `physics_step` are `BatchedWalkPhysics`'s."""
+
+    task_kind = "walk_imitation"
+
+    def __init__(self, refs, view=None, *, batch_size: int, device: int = 0, seed: int = 0, env_id_base: int = 0, future_steps: int = 64,
+                 time_limit: float = 10.0, terminal_com_dist: float = 0.3, control_timestep: float = 2e-3, pad_first_obs: bool = False,
+                 physics_flags: int = 0, canonical_actions: bool = False, clip_actions: bool = False, double_buffer: bool = False,
+                 inference_mode: bool = False, blob_path: str = WALK_BLOB):
+        import json
+
+        from .model.blob import read_blob
+        from .tasks.walk_tracker import make_task
+        from .tasks.walking import WalkModelView
+
+        self._open(batch_size, device)
+        with open(blob_path, "rb") as f:
+            blob = f.read()
+        with open(os.path.splitext(blob_path)[0] + ".json") as f:
+            self._meta = json.load(f)
+        self.view = view = view or WalkModelView()
+        self.refs = refs
+        h_phys = float(read_blob(blob_path)["opt"][0])
+        nsub = int(round(control_timestep / h_phys))
+        wtask, self._keep = make_task(view, refs, future_steps=future_steps, terminal_com_dist=terminal_com_dist, time_limit=time_limit,
+                                      control_timestep=control_timestep, inference_mode=inference_mode)
+        force_switches = int(physics_flags) & (1 | 4 | 8 | 16 | 32)  # FFE_NO_FLUID / _DAMPER / _SPRING / _GRAVITY / _ACTUATION
+        if int(physics_flags) & ~(force_switches | FFE_NO_CONTACT | FFE_WALK_JOINT_LIMITS | FFE_WALK_EPISODES):
+            raise ValueError("BatchedWalkEnv: physics_flags takes the force switches only (floor contacts are not built; joint limits are on)")
+        self.physics_flags = force_switches | FFE_NO_CONTACT | FFE_WALK_JOINT_LIMITS | FFE_WALK_EPISODES
+        task = _capi.WalkPhysicsTask(physics_flags=self.physics_flags, task=C.pointer(wtask), seed=int(seed), env_id_base=int(env_id_base),
+                                     time_limit_steps=time_limit_control_steps(time_limit, h_phys, nsub), pad_first_obs=int(pad_first_obs),
+                                     canonical_actions=int(canonical_actions), clip_actions=int(clip_actions))
+        self.time_limit_steps = int(task.time_limit_steps)
+        h = C.c_void_p()
+        rc = self._L.ffe_create_walk_physics(blob, len(blob), C.byref(task), self.batch_size, device, C.byref(h))
+        self._adopt("ffe_create_walk_physics", rc, h)
+        self.canonical_actions = bool(canonical_actions)
+        s = self.spec
+        self._alloc_outputs(double_buffer)
+        F1 = s.n_ref
+        self._layout = collections.OrderedDict()
+        off = 0
+        for name, shape in (("accelerometer", (3,)), ("actuator_activation", (s.nu,)), ("appendages_pos", (s.off_gyro - 18 - 3 - s.nu,)),
+                            ("force", (18,)), ("gyro", (3,)), ("joints_pos", (s.n_obs_joints,)), ("joints_vel", (s.n_obs_joints,)),
+                            ("ref_displacement", (F1, 3)), ("ref_root_quat", (F1, 4)), ("touch", (6,)), ("velocimeter", (3,)),
+                            ("world_zaxis", (3,))):
+            self._layout["walker/" + name] = (off, shape)
+            off += int(np.prod(shape))
+        assert off == s.obs_dim and self._layout["walker/gyro"][0] == s.off_gyro and self._layout["walker/velocimeter"][0] == s.off_velocimeter
+        assert self._layout["walker/ref_root_quat"][0] == s.off_ref_root_quat and self._layout["walker/world_zaxis"][0] == s.off_world_zaxis
+
+    def set_next_trajectory_index(self, idx, phase=0.0):
+        """`WalkImitation.set_next_trajectory_index` (`walk_imitation.py:84-87`) per env: the clip of each env's next reset (negative: the
+        counter-based draw).  walk_imitation draws no phase; the argument is accepted for the base class's signature and ignored."""
+        super().set_next_trajectory_index(idx, 0.0)
+
+
 class BatchedWalkPhysics(EnvHandle):
     """B walking flies (`assets/fly_walk.ffmb`: free thorax, 6 + 102 dofs, 59 filtered actuators) advanced on one MI355X by
     `ffe_physics_step`: the smooth dynamics of `walk_imitation` with constraints off or, with
     `joint_limits=True`, with the joint limits of the 102 hinges on (step 3a).  Not an environment: there is no reset, step, observation
-    or reward - floor contacts, sensors and the episode protocol are not built yet.  The handle starts at the model's `qpos0` at rest.
+    or reward (`BatchedWalkEnv` is the environment around the same physics; floor contacts are not built yet).  The handle starts at
+    the model's `qpos0` at rest.
 
     `physics_flags` must contain FFE_NO_CONTACT and exactly one of FFE_NO_LIMIT (the default) or FFE_WALK_JOINT_LIMITS;
     `joint_limits=True` sets FFE_NO_CONTACT | FFE_WALK_JOINT_LIMITS plus whatever force switches (FFE_NO_FLUID, ...) `physics_flags`

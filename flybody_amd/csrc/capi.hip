@@ -67,7 +67,7 @@ int ffe_create_walk_on_ball(const void *model_blob, size_t blob_size, const ffe_
 }
 int ffe_create_walk_physics(const void *model_blob, size_t blob_size, const ffe_walk_physics_task *task, int batch, int device, ffe_handle *out) {
   return create("ffe_create_walk_physics", task != nullptr, device, out,
-                [&] { return ffw::walk_create(model_blob, blob_size, task->physics_flags, batch, device); });
+                [&] { return ffw::walk_create(model_blob, blob_size, *task, batch, device); });
 }
 
 int ffe_destroy(ffe_handle h) { return ffe::destroy(h, "", nullptr); }

@@ -13,8 +13,8 @@
 // solution with it is the solution without it plus (0, R' g) on the root alone.  It is added there, in the world frame, after the
 // solve: free fall is exact, and no gravity torque about the root origin is rounded in float32 and divided by the small rotational
 // inertias of S (which cost 2e-3 rad/s^2 of root angular acceleration when gravity went through the solve).
-// Collision, contact rows, sensors, observation, reward and reset are not compiled in: only bare physics (`ffe_physics_step`) exists.
-// Two kernels share the code below.  `walk_step_kernel` is the smooth dynamics alone (a handle created with FFE_NO_CONTACT |
+// Collision and contact rows are not compiled in.  Three kernels share the code below: two of bare physics (`ffe_physics_step`) and
+// the walk_imitation environment with the floor off (`imitation_step_kernel`, at the end of the kernel section).  `walk_step_kernel` is the smooth dynamics alone (a handle created with FFE_NO_CONTACT |
 // FFE_NO_LIMIT).  `walk_limits_kernel` (FFE_NO_CONTACT | FFE_WALK_JOINT_LIMITS) adds the joint-limit
 // rows and the constraint solve on the arrowhead matrix between the smooth forces and the Euler solve of stage 2:
 //   rows     mj_instantiateLimit with margin 0 (sign, D, aref per hinge slot), compacted by ballots in (slot, lane) order, at most RMAX;
@@ -27,18 +27,21 @@
 //   forces   qfrc_constraint = s f on the hinge right-hand side of the Euler solve; the root's is unchanged (J_r = 0): the root
 //            feels a limit through M_rj alone.
 // A substep that instantiates no row skips all of it by a wave-uniform branch.
-// Parity tests: tests/test_gpu_walk_physics.py, tests/test_gpu_walk_limits.py.
+// Parity tests: tests/test_gpu_walk_physics.py, tests/test_gpu_walk_limits.py, tests/test_gpu_walk_episode.py.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
 #include <memory>
 #include <stdexcept>
 #include <string>
+#include <type_traits>
+#include <vector>
 
 #include "walk_env.hpp"
 #include "walk_model.hpp"
 #include "leg_dyn.hpp"
 #include "row_newton.hpp"
+#include "walk_imu.hpp"
 
 namespace ffw {
 using namespace dm;
@@ -58,7 +61,8 @@ struct alignas(16) WState {
 static_assert(sizeof(WState) == 1168, "the four ints fill what used to be padding");
 
 constexpr int BF_WALK_JOINT_LIMITS = 512;  // FFE_WALK_JOINT_LIMITS: host side only, the kernels do not read it
-constexpr int LCOL = 16;                   // solve columns per block of M: a block has at most NSTEP = 14 hinges, each with one limit row
+constexpr int BF_WALK_EPISODES = 1024;     // FFE_WALK_EPISODES: host side only
+constexpr int LCOL = 16;                  // solve columns per block of M: a block has at most NSTEP = 14 hinges, each with one limit row
 static_assert(NSTEP <= LCOL, "a block's limit rows must fit its columns");
 
 struct alignas(16) WTile {
@@ -104,6 +108,33 @@ struct alignas(16) WTileL {
   unsigned char r_dof[RMAX], r_blk[RMAX], r_col[RMAX], rowof[NBLK][LCOL];
 };
 static_assert(sizeof(WTileL) <= 20480, "the tile must leave room for 8 waves per CU");
+
+// Tile of the episode kernel: the limits kernel's, plus the sensor sums of a control step (accelerometer 3, gyro 3, velocimeter 3,
+// force 18, touch 6: the order of the oracle's buffer)
+struct alignas(16) WTileE : WTileL {
+  float sens[36];
+  float qsave[3][64];  // the hinges' right-hand side, parked while the qacc solve runs (three fewer live registers per lane there)
+};
+static_assert(sizeof(WTileE) <= 20480, "the tile must leave room for 8 waves per CU");
+
+// What the episode kernel reads besides the model and the state: fixed at create, in device memory, fetched by scalar loads where it
+// is used (as kernel arguments its thirty dwords stayed in SGPRs over the whole substep loop and spilled into VGPR lanes).
+struct ImitArgs {
+  const double *pose;    // [B][109] qpos of ffe_walktask_reference_pose(clip, 0): what a reset row starts from
+  const int *flag;       // [B] 0 = step, 1 = reset, 2 = leave the env alone (ffe_reset_envs, mask byte 0)
+  double *qpos, *qvel;   // [B][109], [B][108] in the ffe_get_state layout, for the task layer
+  float *term;           // [B][4]: |velocimeter|, |gyro| and sum qacc^2 of the last substep (not the means), 0
+  int obs_dim, off_act, off_force, off_gyro, off_touch, off_velocimeter;  // (the accelerometer heads the row)
+  int canonical, clip, pad_first_obs;
+  float site_pos[3], site_quat[4];  // the IMU site in the root frame
+};
+// ... and what changes from call to call
+struct ImitCall {
+  const ImitArgs *a;
+  const float *action;   // [B][NACT] raw (or canonical) actions; not read by a reset row
+  float *obs;            // [B][obs_dim]: the 92 physics columns are written here
+};
+struct NoEpisode {};  // the bare-physics kernels: no episode code is compiled
 
 template <class Tile>
 struct CtxT {
@@ -340,8 +371,12 @@ __device__ __forceinline__ int limit_forces(C &c, const int R, const int (&lrow)
 }
 
 // ------------------------------------------------------------------------------------------------ stage 2
-template <bool LIMITS, class C>
-__device__ __forceinline__ void stage2(C &c, float act_reg, float ctrl_reg, float &act_out, int &nlim_out, int &iters_out) {
+// EP (the episode kernel): also mj's qacc = M^-1 (qfrc_smooth + qfrc_constraint) through M's own factor - the Euler solve below is
+// implicit in the joint damping, so its solution is not qacc - for the accelerometer of this substep (`acc`, from the state before the
+// integration) and for sum qacc^2 (`qn2`); `integrate` false stops there (mj_forward of a reset: nothing is advanced).
+template <bool LIMITS, bool EP = false, class C>
+__device__ __forceinline__ void stage2(C &c, float act_reg, float ctrl_reg, float &act_out, int &nlim_out, int &iters_out,
+                                       const ImitArgs *ep = nullptr, bool integrate = true, float *acc = nullptr, float *qn2 = nullptr) {
   auto &T = *c.T;
   const BallModel FFE_GLOBAL &M = model(c);
   const int lane = c.lane;
@@ -433,6 +468,57 @@ __device__ __forceinline__ void stage2(C &c, float act_reg, float ctrl_reg, floa
       for (int s = 0; s < 3; s++) mrj[s] = slot_on(c, s) ? ld6(T.F[opq(c.sdof[s])]) : zero6();
     }
   }
+  if constexpr (EP) {
+    S6 ym[3];
+    float zm[3];
+#pragma unroll
+    for (int s = 0; s < 3; s++) T.qsave[s][lane] = qs[s];
+#pragma unroll
+    for (int s = 0; s < 3; s++) if (slot_on(c, s)) T.X4[opq(c.sdof[s])] = make_float4(qs[s], mrj[s].a0, mrj[s].a1, mrj[s].a2);
+    DM_SYNC();
+    solve4(c, T.Lm, T.dinv_m);
+#pragma unroll
+    for (int s = 0; s < 3; s++) {
+      const float4 x = slot_on(c, s) ? T.X4[opq(c.sdof[s])] : make_float4(0.f, 0.f, 0.f, 0.f);
+      zm[s] = x.x; ym[s].a0 = x.y; ym[s].a1 = x.z; ym[s].a2 = x.w;
+    }
+    DM_SYNC();
+#pragma unroll
+    for (int s = 0; s < 3; s++) if (slot_on(c, s)) T.X4[opq(c.sdof[s])] = make_float4(mrj[s].l0, mrj[s].l1, mrj[s].l2, 0.f);
+    DM_SYNC();
+    solve4(c, T.Lm, T.dinv_m);
+#pragma unroll
+    for (int s = 0; s < 3; s++) {
+      const float4 x = slot_on(c, s) ? T.X4[opq(c.sdof[s])] : make_float4(0.f, 0.f, 0.f, 0.f);
+      ym[s].l0 = x.x; ym[s].l1 = x.y; ym[s].l2 = x.z;
+    }
+    DM_SYNC();
+    float Sm[6][6], br[6], id[6], xr[6];
+    schur(c, mrj, ym, zm, Sm, br);
+    chol6(Sm, id);
+    chol6_forward(Sm, id, br, xr);
+    chol6_backward(Sm, id, xr);
+    float sq = 0.f;
+#pragma unroll
+    for (int s = 0; s < 3; s++) {
+      if (slot_on(c, s)) {
+        float a = zm[s];
+#pragma unroll
+        for (int k = 0; k < 6; k++) a -= comp(ym[s], k) * xr[k];
+        sq += a * a;
+      }
+    }
+    const M3 R = q2m(c.rq);
+    const bool grav = !(c.flags & BF_NO_GRAVITY);
+    V3 aw = mv(R, V3{xr[3], xr[4], xr[5]} + cross(ang(c.V0), lin(c.V0)));
+    if (grav) aw.z += M.gz;
+    *qn2 = wave_sum(sq) + dot(aw, aw) + xr[0] * xr[0] + xr[1] * xr[1] + xr[2] * xr[2];
+    const float qr[4] = {c.rq.w, c.rq.x, c.rq.y, c.rq.z}, wb[3] = {c.wb.x, c.wb.y, c.wb.z}, al[3] = {aw.x, aw.y, aw.z}, wd[3] = {xr[0], xr[1], xr[2]};
+    wi::imu_acceleration<float>(qr, wb, al, wd, grav ? M.gz : 0.f, ep->site_pos, ep->site_quat, acc);
+    if (!integrate) { act_out = act_reg; return; }
+#pragma unroll
+    for (int s = 0; s < 3; s++) { qs[s] = T.qsave[s][lane]; mrj[s] = slot_on(c, s) ? ld6(T.F[opq(c.sdof[s])]) : zero6(); }
+  }
 #pragma unroll
   for (int s = 0; s < 3; s++) if (slot_on(c, s)) T.X4[opq(c.sdof[s])] = make_float4(qs[s], mrj[s].a0, mrj[s].a1, mrj[s].a2);
   DM_SYNC();
@@ -491,9 +577,25 @@ __device__ __forceinline__ void stage2(C &c, float act_reg, float ctrl_reg, floa
 }
 
 // ------------------------------------------------------------------------------------------------ kernels
-template <bool LIMITS, class Tile>
+// the state in the ffe_get_state layout, from the registers of the wave that holds it
+template <class C>
+__device__ __forceinline__ void export_state(const C &c, double *__restrict__ qp, double *__restrict__ qv) {
+#pragma unroll
+  for (int s = 0; s < 3; s++) if (slot_on(c, s)) { qp[7 + c.sdof[s]] = (double)c.q[s]; qv[6 + c.sdof[s]] = (double)c.v[s]; }
+  if (c.lane == 0) {
+    qp[0] = c.pos[0]; qp[1] = c.pos[1]; qp[2] = c.pos[2];
+    qp[3] = (double)c.rq.w; qp[4] = (double)c.rq.x; qp[5] = (double)c.rq.y; qp[6] = (double)c.rq.z;
+    qv[0] = (double)c.vw.x; qv[1] = (double)c.vw.y; qv[2] = (double)c.vw.z;
+    qv[3] = (double)c.wb.x; qv[4] = (double)c.wb.y; qv[5] = (double)c.wb.z;
+  }
+}
+
+// `ep` (the episode kernel alone, `Ep` = ImitCall): one control step of the env, or its reset, in place of `nphys` bare substeps - see
+// imitation_step_kernel below.  With `Ep` = NoEpisode none of it is compiled.
+template <bool LIMITS, class Tile, class Ep = NoEpisode>
 __device__ __forceinline__ void walk_substeps(Tile &T, const WalkModel *__restrict__ Wp, int flags, WState *__restrict__ states,
-                                              const float *__restrict__ ctrl, int nphys) {
+                                              const float *__restrict__ ctrl, int nphys, const Ep &ep = Ep()) {
+  constexpr bool EP = !std::is_same<Ep, NoEpisode>::value;
   const int env = blockIdx.x, lane = threadIdx.x;
   const BallModel &M = Wp->b;
   WState &S = states[env];
@@ -508,13 +610,63 @@ __device__ __forceinline__ void walk_substeps(Tile &T, const WalkModel *__restri
   c.vw = {S.vlin[0], S.vlin[1], S.vlin[2]}; c.wb = {S.wb[0], S.wb[1], S.wb[2]};
   c.pos[0] = S.pos[0]; c.pos[1] = S.pos[1]; c.pos[2] = S.pos[2];
   float act_reg = lane < NU ? S.act[lane] : 0.f;
-  const float ctrl_reg = lane < NU ? ctrl[(size_t)env * NU + lane] : 0.f;
+  float ctrl_reg = 0.f;
+  int row = 0;  // episode kernel: 0 step, 1 reset
+  if constexpr (EP) {
+    row = ep.a->flag[env];
+    if (row == 2) {  // not this call's env: the task layer still reads its state
+      export_state(c, ep.a->qpos + (size_t)env * 109, ep.a->qvel + (size_t)env * 108);
+      return;
+    }
+    if (row == 1) {
+      // mj: walk_imitation.py:112-121 initialize_episode: the pose of row 0 of the clip (qpos0, root, tracked joints, retracted wings),
+      // zero velocity, activation and ctrl; rounded to float32 as ffe_set_state rounds it
+      const double *qp = ep.a->pose + (size_t)env * 109;
+#pragma unroll
+      for (int s = 0; s < 3; s++) { c.q[s] = slot_on(c, s) ? (float)qp[7 + c.sdof[s]] : 0.f; c.v[s] = 0.f; }
+      c.rq = qnormalize(Q4{(float)qp[3], (float)qp[4], (float)qp[5], (float)qp[6]});
+      c.vw = {0.f, 0.f, 0.f}; c.wb = {0.f, 0.f, 0.f};
+      c.pos[0] = qp[0]; c.pos[1] = qp[1]; c.pos[2] = qp[2];
+      act_reg = 0.f;
+      c.flags |= BF_NO_ACTUATION;  // dm_control's after_reset: mj_forward with actuation disabled
+    } else if (lane < NU) {
+      // ref: fruitfly.py:480-492 apply_action (+ the CanonicalSpecWrapper the reference wraps every env in), as ball_env.hip
+      const int ai = M.a_action[lane];
+      float av = ai >= 0 ? ep.action[(size_t)env * NACT + ai] : 0.f;
+      if (!(av == av)) av = 0.f;
+      if (ep.a->canonical && ai >= 0) {
+        if (ep.a->clip) av = fminf(fmaxf(av, -1.f), 1.f);
+        av = M.act_lo[ai] + 0.5f * (av + 1.f) * (M.act_hi[ai] - M.act_lo[ai]);
+      }
+      ctrl_reg = av;
+    }
+    nphys = row == 1 ? 1 : M.nsub;
+    if (lane < 36) T.sens[lane] = 0.f;  // (the sums are cleared at substep 0)
+    DM_SYNC();
+  } else {
+    ctrl_reg = lane < NU ? ctrl[(size_t)env * NU + lane] : 0.f;
+  }
   int nlim = 0, iters = 0;
+  float qn2 = 0.f;
 #pragma unroll 1
   for (int s = 0; s < nphys; s++) {
     stage1(c);
     float act_new;
-    stage2<LIMITS>(c, act_reg, ctrl_reg, act_new, nlim, iters);
+    if constexpr (EP) {
+      // dm_control runs mj_step2 ; mj_step1 and samples: the accelerometer is the acceleration stage's (the state before the
+      // integration, this substep's qacc), gyro and velocimeter belong to the state after it.  Force and touch stay zero: no contacts.
+      float acc[3], gy[3], ve[3];
+      stage2<LIMITS, true>(c, act_reg, ctrl_reg, act_new, nlim, iters, ep.a, row == 0, acc, &qn2);
+      const float qr[4] = {c.rq.w, c.rq.x, c.rq.y, c.rq.z}, vl[3] = {c.vw.x, c.vw.y, c.vw.z}, wb[3] = {c.wb.x, c.wb.y, c.wb.z};
+      wi::imu_velocity<float>(qr, vl, wb, ep.a->site_pos, ep.a->site_quat, gy, ve);
+      if (lane < 3) {
+        T.sens[lane] += lane == 0 ? acc[0] : (lane == 1 ? acc[1] : acc[2]);
+        T.sens[3 + lane] += lane == 0 ? gy[0] : (lane == 1 ? gy[1] : gy[2]);
+        T.sens[6 + lane] += lane == 0 ? ve[0] : (lane == 1 ? ve[1] : ve[2]);
+      }
+    } else {
+      stage2<LIMITS>(c, act_reg, ctrl_reg, act_new, nlim, iters);
+    }
     act_reg = act_new;
   }
 #pragma unroll
@@ -526,6 +678,31 @@ __device__ __forceinline__ void walk_substeps(Tile &T, const WalkModel *__restri
     S.wb[0] = c.wb.x; S.wb[1] = c.wb.y; S.wb[2] = c.wb.z;
     S.pos[0] = c.pos[0]; S.pos[1] = c.pos[1]; S.pos[2] = c.pos[2];
     if constexpr (LIMITS) { S.nlim = nlim; S.iters = iters; S.step_bits = c.overflow; }
+  }
+  if constexpr (EP) {
+    // ---- the 92 physics columns of the observation row (the task layer writes the kinematic ones), the state for the task layer, and
+    //      what check_termination reads of the last substep
+    DM_SYNC();
+    float *ob = ep.obs + (size_t)env * (size_t)ep.a->obs_dim;
+    const float inv = (row == 1 && ep.a->pad_first_obs) ? 1.f : 1.f / (float)M.nsub;
+    if (lane < 3) {
+      ob[lane] = T.sens[lane] * inv;
+      ob[ep.a->off_gyro + lane] = T.sens[3 + lane] * inv;
+      ob[ep.a->off_velocimeter + lane] = T.sens[6 + lane] * inv;
+    }
+    if (lane < NU) ob[ep.a->off_act + lane] = act_reg;
+    if (lane < 18) ob[ep.a->off_force + lane] = T.sens[9 + lane] * inv;
+    if (lane < 6) ob[ep.a->off_touch + lane] = T.sens[27 + lane] * inv;
+    export_state(c, ep.a->qpos + (size_t)env * 109, ep.a->qvel + (size_t)env * 108);
+    if (lane == 0) {
+      float gy[3], ve[3];
+      const float qr[4] = {c.rq.w, c.rq.x, c.rq.y, c.rq.z}, vl[3] = {c.vw.x, c.vw.y, c.vw.z}, wb[3] = {c.wb.x, c.wb.y, c.wb.z};
+      wi::imu_velocity<float>(qr, vl, wb, ep.a->site_pos, ep.a->site_quat, gy, ve);
+      float *t = ep.a->term + (size_t)env * 4;
+      t[0] = fsqrt(ve[0] * ve[0] + ve[1] * ve[1] + ve[2] * ve[2]);
+      t[1] = fsqrt(gy[0] * gy[0] + gy[1] * gy[1] + gy[2] * gy[2]);
+      t[2] = qn2; t[3] = 0.f;
+    }
   }
 }
 
@@ -543,6 +720,120 @@ __global__ __launch_bounds__(64, 2) void walk_limits_kernel(const WalkModel *__r
   if ((int)blockIdx.x >= batch) return;
   __shared__ WTileL T;
   walk_substeps<true>(T, Wp, flags, states, ctrl, nphys);
+}
+
+// ------------------------------------------------------------------------------------------------ walk_imitation, floor off
+// One control step of fly_envs.walk_imitation per wave (FFE_WALK_EPISODES), or the reset of an env that
+// episode_begin_kernel flagged: the limits kernel's substeps, the action row in front of them, the sensor sums, the physics columns
+// of the observation row and the state for the task layer behind them.  A step is five launches on the caller's stream:
+//   episode_begin_kernel           who resets, the clip draw, the step counters
+//   ffe_walktask_reference_pose    the pose a reset row starts from (row 0 of its clip)
+//   imitation_step_kernel          this one
+//   ffe_walktask_evaluate          reward, termination bits and the kinematic observation columns of (qpos, qvel, clip, step)
+//   episode_close_kernel           reward, discount, step_type; who resets next
+// (its name carries no `walk_`: the two kernels above are the bare-physics step kernels the older tests count)
+__global__ __launch_bounds__(64, 2) void imitation_step_kernel(const WalkModel *__restrict__ Wp, int flags, WState *__restrict__ states,
+                                                              const ImitArgs *__restrict__ args, const float *__restrict__ action,
+                                                              float *__restrict__ obs, int batch) {
+  if ((int)blockIdx.x >= batch) return;
+  __shared__ WTileE T;
+  walk_substeps<true>(T, Wp, flags, states, nullptr, 0, ImitCall{args, action, obs});
+}
+
+// Episode record of an env (the oracle's fo_walk_env counters)
+struct EpState {
+  unsigned long long episode;  // episodes started so far: the counter of the clip draw
+  int clip, step, needs_reset, forced;  // forced: clip of the next reset (-1: draw)
+  int episode_steps;           // min(len - future_steps - 1, round(time_limit / dt) + 1) of the clip
+  int ep_flagged, ep_bits;     // validity: flagged control steps of the episode, OR of their step_bits
+  int pad;
+};
+
+__device__ __forceinline__ unsigned long long splitmix64(unsigned long long x) {
+  x += 0x9E3779B97F4A7C15ULL;
+  x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ULL;
+  x = (x ^ (x >> 27)) * 0x94D049BB133111EBULL;
+  return x ^ (x >> 31);
+}
+// the counter-based generator of fly_env.hip (include/flybody_env.h)
+__device__ __forceinline__ unsigned long long env_rng(unsigned long long seed, unsigned long long env, unsigned long long episode, unsigned long long stream) {
+  return splitmix64(splitmix64(splitmix64(seed ^ 0xF1B0D7ULL) + env) + (episode << 2) + stream);
+}
+
+// mode 0 step, 1 reset all, 3 reset the envs whose mask byte is set.  ref: walk_imitation.py:89-110 (the clip of a new episode),
+// base.py: step_counter.  `zero`: the row index ffe_walktask_reference_pose reads the pose from.
+__global__ void episode_begin_kernel(EpState *eps, const unsigned char *mask, int mode, unsigned long long seed, unsigned long long env_id_base,
+                                     int ntraj, const int *clip_steps, int *flag, int *clip, int *step, int *zero, int batch) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= batch) return;
+  EpState &e = eps[i];
+  const bool skip = mode == 3 && !mask[i];
+  const bool reset = mode == 1 || (mode == 3 && !skip) || (mode == 0 && e.needs_reset != 0);
+  if (reset) {
+    if (e.forced >= 0) { e.clip = e.forced; e.forced = -1; }
+    else e.clip = (int)(env_rng(seed, env_id_base + (unsigned long long)i, e.episode, 0) % (unsigned long long)ntraj);
+    e.episode++;
+    e.episode_steps = clip_steps[e.clip];
+    e.step = 0;
+  } else if (!skip) {
+    e.step++;
+  }
+  flag[i] = skip ? 2 : (reset ? 1 : 0);
+  clip[i] = e.clip; step[i] = e.step; zero[i] = 0;
+}
+
+// ref: walk_imitation.py:148-177 get_reward_factors / check_termination, composer.Environment's time limit.  `reward_in` and `bits`
+// are ffe_walktask_evaluate's (the product of the four factors with NaN -> 0, 1 in inference mode; bit 0 distance, bit 1 end of clip).
+__global__ void episode_close_kernel(EpState *eps, const WState *states, const int *flag, const float *term, const float *reward_in, const int *bits,
+                                     int time_limit_steps, float *rew, float *disc, int *st, int batch) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= batch) return;
+  if (flag[i] == 2) return;
+  EpState &e = eps[i];
+  if (flag[i] == 1) {
+    rew[i] = 0.f; disc[i] = 1.f; st[i] = 0;
+    e.needs_reset = 0; e.ep_flagged = 0; e.ep_bits = 0;
+    return;
+  }
+  const float *t = term + (size_t)i * 4;
+  const bool end = (bits[i] & 2) != 0;
+  const bool fatal = t[0] > 50.f || t[1] > 200.f || (bits[i] & 1) != 0 || !(t[2] == t[2]) || !(sqrtf(t[2]) <= 1e14f);
+  const bool stop = fatal || end;
+  const bool timeup = e.step >= time_limit_steps;
+  const float r = reward_in[i];
+  rew[i] = r == r ? r : 0.f;
+  disc[i] = (stop && !end) ? 0.f : 1.f;
+  st[i] = (stop || timeup) ? 2 : 1;
+  e.needs_reset = (stop || timeup) ? 1 : 0;
+  const int sb = states[i].step_bits;
+  e.ep_flagged += sb ? 1 : 0; e.ep_bits |= sb;
+}
+
+__global__ void episode_force_kernel(EpState *eps, const int *traj, int batch) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < batch && traj[i] >= 0) eps[i].forced = traj[i];
+}
+__global__ void episode_init_kernel(EpState *eps, int batch) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= batch) return;
+  EpState z{};
+  z.needs_reset = 1; z.forced = -1;
+  eps[i] = z;
+}
+// episode handle: task state {clip, step counter, episode (low 32 bits), needs_reset, limit rows of the last substep, 0, solver
+// iterations of the last substep, overflow bits of the last launch}, reals zero; validity {step_bits, episode_flagged_steps,
+// episode_bits, episode_steps}
+__global__ void episode_report_kernel(const EpState *eps, const WState *states, int *ints, double *reals, int *info, int batch) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= batch) return;
+  const WState &S = states[i];
+  const EpState &e = eps[i];
+  if (ints) {
+    int *o = ints + (size_t)i * 8;
+    o[0] = e.clip; o[1] = e.step; o[2] = (int)(unsigned)e.episode; o[3] = e.needs_reset; o[4] = S.nlim; o[5] = 0; o[6] = S.iters; o[7] = S.step_bits;
+    for (int k = 0; k < 8; k++) reals[(size_t)i * 8 + k] = 0.0;
+  }
+  if (info) *reinterpret_cast<int4 *>(info + (size_t)i * 4) = make_int4(S.step_bits, e.ep_flagged, e.ep_bits, e.step);
 }
 
 // mj: mj_normalizeQuat as the position stage applies it (float32, a null quaternion becomes the identity)
@@ -599,38 +890,95 @@ __global__ void walk_act_kernel(WState *states, double *act, int batch, int set)
 }
 
 // ================================================================================================ host side
-// Bare physics is all that is built: reset, step, forced episodes and the timers are refused.
+// Bare physics (reset, step, forced episodes and the timers are refused) or, created with FFE_WALK_EPISODES, the walk_imitation
+// environment with the floor off.
 struct WalkEnv final : ffe::EnvBackend {
   int flags = 0;
-  bool limits = false;  // FFE_WALK_JOINT_LIMITS: walk_limits_kernel steps this handle
+  bool limits = false;    // FFE_WALK_JOINT_LIMITS: walk_limits_kernel steps this handle
+  bool episodes = false;  // FFE_WALK_EPISODES: ffe_step / ffe_reset / ... work, imitation_step_kernel steps them
   WalkHost host;
+  ffe::DeviceBuffers mem{"ffe_create_walk_physics"};  // everything below lives here
   WalkModel *model_dev = nullptr;
   WState *states = nullptr;
+  // episode handle only
+  ffe_walktask_handle task = nullptr;  // the float32 task layer of this env
+  ImitArgs args{};
+  ImitArgs *args_dev = nullptr;  // its copy on the device
+  EpState *eps = nullptr;
+  int *flag = nullptr, *clip = nullptr, *step = nullptr, *zero = nullptr, *clip_steps = nullptr, *bits = nullptr, *forced_dev = nullptr;
+  float *reward_tmp = nullptr;
+  unsigned long long seed = 0, env_id_base = 0;
+  int ntraj = 0, time_limit_steps = 0, n_obs_joints = 0, n_ref = 0, off_jpos = -1, off_jvel = -1, off_disp = -1, off_rquat = -1, off_zaxis = -1;
+  ffe::KernelTimer tm;
 
   ~WalkEnv() override {
-    (void)hipFree(model_dev); (void)hipFree(states);
+    if (task) (void)ffe_walktask_destroy(task);
   }
 
   [[noreturn]] void refuse(const char *what) const override {
     throw ffe::Refused(std::string(what) + ": not available on a walk physics handle (bare physics only: limits, floor contacts, sensors and the episode protocol are not built yet)");
   }
+  // a failure of the task layer becomes this handle's error
+  void task_ok(int rc, const char *what) const {
+    if (rc != 0) throw std::runtime_error(std::string(what) + ": " + ffe_walktask_last_error(task));
+  }
 
-  void spec(ffe_spec_t &s) const override {  // no observation row: every offset is -1
+  void spec(ffe_spec_t &s) const override {  // bare physics: no observation row, every offset is -1
     s = ffe_spec_t{};
     s.batch = batch; s.nq = host.nq; s.nv = host.nv; s.nu = NU; s.action_dim = NACT; s.obs_dim = 0; s.nsub = host.m.b.nsub;
     s.physics_timestep = host.m.b.h; s.control_timestep = (double)host.m.b.nsub * (double)host.m.b.h;
     s.off_accelerometer = s.off_gyro = s.off_joints_pos = s.off_joints_vel = s.off_velocimeter = s.off_world_zaxis = -1;
     s.off_ref_displacement = -1; s.off_ref_root_quat = -1;
+    if (episodes) {
+      // accelerometer 3 | actuator_activation 59 | appendages_pos | force 18 | gyro 3 | joints_pos | joints_vel | ref_displacement |
+      // ref_root_quat | touch 6 | velocimeter 3 | world_zaxis 3
+      s.obs_dim = args.obs_dim; s.off_accelerometer = 0; s.off_gyro = args.off_gyro; s.off_joints_pos = off_jpos; s.off_joints_vel = off_jvel;
+      s.off_velocimeter = args.off_velocimeter; s.off_world_zaxis = off_zaxis; s.off_ref_displacement = off_disp; s.off_ref_root_quat = off_rquat;
+      s.n_obs_joints = n_obs_joints; s.n_ref = n_ref;
+    }
   }
   void action_bounds(float *mn, float *mx) const override {
     for (int k = 0; k < NACT; k++) { mn[k] = host.action_min[k]; mx[k] = host.action_max[k]; }
   }
-  void launch(const float *ctrl, float *, float *, float *, int32_t *, void *stream, int mode, int nphys, const uint8_t *) override {  // ctrl[B][59]
-    if (mode != 2) refuse("ffe_reset / ffe_reset_envs / ffe_step");
-    if (!ctrl || nphys <= 0) throw std::runtime_error("walk physics: null control buffer or no steps");
-    if (limits) hipLaunchKernelGGL(walk_limits_kernel, dim3(batch), dim3(64), 0, (hipStream_t)stream, model_dev, flags, states, ctrl, batch, nphys);
-    else hipLaunchKernelGGL(walk_step_kernel, dim3(batch), dim3(64), 0, (hipStream_t)stream, model_dev, flags, states, ctrl, batch, nphys);
+  ffe::KernelTimer *timer() override { return episodes ? &tm : nullptr; }
+
+  void launch(const float *act, float *obs, float *rew, float *disc, int32_t *st, void *stream, int mode, int nphys, const uint8_t *mask) override {
+    hipStream_t s = (hipStream_t)stream;
+    if (mode == 2) {  // bare physics: act = ctrl[B][59]
+      if (!act || nphys <= 0) throw std::runtime_error("walk physics: null control buffer or no steps");
+      if (limits) hipLaunchKernelGGL(walk_limits_kernel, dim3(batch), dim3(64), 0, s, model_dev, flags, states, act, batch, nphys);
+      else hipLaunchKernelGGL(walk_step_kernel, dim3(batch), dim3(64), 0, s, model_dev, flags, states, act, batch, nphys);
+      HIP_OK(hipGetLastError());
+      return;
+    }
+    if (!episodes) refuse("ffe_reset / ffe_reset_envs / ffe_step");
+    ffe::need(mode != 0 || act, "walk_imitation: null action buffer");
+    ffe::need(obs && rew && disc && st, "walk_imitation: null output buffer");
+    const dim3 grid((batch + 63) / 64), block(64);
+    hipLaunchKernelGGL(episode_begin_kernel, grid, block, 0, s, eps, mask, mode, seed, env_id_base, ntraj, clip_steps, flag, clip, step, zero, batch);
     HIP_OK(hipGetLastError());
+    task_ok(ffe_walktask_reference_pose(task, clip, zero, batch, const_cast<double *>(args.pose), nullptr, stream), "walk_imitation");
+    const ImitArgs &a = args;
+    tm.start(s);
+    hipLaunchKernelGGL(imitation_step_kernel, dim3(batch), dim3(64), 0, s, model_dev, flags, states, args_dev, act, obs, batch);
+    HIP_OK(hipGetLastError());
+    tm.stop(s);
+    task_ok(ffe_walktask_evaluate(task, a.qpos, a.qvel, clip, step, batch, nullptr, reward_tmp, bits, obs, a.obs_dim, stream), "walk_imitation");
+    hipLaunchKernelGGL(episode_close_kernel, grid, block, 0, s, eps, states, flag, a.term, reward_tmp, bits, time_limit_steps, rew, disc, st, batch);
+    HIP_OK(hipGetLastError());
+    tm.collect();
+  }
+  void force_next_episode(const int32_t *traj, const double *, void *stream) override {  // (walk_imitation draws no phase)
+    if (!episodes) refuse("ffe_force_next_episode");
+    for (int i = 0; i < batch; i++)
+      if (traj[i] >= ntraj) throw ffe::Refused("ffe_force_next_episode: trajectory index out of range");
+    hipStream_t s = (hipStream_t)stream;
+    // pageable host memory: the copy is staged before the call returns, ordered on `s` with the kernel below; the stream is
+    // synchronised once so that a second call cannot overwrite the staging buffer under a pending kernel (as the flight handle)
+    HIP_OK(hipMemcpyAsync(forced_dev, traj, sizeof(int) * (size_t)batch, hipMemcpyHostToDevice, s));
+    hipLaunchKernelGGL(episode_force_kernel, dim3((batch + 63) / 64), dim3(64), 0, s, eps, forced_dev, batch);
+    HIP_OK(hipGetLastError());
+    HIP_OK(hipStreamSynchronize(s));
   }
   void get_state(double *qpos, double *qvel, void *stream) override {  // qpos[B][109], qvel[B][108]: MuJoCo's free-joint layout
     hipLaunchKernelGGL(walk_get_state_kernel, dim3(batch), dim3(128), 0, (hipStream_t)stream, states, qpos, qvel, batch);
@@ -649,6 +997,11 @@ struct WalkEnv final : ffe::EnvBackend {
     HIP_OK(hipGetLastError());
   }
   void get_task_state(int32_t *ints, double *reals, void *stream) override {  // int32[B][8] and float64[B][8]: zeros on a plain handle
+    if (episodes) {
+      hipLaunchKernelGGL(episode_report_kernel, dim3((batch + 63) / 64), dim3(64), 0, (hipStream_t)stream, eps, states, ints, reals, (int *)nullptr, batch);
+      HIP_OK(hipGetLastError());
+      return;
+    }
     if (limits) {
       hipLaunchKernelGGL(walk_limits_report_kernel, dim3((batch + 63) / 64), dim3(64), 0, (hipStream_t)stream, states, ints, reals, (int *)nullptr, batch);
       HIP_OK(hipGetLastError());
@@ -658,6 +1011,11 @@ struct WalkEnv final : ffe::EnvBackend {
     HIP_OK(hipMemsetAsync(reals, 0, sizeof(double) * 8 * (size_t)batch, (hipStream_t)stream));
   }
   void get_validity(int32_t *info, void *stream) override {  // int32[B][4]: zeros on a plain handle
+    if (episodes) {
+      hipLaunchKernelGGL(episode_report_kernel, dim3((batch + 63) / 64), dim3(64), 0, (hipStream_t)stream, eps, states, (int *)nullptr, (double *)nullptr, info, batch);
+      HIP_OK(hipGetLastError());
+      return;
+    }
     if (limits) {
       hipLaunchKernelGGL(walk_limits_report_kernel, dim3((batch + 63) / 64), dim3(64), 0, (hipStream_t)stream, states, (int *)nullptr, (double *)nullptr, info, batch);
       HIP_OK(hipGetLastError());
@@ -667,10 +1025,67 @@ struct WalkEnv final : ffe::EnvBackend {
   }
 };
 
-std::unique_ptr<ffe::EnvBackend> walk_create(const void *blob, size_t blob_size, int physics_flags, int batch, int device) {
+// what FFE_WALK_EPISODES adds to a limits handle: the task layer, the episode records and the buffers between the launches of a step
+static void make_episodes(WalkEnv &e, const Blob &b, const void *blob, size_t blob_size, const ffe_walk_physics_task &t) {
+  const int B = e.batch;
+  if (ffe_walktask_create(blob, blob_size, t.task, 0, e.device, &e.task) != 0)
+    throw std::runtime_error(std::string("ffe_create_walk_physics: FFE_WALK_EPISODES: ") + ffe_walktask_last_error(nullptr));
+  int32_t dims[16];
+  e.task_ok(ffe_walktask_info(e.task, dims, nullptr), "ffe_create_walk_physics");
+  e.ntraj = dims[4];
+  if (e.ntraj <= 0) throw std::runtime_error("ffe_create_walk_physics: FFE_WALK_EPISODES needs reference clips in the task");
+  if (dims[0] != e.host.nq || dims[1] != e.host.nv) throw std::runtime_error("ffe_create_walk_physics: FFE_WALK_EPISODES: the task layer's model is not the walk model");
+  if (llround(t.task->control_timestep / (double)e.host.m.b.h) != e.host.m.b.nsub)
+    throw std::runtime_error("ffe_create_walk_physics: FFE_WALK_EPISODES: the task's control_timestep must be 10 physics steps");
+  if (t.time_limit_steps <= 0) throw std::runtime_error("ffe_create_walk_physics: FFE_WALK_EPISODES: time_limit_steps must be positive");
+  std::vector<int32_t> ep((size_t)e.ntraj);
+  e.task_ok(ffe_walktask_info(e.task, dims, ep.data()), "ffe_create_walk_physics");
+  // the row: accelerometer 3 | actuator_activation 59 | appendages_pos | force 18 | gyro 3 | joints_pos | joints_vel | ref_displacement |
+  // ref_root_quat | touch 6 | velocimeter 3 | world_zaxis 3; the kinematic offsets are the task layer's
+  ImitArgs &a = e.args;
+  const int F1 = dims[5] + 1;
+  a.obs_dim = dims[6]; a.off_act = 3; a.off_force = dims[7] + 3 * dims[13]; a.off_gyro = a.off_force + 18;
+  a.off_touch = dims[11] + 4 * F1; a.off_velocimeter = a.off_touch + 6;
+  e.off_jpos = dims[8]; e.off_jvel = dims[9]; e.off_disp = dims[10]; e.off_rquat = dims[11]; e.off_zaxis = dims[12];
+  e.n_obs_joints = dims[14]; e.n_ref = F1;
+  if (dims[7] != 3 + NU || dims[8] != a.off_gyro + 3 || dims[12] != a.off_velocimeter + 3 || a.obs_dim != dims[12] + 3)
+    throw std::runtime_error("ffe_create_walk_physics: FFE_WALK_EPISODES: the task layer's observation row leaves no room for the 92 physics columns");
+  a.canonical = t.canonical_actions; a.clip = t.clip_actions; a.pad_first_obs = t.pad_first_obs;
+  {
+    const Tensor &site = b.get("site");  // body, position 3, quaternion 4 of the IMU site (the thorax is the root: already its frame)
+    for (int k = 0; k < 3; k++) a.site_pos[k] = (float)site.f(1 + k);
+    for (int k = 0; k < 4; k++) a.site_quat[k] = (float)site.f(4 + k);
+  }
+  e.seed = t.seed; e.env_id_base = t.env_id_base; e.time_limit_steps = t.time_limit_steps;
+  a.pose = e.mem.zeroed<double>((size_t)B * 109);
+  a.qpos = e.mem.zeroed<double>((size_t)B * 109); a.qvel = e.mem.zeroed<double>((size_t)B * 108);
+  a.term = e.mem.zeroed<float>((size_t)B * 4);
+  e.eps = e.mem.zeroed<EpState>((size_t)B);
+  e.flag = e.mem.zeroed<int>((size_t)B); e.clip = e.mem.zeroed<int>((size_t)B); e.step = e.mem.zeroed<int>((size_t)B);
+  e.zero = e.mem.zeroed<int>((size_t)B); e.bits = e.mem.zeroed<int>((size_t)B); e.forced_dev = e.mem.zeroed<int>((size_t)B);
+  e.reward_tmp = e.mem.zeroed<float>((size_t)B);
+  e.clip_steps = e.mem.zeroed<int>((size_t)e.ntraj);
+  a.flag = e.flag;
+  e.args_dev = e.mem.zeroed<ImitArgs>(1);
+  HIP_OK(hipMemcpy(e.args_dev, &a, sizeof(ImitArgs), hipMemcpyHostToDevice));
+  HIP_OK(hipMemcpy(e.clip_steps, ep.data(), sizeof(int32_t) * (size_t)e.ntraj, hipMemcpyHostToDevice));
+  hipLaunchKernelGGL(episode_init_kernel, dim3((B + 63) / 64), dim3(64), 0, 0, e.eps, B);
+  HIP_OK(hipGetLastError());
+  e.tm.create();
+}
+
+std::unique_ptr<ffe::EnvBackend> walk_create(const void *blob, size_t blob_size, const ffe_walk_physics_task &task, int batch, int device) {
+  const int physics_flags = task.physics_flags;
   if (!blob || batch <= 0) throw std::runtime_error("ffe_create_walk_physics: bad arguments");
   const bool limits = (physics_flags & BF_WALK_JOINT_LIMITS) != 0, no_limit = (physics_flags & BF_NO_LIMIT) != 0;
-  if (!(physics_flags & BF_NO_CONTACT) || limits == no_limit) {
+  const bool episodes = (physics_flags & BF_WALK_EPISODES) != 0;
+  if (episodes) {
+    const int force_switches = BF_NO_FLUID | BF_NO_DAMPER | BF_NO_SPRING | BF_NO_GRAVITY | BF_NO_ACTUATION;
+    if ((physics_flags & ~force_switches) != (BF_NO_CONTACT | BF_WALK_JOINT_LIMITS | BF_WALK_EPISODES))
+      throw std::runtime_error("ffe_create_walk_physics: FFE_WALK_EPISODES (the walk_imitation environment with the floor off) needs FFE_NO_CONTACT | "
+                               "FFE_WALK_JOINT_LIMITS and takes the force switches only: floor contacts are not built yet");
+    if (!task.task) throw std::runtime_error("ffe_create_walk_physics: FFE_WALK_EPISODES needs the task (a null ffe_walk_task pointer)");
+  } else if (!(physics_flags & BF_NO_CONTACT) || limits == no_limit) {
     // without the new bit the text is the one the C ABI contract pins; with it the text names the bit
     if (!limits) throw std::runtime_error("ffe_create_walk_physics: floor contacts and joint limits are not built yet: physics_flags must contain FFE_NO_CONTACT | FFE_NO_LIMIT");
     throw std::runtime_error("ffe_create_walk_physics: floor contacts and joint limits are not built yet as a step kernel: FFE_WALK_JOINT_LIMITS needs "
@@ -679,13 +1094,14 @@ std::unique_ptr<ffe::EnvBackend> walk_create(const void *blob, size_t blob_size,
   std::unique_ptr<WalkEnv> e(new WalkEnv());  // frees the device allocations made so far if a later step throws
   Blob b(blob, blob_size);
   e->host = build_walk_model(b);
-  e->device = device; e->batch = batch; e->flags = physics_flags; e->limits = limits;
-  e->host.m.b.nsub = 10;  // ffe_spec's figure: the reference's control step of 2 ms over the model's 0.2 ms (nothing here steps by it)
-  HIP_OK(hipMalloc((void **)&e->model_dev, sizeof(WalkModel)));
+  e->device = device; e->batch = batch; e->flags = physics_flags & ~BF_WALK_EPISODES; e->limits = limits; e->episodes = episodes;
+  e->host.m.b.nsub = 10;  // the reference's control step of 2 ms over the model's 0.2 ms (bare physics: ffe_spec's figure alone)
+  e->model_dev = e->mem.zeroed<WalkModel>(1);
   HIP_OK(hipMemcpy(e->model_dev, &e->host.m, sizeof(WalkModel), hipMemcpyHostToDevice));
-  HIP_OK(hipMalloc((void **)&e->states, sizeof(WState) * (size_t)batch));
+  e->states = e->mem.zeroed<WState>((size_t)batch);
   hipLaunchKernelGGL(walk_init_states, dim3(batch), dim3(64), 0, 0, e->states, e->model_dev, batch);
   HIP_OK(hipGetLastError());
+  if (episodes) make_episodes(*e, b, blob, blob_size, task);
   HIP_OK(hipDeviceSynchronize());
   return e;
 }

@@ -1,8 +1,9 @@
 """Environment factories with the reference's names and keyword meaning (`vnl_ray/fly_envs.py`), returning
 batched MI355X environments instead of single-instance `composer.Environment`s.
 
-Built so far: `flight_imitation` (`fly_envs.py:29-72`) and `walk_on_ball` (`fly_envs.py:125-157`).  `walk_imitation`,
-`vision_guided_flight` and `template_task` are later rows of SURVEY.md section 8 and raise `NotImplementedError`.
+Built so far: `flight_imitation` (`fly_envs.py:29-72`), `walk_on_ball` (`fly_envs.py:125-157`) and `walk_imitation` without its
+floor (`floor_contacts=False`; the default call raises until floor contacts exist).  `vision_guided_flight` and `template_task` are
+later rows of SURVEY.md section 8 and raise `NotImplementedError`.
 """
 
 from __future__ import annotations
@@ -60,20 +61,54 @@ def walk_on_ball(random_state=None, *, batch_size: int = 1, device: int = 0, **e
     return BatchedBallEnv(batch_size=batch_size, device=device, time_limit=2.0, **env_kwargs)
 
 
-def walk_imitation(ref_path=None, random_state=None, terminal_com_dist: float = 0.3, **env_kwargs):
+def walk_imitation(ref_path=None, random_state=None, terminal_com_dist: float = 0.3, *, floor_contacts: bool = True, batch_size: int = 1,
+                   device: int = 0, **env_kwargs):
     """Requires a fruitfly to track a reference walking fly (`fly_envs.py:75-122`).
 
-    Built so far: the compiled model (`assets/fly_walk.ffmb`: free root, floor plane, Walking
+    Built: the compiled model (`assets/fly_walk.ffmb`: free root, floor plane, Walking
     configuration), the snippet layout and walker features (`tasks/walking.py`), the DeepMimic reward maths (`tasks/rewards.py`), the
     task layer on the device (`tasks/walk_tracker.py`: features, reward, termination, observation columns), the free-root smooth
-    dynamics on the device (`batched_env.BatchedWalkPhysics`: `ffe_physics_step` with constraints off, or with `joint_limits=True`
-    with the joint limits of the 102 hinges on) and the float64 CPU restatement of the whole task that the tests check against (test
-    infrastructure, outside this package).  Missing: joint limits inside a step kernel (they exist as an opt-in of the bare physics
-    only), floor contacts, sensors and the episode protocol of the step kernel.  This package has no CPU path: the factory fails
-    instead of returning a slow environment."""
-    raise NotImplementedError("walk_imitation: model, reference layout, reward maths, oracle, the device task layer (WalkTracker), the "
-                              "free-root smooth dynamics and, opt-in, their joint limits (BatchedWalkPhysics) exist; floor contacts, sensors "
-                              "and the episode protocol of the HIP step kernel are not built yet - see DESIGN.md section 12")
+    dynamics with the joint limits of the 102 hinges (`batched_env.BatchedWalkPhysics`), and around them the sensors and the episode
+    protocol of the step kernel (`batched_env.BatchedWalkEnv`); the float64 CPU restatement of the whole task that the tests check
+    against is test infrastructure, outside this package.  Missing: floor contacts - the one remaining piece.
+
+    So the default call (`floor_contacts=True`, the reference's task) raises `NotImplementedError`: this package has no CPU path and
+    the factory fails instead of returning a slow or a different environment.  `floor_contacts=False` is the explicit opt-in to what
+    exists: a `BatchedWalkEnv` whose fly falls freely under gravity (or floats with `physics_flags=FFE_NO_GRAVITY`), with force and
+    touch reading zero - the environment the next floor attempt slots its contact rows into.
+
+    Args:
+        ref_path: `.npz` written by `tasks.walking.save_npz` (clips of individual lengths with their tracked features).  None = the
+            build's synthetic snippets.
+        random_state: int seed or `np.random.RandomState`; seeds the per-env counter-based generator that draws every episode's clip.
+        terminal_com_dist: an episode terminates when the root is further than this from the reference root (cm).
+        floor_contacts: True (the default) raises; False returns the environment without the floor.
+        batch_size, device: batching.  `env_kwargs` go to `BatchedWalkEnv` (`inference_mode`, `env_id_base`, `pad_first_obs`,
+            `physics_flags`, `canonical_actions`, `clip_actions`, `double_buffer`)."""
+    if floor_contacts:
+        raise NotImplementedError("walk_imitation: floor contacts of the HIP step kernel are not built yet (DESIGN.md section 12).  The model, "
+                                  "the device task layer (WalkTracker), the free-root smooth dynamics with their joint limits "
+                                  "(BatchedWalkPhysics), the sensors and the episode protocol (BatchedWalkEnv) exist: "
+                                  "walk_imitation(floor_contacts=False) returns that environment, a fly without a floor under it")
+    from .batched_env import BatchedWalkEnv
+    from .tasks import walking
+
+    view = walking.WalkModelView()
+    if ref_path is None:
+        refs = walking.WalkRefSet(walking.synthetic_snippets(view))
+    else:
+        refs, joint_names, site_names, dt = walking.load_npz(ref_path)
+        if abs(dt - 2e-3) > 1e-12:
+            raise ValueError(f"trajectory timestep {dt} != control timestep 0.002")
+        if list(joint_names) != list(view.meta["mocap_joints"]) or list(site_names) != list(view.meta["mocap_sites"]):
+            raise ValueError("the file's tracked joints / sites are not the model's (assets/fly_walk.json: mocap_joints, mocap_sites)")
+    if isinstance(random_state, np.random.RandomState):
+        seed = int(random_state.randint(0, 2**31 - 1))
+    else:
+        seed = 0 if random_state is None else int(random_state)
+    # fly_envs.py:100-118: time_limit 10 s, future_steps 64, joint_filter / adhesion_filter compiled into the model
+    return BatchedWalkEnv(refs, view, batch_size=batch_size, device=device, seed=seed, future_steps=64, time_limit=10.0,
+                          terminal_com_dist=terminal_com_dist, **env_kwargs)
 
 
 def vision_guided_flight(*args, **kwargs):

@@ -1,7 +1,7 @@
 """Device task layer of `fly_envs.walk_imitation` (include/flybody_env.h `ffe_walktask_*`, csrc/walk_task.hip): the walker
 features of `tasks/rewards.py:36-61`, the four DeepMimic reward factors, the task's termination bits and the kinematic columns of
 the observation row, as a pure function of (qpos, qvel, clip, step) on batches of states that live on the device.  No physics: the
-step kernel of walk_imitation is not built yet, so `fly_envs.walk_imitation` still raises; this scores
+environment (`batched_env.BatchedWalkEnv`) holds a handle of this layer of its own; this class scores
 recorded states against clips (reward relabelling, dataset QC) and turns raw pose rows into reference tables (`walking.featurize`).
 """
 

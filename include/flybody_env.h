@@ -23,8 +23,9 @@
  *         flight        ffe_get_act, ffe_set_act
  *         walk_on_ball  ffe_force_next_episode ("no per-episode randomness")
  *         walk physics  ffe_reset, ffe_reset_envs, ffe_step, ffe_force_next_episode, ffe_time_steps, ffe_time_kernel
- *                       ("... not available on a walk physics handle"); ffe_get_task_state / ffe_get_validity zero-fill
- *                       (a FFE_WALK_JOINT_LIMITS handle: see ffe_create_walk_physics).
+ *                       ("... not available on a walk physics handle"; a FFE_WALK_EPISODES handle has all six);
+ *                       ffe_get_task_state / ffe_get_validity zero-fill (a FFE_WALK_JOINT_LIMITS or FFE_WALK_EPISODES handle: see
+ *                       ffe_create_walk_physics).
  *   -2  a HIP call failed (text: the call and hipGetErrorString).  For historical reasons also walk_on_ball's NULL-buffer
  *       checks of ffe_step / ffe_reset ("walk_on_ball: null output buffer" / "null action buffer").
  *   Since the calls moved into csrc/capi.hip every -1 / -2 on a non-NULL handle sets ffe_last_error(h) (NULL-argument -1s and some
@@ -60,8 +61,14 @@ enum {
   /* ffe_create_walk_physics only: joint limits on (the second step kernel of csrc/walk_env.hip).  An opt-in bit and provisional: it
    * exists because plain FFE_NO_CONTACT is a pinned refusal of that create call while floor contacts are missing; when the step
    * kernel lands it folds into "FFE_NO_LIMIT absent". */
-  FFE_WALK_JOINT_LIMITS = 512
+  FFE_WALK_JOINT_LIMITS = 512,
+  /* ffe_create_walk_physics only: the handle is the walk_imitation environment with the floor off (sensors, episode protocol, task
+   * layer; the third step kernel of csrc/walk_env.hip).  Accepted only as FFE_NO_CONTACT | FFE_WALK_JOINT_LIMITS | FFE_WALK_EPISODES
+   * plus force switches.  An opt-in bit and provisional for the same reason: it goes when floor contacts land. */
+  FFE_WALK_EPISODES = 1024
 };
+
+typedef struct ffe_walk_task_s ffe_walk_task; /* the walk_imitation task layer's inputs, defined with ffe_walktask_create below */
 
 /* Task inputs of fly_envs.flight_imitation (vnl_ray/fly_envs.py:29-72).  All host pointers, float64,
  * copied during ffe_create. */
@@ -137,13 +144,23 @@ int ffe_create_walk_on_ball(const void *model_blob, size_t blob_size, const ffe_
                             ffe_handle *out);
 /* The walking fly of fly_envs.walk_imitation (fly_envs.py:75-122; flybody_amd/assets/fly_walk.ffmb: free thorax, 6 + 102 dofs, 59
  * filtered actuators) as bare physics: smooth dynamics on the device with constraints off ("dynamics only", as ffe_physics_step offers
- * for the other two tasks), or with the joint limits of its 102 hinges on (FFE_WALK_JOINT_LIMITS).  Floor contacts, sensors and the
- * episode protocol are not built yet. */
+ * for the other two tasks), or with the joint limits of its 102 hinges on (FFE_WALK_JOINT_LIMITS); and, with FFE_WALK_EPISODES on top
+ * of that, the walk_imitation environment itself with the floor off: sensors, observation row, reward, termination and the episode
+ * protocol on the device, a fly that falls freely (or floats with FFE_NO_GRAVITY).  Floor contacts are not built yet. */
 typedef struct {
   /* FFE_NO_CONTACT and exactly one of FFE_NO_LIMIT (smooth dynamics alone) or FFE_WALK_JOINT_LIMITS (joint limits on: up to 48 limit
    * rows per env and substep), plus any of the force switches FFE_NO_FLUID / _DAMPER / _SPRING / _GRAVITY / _ACTUATION; every other
-   * set is refused (the text names FFE_WALK_JOINT_LIMITS when that bit was passed) */
+   * set is refused (the text names FFE_WALK_JOINT_LIMITS when that bit was passed).  FFE_WALK_EPISODES is accepted only together with
+   * FFE_NO_CONTACT | FFE_WALK_JOINT_LIMITS (plus force switches); every other set with it is refused with a text naming it */
   int32_t physics_flags;
+  /* read only when physics_flags has FFE_WALK_EPISODES (a caller without the bit may pass the one int above alone) */
+  const ffe_walk_task *task;  /* clips, tracked joints / sites, reward and termination constants: a float32 task layer of the env's
+                                 own is created from it (host pointers, copied during the create call); control_timestep must be 10
+                                 physics steps */
+  uint64_t seed, env_id_base; /* clip of an episode: rng(seed, env_id_base + env, episode, 0) % ntraj, the generator of ffe_create_flight */
+  int32_t time_limit_steps;   /* control steps after which the time limit ends an episode, the count ffe_ball_task carries; 10 s: 5001 */
+  int32_t pad_first_obs;      /* 0 = dm_control zero-padded sensor buffers at reset */
+  int32_t canonical_actions, clip_actions; /* as in ffe_ball_task */
 } ffe_walk_physics_task;
 /* The handle starts at the blob's qpos0 with zero velocity and zero activation and works with ffe_spec (nq 109, nv 108, nu 59,
  * action_dim 59, obs_dim 0, nsub 10, every observation offset -1) / ffe_action_bounds / ffe_physics_step (ctrl[B][59], clamped to
@@ -159,7 +176,21 @@ typedef struct {
  *                       fit were dropped for that substep; columns 1-3 zero
  *   ffe_get_task_state  int 4 = limit rows instantiated in the last substep, int 6 = solver iterations of the last substep, int 7 =
  *                       the same overflow bits; every other int and every real zero
- * and all of them are zero until the first ffe_physics_step. */
+ * and all of them are zero until the first ffe_physics_step.
+ * A handle created with FFE_WALK_EPISODES is an environment (everything above still works on it): ffe_reset, ffe_reset_envs, ffe_step,
+ * ffe_force_next_episode (the clip; the phase array is ignored), ffe_time_steps and ffe_time_kernel work as on a walk_on_ball handle,
+ * and ffe_spec reports obs_dim 741 with the offsets of the row: accelerometer 3 | actuator_activation 59 | appendages_pos 21 |
+ * force 18 | gyro 3 | joints_pos 85 | joints_vel 85 | ref_displacement 195 | ref_root_quat 260 | touch 6 | velocimeter 3 |
+ * world_zaxis 3.  Force and touch are zero (no contacts).  A step is five launches on `stream` (episode bookkeeping, the reset pose,
+ * the step kernel, the task layer, the closing rule), with no allocation and no synchronisation, so it can be captured into a HIP
+ * graph.  Episode rules (walk_imitation.py:89-177): a reset takes the forced clip or draws one, starts at row 0 of it with zero
+ * velocity and activation; a step ends the episode when |velocimeter| > 50, |gyro| > 200, the root is further than terminal_com_dist
+ * from the clip's, sqrt(sum qacc^2) > 1e14 or NaN (discount 0), or at the end of the clip (discount 1), or at the time limit.
+ *   ffe_get_validity    {step_bits, episode_flagged_steps, episode_bits, episode_steps}, the limit-overflow bit (value 2) sticky over
+ *                       the episode in episode_bits, as on a walk_on_ball handle
+ *   ffe_get_task_state  int 0 = clip, int 1 = step counter, int 2 = episodes started (low 32 bits), int 3 = needs_reset (the next
+ *                       ffe_step resets this env), ints 4, 6, 7 as on a limits handle, int 5 and every real zero
+ * A failure of the env's task layer is the env handle's error text. */
 int ffe_create_walk_physics(const void *model_blob, size_t blob_size, const ffe_walk_physics_task *task, int batch, int device,
                             ffe_handle *out);
 /* physics.data.act (actuator activations, [B][nu] float64 device buffers) of a walk_on_ball or walk physics handle */
@@ -405,7 +436,7 @@ const char *ffe_eplog_last_error(ffe_eplog_handle h);
 typedef struct ffe_walktask *ffe_walktask_handle;
 enum { FFE_WALKTASK_FLOAT64 = 1 };
 /* all host pointers, copied during create */
-typedef struct {
+struct ffe_walk_task_s { /* (typedef ffe_walk_task, declared above ffe_walk_physics_task) */
   int32_t n_joints; const int32_t *joints;   /* tracked hinge joints (model joint indices); may be 0 */
   int32_t n_sites; const int32_t *sites;     /* tracked sites (model site indices); may be 0 */
   /* reference clips of individual lengths, rows concatenated (HDF5WalkingTrajectoryLoader.get_trajectory, trajectory_loaders.py:163-215);
@@ -421,7 +452,7 @@ typedef struct {
   int32_t n_overrides; const int32_t *override_qadr; const double *override_val; /* qpos written after the reference pose at reset
                                                                                     (retract_wings, task_utils.py:117-122) */
   int32_t inference_mode;                    /* walk_imitation.py:148-151: the reward is the constant 1 */
-} ffe_walk_task;
+};
 /* flags: 0 = float32 kinematics and outputs, FFE_WALKTASK_FLOAT64 = the float64 instantiation (dataset featurisation).  The root
  * position and every difference against it are float64 in both.  Refused with rc < 0 and a text in ffe_walktask_last_error(NULL):
  * a null required pointer, a tracked joint that is not a hinge, a joint / site / override index out of range, a clip shorter than
