@@ -26,6 +26,7 @@ WALK_BLOB = os.path.join(_ASSETS, "fly_walk.ffmb")
 FFE_NO_LIMIT, FFE_NO_CONTACT = 2, 64  # include/flybody_env.h
 FFE_WALK_JOINT_LIMITS = 512  # ffe_create_walk_physics only: joint limits on (provisional opt-in, see the header)
 FFE_WALK_EPISODES = 1024  # ffe_create_walk_physics only: the walk_imitation environment with the floor off (provisional opt-in)
+FFE_WALK_FLOOR = 2048  # ffe_create_walk_physics only: the floor plane against the fly's sphere / capsule geoms, bare physics (opt-in)
 
 
 # `env.validity()`: four int32 [B] views of one [B, 4] device buffer (include/flybody_env.h, ffe_get_validity)
@@ -463,6 +464,13 @@ class BatchedWalkPhysics(EnvHandle):
     substep and `validity()`'s step_bits (and int 7 of `get_task_state()`) carry bit value 2.  `get_task_state()` ints 4 and 6 are the
     limit rows and the solver iterations of the last substep.
 
+    `floor_contacts=True` (step 3b; it implies `joint_limits`) adds FFE_WALK_FLOOR: the floor plane against the fly's 48 sphere / capsule
+    geoms, as elliptic-cone contacts with the model's noslip sweeps and the adhesion actuators (FFE_NO_NOSLIP / FFE_NO_ADHESION in
+    `physics_flags` switch those off); the fly's own contacts stay off.  Up to 16 contacts and 48 rows per env and substep, 24 rows
+    per block of the inertia; beyond that the deepest contacts are kept, rows without a column are switched off for the substep and
+    step_bits carry 1 / 2 / 4.  `get_task_state()` then also gives int 5 = floor contacts of the last substep, real 0 = the sum of
+    their normal forces, real 1 = the smallest contact distance.
+
     Tensor conventions are `BatchedBallEnv`'s: `get_state` returns float64 cuda tensors qpos[B, 109] = root position (float64 on the
     device too), root quaternion, 102 hinges and qvel[B, 108] = root linear velocity (world frame), root angular velocity (body
     frame), hinges; `set_state` takes the same and normalises the quaternion; `physics_step` takes float32 ctrl[B, 59]."""
@@ -470,9 +478,11 @@ class BatchedWalkPhysics(EnvHandle):
     task_kind = "walk_physics"
 
     def __init__(self, *, batch_size: int, device: int = 0, physics_flags: int = FFE_NO_CONTACT | FFE_NO_LIMIT, blob_path: str = WALK_BLOB,
-                 joint_limits: bool = False):
-        if joint_limits:
+                 joint_limits: bool = False, floor_contacts: bool = False):
+        if joint_limits or floor_contacts:
             physics_flags = (int(physics_flags) & ~(FFE_NO_CONTACT | FFE_NO_LIMIT)) | FFE_NO_CONTACT | FFE_WALK_JOINT_LIMITS
+        if floor_contacts:
+            physics_flags |= FFE_WALK_FLOOR
         self._open(batch_size, device)
         with open(blob_path, "rb") as f:
             blob = f.read()

@@ -18,7 +18,7 @@ PER_SOURCE_FLAGS = {
     "ball_env.hip": ["-mllvm", "-sink-insts-to-avoid-spills=1"],
     "walk_env.hip": ["-mllvm", "-sink-insts-to-avoid-spills=1"],  # the same leg code in the same kind of substep loop
 }
-HEADERS = ["handle.hpp", "env_backend.hpp", "fly_env.hpp", "dev_model.hpp", "ball_model.hpp", "ball_env.hpp", "leg_dyn.hpp", "leg_stage1.inc", "row_newton.hpp", "walk_model.hpp", "walk_env.hpp", "walk_imu.hpp", "dev_math.hpp", "convex.hpp", "launch_order.hpp", "nstep_ring.hpp", "walk_task.hpp", os.path.join("..", "..", "include", "flybody_env.h")]
+HEADERS = ["handle.hpp", "env_backend.hpp", "fly_env.hpp", "dev_model.hpp", "ball_model.hpp", "ball_env.hpp", "leg_dyn.hpp", "leg_stage1.inc", "row_newton.hpp", "walk_model.hpp", "walk_env.hpp", "walk_imu.hpp", "walk_floor.hpp", "dev_math.hpp", "convex.hpp", "launch_order.hpp", "nstep_ring.hpp", "walk_task.hpp", os.path.join("..", "..", "include", "flybody_env.h")]
 
 
 def needs_build() -> bool:

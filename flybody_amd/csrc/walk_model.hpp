@@ -11,6 +11,7 @@
 #pragma once
 
 #include "ball_model.hpp"
+#include "walk_floor.hpp"
 
 namespace ffb {
 
@@ -22,6 +23,19 @@ struct WalkExtra {
   float qpos0[7];  // free joint reference: position, quaternion
   // what step 3 of DESIGN.md section 12 will need; here it only decides what is refused
   int floor_geom, n_limited;
+  // ---- the floor plane against the fly's sphere / capsule geoms (FFE_WALK_FLOOR; lane = geom in the collision pass): the geoms that
+  //      pass mj_collision's filters against the floor geom, in model order, with the contact parameters of the pair (mj_contactParam:
+  //      friction, margin and gap the larger value, solref / solimp weighted by solmix, condim 3)
+  int f_n, f_ok;                     // geoms listed; 0 if some pair is not condim 3 or the solimp is not uniform (the bit is then refused)
+  float f_frame[9], f_off;           // mju_makeFrame of the plane's normal, in the world; normal . plane position
+  int f_geom[NL];                    // the geom's index in the model
+  int f_link[NL], f_adh[NL], f_blk[NL], f_amask[NL];  // link of the geom, its adhesion actuator (-1: none), block and dof mask of its chain
+  float f_pos[3][NL], f_axis[3][NL], f_rad[NL], f_half[NL], f_fric[NL], f_K[NL], f_B[NL], f_margin[NL], f_gap[NL], f_invw[NL];
+  float f_solimp[5];
+  // No geom of the table can touch the floor while the root origin is higher than this over the plane, whatever the joint angles:
+  // the largest margin + over the geoms (the lengths of the link offsets down its chain + |local centre| + half length + radius),
+  // rounded up.  Above it a substep of the floor kernel is the limits kernel's substep.
+  float f_reach;
 };
 
 struct WalkModel {
@@ -35,6 +49,39 @@ struct WalkHost {
   double root_mass = 0, total_mass = 0;
   int nq = 109, nv = 108;
 };
+
+// One floor candidate in float64: the geom in its link's frame and the contact parameters of the pair (floor geom `fg`, geom `g`) by
+// mj_contactParam (geom1 = the floor): friction, margin and gap the larger value, solref / solimp weighted by solmix.  The device table
+// holds these rounded to float32; tests/walk_floor_host.cpp reads them unrounded.
+struct FloorGeom {
+  double pos[3], axis[3], rad, half, fric, K, B, margin, gap, invw, solimp[5];
+  int condim;
+};
+inline FloorGeom floor_geom_params(const Blob &b, int fg, int g) {
+  using namespace detail;
+  const Tensor &gbody = b.get("geom_bodyid"), &gtype = b.get("geom_type"), &gsize = b.get("geom_size"), &gpos = b.get("geom_pos"),
+               &gquat = b.get("geom_quat"), &gfric = b.get("geom_friction"), &gmargin = b.get("geom_margin"), &ggap = b.get("geom_gap"),
+               &gsolref = b.get("geom_solref"), &gsolimp = b.get("geom_solimp"), &gsolmix = b.get("geom_solmix"), &gcondim = b.get("geom_condim"),
+               &binvw = b.get("body_invweight0");
+  FloorGeom o;
+  double q[4] = {gquat.f(4 * g), gquat.f(4 * g + 1), gquat.f(4 * g + 2), gquat.f(4 * g + 3)}, mm[9];
+  q2m(q, mm);
+  for (int k = 0; k < 3; k++) { o.pos[k] = gpos.f(3 * g + k); o.axis[k] = mm[3 * k + 2]; }
+  o.rad = gsize.f(3 * g); o.half = gtype.i(g) == 3 ? gsize.f(3 * g + 1) : 0.0;
+  o.margin = std::max(gmargin.f(g), gmargin.f(fg)); o.gap = std::max(ggap.f(g), ggap.f(fg));
+  o.fric = std::max(gfric.f(3 * g), gfric.f(3 * fg));
+  o.condim = std::max(gcondim.i(g), gcondim.i(fg));
+  const double s1 = gsolmix.f(fg), s2 = gsolmix.f(g);
+  const double mix = (s1 >= 1e-15 && s2 >= 1e-15) ? s1 / (s1 + s2) : ((s1 < 1e-15 && s2 < 1e-15) ? 0.5 : (s1 < 1e-15 ? 0.0 : 1.0));
+  double sr[2];
+  for (int k = 0; k < 2; k++)
+    sr[k] = (gsolref.f(2 * fg) > 0 && gsolref.f(2 * g) > 0) ? mix * gsolref.f(2 * fg + k) + (1 - mix) * gsolref.f(2 * g + k)
+                                                             : std::min(gsolref.f(2 * fg + k), gsolref.f(2 * g + k));
+  for (int k = 0; k < 5; k++) o.solimp[k] = mix * gsolimp.f(5 * fg + k) + (1 - mix) * gsolimp.f(5 * g + k);
+  kb(sr[0], sr[1], o.solimp[1], b.get("opt").f(0), &o.K, &o.B);
+  o.invw = binvw.f(2 * gbody.i(fg)) + binvw.f(2 * gbody.i(g));
+  return o;
+}
 
 inline WalkHost build_walk_model(const Blob &b) {
   using namespace detail;
@@ -120,6 +167,57 @@ inline WalkHost build_walk_model(const Blob &b) {
     for (int g = 0; g < (int)gbody.count; g++) if (gbody.i(g) == 0 && gtype.i(g) == 0) X.floor_geom = g;
     if (X.floor_geom < 0) throw std::runtime_error("walk model: floor plane missing");
     for (int j = 1; j < (int)jlim.count; j++) X.n_limited += jlim.i(j) ? 1 : 0;
+  }
+  // ---- floor contacts: one table row per primitive geom that can touch the floor
+  {
+    const Tensor &gbody = b.get("geom_bodyid"), &gtype = b.get("geom_type"), &gsize = b.get("geom_size"), &gpos = b.get("geom_pos"),
+                 &gquat = b.get("geom_quat"), &gct = b.get("geom_contype"), &gca = b.get("geom_conaffinity"), &excl = b.get("exclude_pairs");
+    (void)gsize;
+    const int fg = X.floor_geom, nex = (int)excl.count / 2;
+    {
+      double q[4] = {gquat.f(4 * fg), gquat.f(4 * fg + 1), gquat.f(4 * fg + 2), gquat.f(4 * fg + 3)}, mm[9], wq[4], wp[3], fr[9];
+      // (the floor hangs on the world body: its frame in the world is its frame in that body)
+      const double bq[4] = {bquat.f(0), bquat.f(1), bquat.f(2), bquat.f(3)}, gp[3] = {gpos.f(3 * fg), gpos.f(3 * fg + 1), gpos.f(3 * fg + 2)};
+      qmul(bq, q, wq);
+      q2m(wq, mm);
+      rot(bq, gp, wp);
+      for (int k = 0; k < 3; k++) { fr[k] = mm[3 * k + 2]; wp[k] += bpos.f(k); }
+      wf::make_frame(fr);
+      for (int k = 0; k < 9; k++) X.f_frame[k] = (float)fr[k];
+      X.f_off = (float)(fr[0] * wp[0] + fr[1] * wp[1] + fr[2] * wp[2]);
+    }
+    std::vector<int> lane_of((size_t)nb, -1);
+    for (int l = 0; l < NL; l++) lane_of[(size_t)M.l_body[l]] = l;
+    X.f_ok = 1;
+    for (int l = 0; l < NL; l++) { X.f_link[l] = -1; X.f_adh[l] = -1; }
+    for (int g = 0; g < (int)gbody.count; g++) {
+      const int body = gbody.i(g), l = lane_of[(size_t)body], ty = gtype.i(g);
+      if (l < 0 || (ty != 2 && ty != 3)) continue;  // a plane against an ellipsoid or a cylinder is not built
+      if (!((gct.i(fg) & gca.i(g)) || (gct.i(g) & gca.i(fg)))) continue;
+      bool skip = false;
+      for (int e = 0; e < nex; e++) skip |= (excl.i(2 * e) == 0 && excl.i(2 * e + 1) == body) || (excl.i(2 * e) == body && excl.i(2 * e + 1) == 0);
+      if (skip) continue;
+      if (X.f_n >= NL) throw std::runtime_error("walk model: more floor candidates than lanes");
+      const int s = X.f_n++;
+      const FloorGeom fp = floor_geom_params(b, fg, g);
+      X.f_geom[s] = g; X.f_link[s] = l; X.f_adh[s] = M.l_adh[l];
+      const int last = M.s_dof[M.l_ndof[l] - 1][l];
+      X.f_blk[s] = M.d_blk[last]; X.f_amask[s] = M.d_amask[last];
+      for (int k = 0; k < 3; k++) { X.f_pos[k][s] = (float)fp.pos[k]; X.f_axis[k][s] = (float)fp.axis[k]; }
+      X.f_rad[s] = (float)fp.rad; X.f_half[s] = (float)fp.half; X.f_margin[s] = (float)fp.margin; X.f_gap[s] = (float)fp.gap;
+      X.f_fric[s] = (float)fp.fric; X.f_K[s] = (float)fp.K; X.f_B[s] = (float)fp.B; X.f_invw[s] = (float)fp.invw;
+      {
+        double reach = std::sqrt(fp.pos[0] * fp.pos[0] + fp.pos[1] * fp.pos[1] + fp.pos[2] * fp.pos[2]) + fp.half + fp.rad + fp.margin;
+        for (int a = l; a >= 0; a = M.l_parent[a])
+          reach += std::sqrt((double)M.l_pos[0][a] * M.l_pos[0][a] + (double)M.l_pos[1][a] * M.l_pos[1][a] + (double)M.l_pos[2][a] * M.l_pos[2][a]);
+        X.f_reach = std::max(X.f_reach, (float)(1.001 * reach + 1e-6));
+      }
+      if (fp.condim != 3) X.f_ok = 0;
+      for (int k = 0; k < 5; k++) {
+        if (s == 0) X.f_solimp[k] = (float)fp.solimp[k];
+        else if (X.f_solimp[k] != (float)fp.solimp[k]) X.f_ok = 0;
+      }
+    }
   }
   return W;
 }

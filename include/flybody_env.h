@@ -65,7 +65,12 @@ enum {
   /* ffe_create_walk_physics only: the handle is the walk_imitation environment with the floor off (sensors, episode protocol, task
    * layer; the third step kernel of csrc/walk_env.hip).  Accepted only as FFE_NO_CONTACT | FFE_WALK_JOINT_LIMITS | FFE_WALK_EPISODES
    * plus force switches.  An opt-in bit and provisional for the same reason: it goes when floor contacts land. */
-  FFE_WALK_EPISODES = 1024
+  FFE_WALK_EPISODES = 1024,
+  /* ffe_create_walk_physics only: the floor plane against the fly's sphere and capsule geoms, on the bare-physics handle (the fourth
+   * step kernel of csrc/walk_env.hip).  Accepted only as FFE_NO_CONTACT | FFE_WALK_JOINT_LIMITS | FFE_WALK_FLOOR plus force switches,
+   * FFE_NO_NOSLIP and FFE_NO_ADHESION; on such a handle FFE_NO_CONTACT keeps meaning "the fly's own contacts are off" (they are not
+   * built).  An opt-in bit and provisional as the two above. */
+  FFE_WALK_FLOOR = 2048
 };
 
 typedef struct ffe_walk_task_s ffe_walk_task; /* the walk_imitation task layer's inputs, defined with ffe_walktask_create below */
@@ -146,12 +151,17 @@ int ffe_create_walk_on_ball(const void *model_blob, size_t blob_size, const ffe_
  * filtered actuators) as bare physics: smooth dynamics on the device with constraints off ("dynamics only", as ffe_physics_step offers
  * for the other two tasks), or with the joint limits of its 102 hinges on (FFE_WALK_JOINT_LIMITS); and, with FFE_WALK_EPISODES on top
  * of that, the walk_imitation environment itself with the floor off: sensors, observation row, reward, termination and the episode
- * protocol on the device, a fly that falls freely (or floats with FFE_NO_GRAVITY).  Floor contacts are not built yet. */
+ * protocol on the device, a fly that falls freely (or floats with FFE_NO_GRAVITY).  Floor contacts exist on the bare-physics handle
+ * alone (FFE_WALK_FLOOR): the floor plane against the fly's 48 sphere / capsule geoms, elliptic cones, noslip and adhesion; the fly's
+ * own contacts, the floor against ellipsoids and cylinders, and the floor under FFE_WALK_EPISODES are not built yet. */
 typedef struct {
   /* FFE_NO_CONTACT and exactly one of FFE_NO_LIMIT (smooth dynamics alone) or FFE_WALK_JOINT_LIMITS (joint limits on: up to 48 limit
    * rows per env and substep), plus any of the force switches FFE_NO_FLUID / _DAMPER / _SPRING / _GRAVITY / _ACTUATION; every other
    * set is refused (the text names FFE_WALK_JOINT_LIMITS when that bit was passed).  FFE_WALK_EPISODES is accepted only together with
-   * FFE_NO_CONTACT | FFE_WALK_JOINT_LIMITS (plus force switches); every other set with it is refused with a text naming it */
+   * FFE_NO_CONTACT | FFE_WALK_JOINT_LIMITS (plus force switches); every other set with it is refused with a text naming it.
+   * FFE_WALK_FLOOR is accepted only as FFE_NO_CONTACT | FFE_WALK_JOINT_LIMITS | FFE_WALK_FLOOR plus force switches, FFE_NO_NOSLIP and
+   * FFE_NO_ADHESION (meaningful only with this bit); every other set with it - with FFE_WALK_EPISODES, with FFE_NO_LIMIT, without
+   * FFE_WALK_JOINT_LIMITS - is refused with a text naming FFE_WALK_FLOOR */
   int32_t physics_flags;
   /* read only when physics_flags has FFE_WALK_EPISODES (a caller without the bit may pass the one int above alone) */
   const ffe_walk_task *task;  /* clips, tracked joints / sites, reward and termination constants: a float32 task layer of the env's
@@ -177,6 +187,12 @@ typedef struct {
  *   ffe_get_task_state  int 4 = limit rows instantiated in the last substep, int 6 = solver iterations of the last substep, int 7 =
  *                       the same overflow bits; every other int and every real zero
  * and all of them are zero until the first ffe_physics_step.
+ * A handle created with FFE_WALK_FLOOR reports the same and on top of it:
+ *   ffe_get_validity    column 0 also carries walk_on_ball's other two bits: 1 = more floor contacts than slots (16; the deepest were
+ *                       kept), 4 = more rows in one block of the inertia than columns (24; the rows without a column were switched
+ *                       off for that substep); bit value 2 counts contact and limit rows together (48)
+ *   ffe_get_task_state  int 5 = floor contacts kept in the last substep, real 0 = the sum of their normal forces, real 1 = the
+ *                       smallest contact distance (0 without a contact)
  * A handle created with FFE_WALK_EPISODES is an environment (everything above still works on it): ffe_reset, ffe_reset_envs, ffe_step,
  * ffe_force_next_episode (the clip; the phase array is ignored), ffe_time_steps and ffe_time_kernel work as on a walk_on_ball handle,
  * and ffe_spec reports obs_dim 741 with the offsets of the row: accelerometer 3 | actuator_activation 59 | appendages_pos 21 |
