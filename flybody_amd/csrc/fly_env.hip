@@ -474,6 +474,11 @@ __device__ unsigned long long g_trace[32768][4];
 #define TRACE_HI(c) 0
 #define TRACE_END(slot, tr_extra, tr_hi) do {} while (0)
 #endif
+// A wave that meets heavy work - the second collision pass, or a second factorisation within one substep - raises its issue priority
+// for the rest of its life (set again at every such point: one instruction inside a branch the wave takes anyway).  These are the
+// waves the launch order could not foresee; the ones among them that start in the second round are the youngest on their SIMD, get
+// the leftover issue slots and end the launch.
+#define HEAVY_PRIO() __builtin_amdgcn_s_setprio(3)
 // timing-only ablation switches (bench experiments; results are wrong when set)
 // The in-kernel ones exist only in the -DFFE_ABLATION diagnostic build (tools/ablate.py); the shipped kernel carries neither the
 // branches nor the flag bits through its loops.
@@ -711,6 +716,7 @@ __device__ __forceinline__ void flight_collide(Ctx &c) {
 #endif
   int r = __builtin_amdgcn_readfirstlane(flight_collide_a<MC>(&T, c.Mp, lane, c.sd_cnt, c.sd_pid));
   if (r & 0x40000000) {
+    HEAVY_PRIO();
     r = __builtin_amdgcn_readfirstlane(flight_collide_b<MC>(&T, c.Mp, lane, r));
     c.nrare++;
   }
@@ -1341,7 +1347,7 @@ __device__ __forceinline__ V3 stage2(Ctx &c, float qfrc_act, bool integrate, boo
       bool need_y0 = false;
       if (lim_changed) {
         if (it == 0) bfactor<true>(c, add, hB);
-        else bfactor<false>(c, add, 0.f);
+        else { HEAVY_PRIO(); bfactor<false>(c, add, 0.f); }
         c.nfac++;
         need_y0 = true;
         ymask = 0u;

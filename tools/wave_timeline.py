@@ -3,7 +3,7 @@ every wave's start / end time (100 MHz reference clock ticks) and hardware slot.
 of resident waves over time and per-CU slot use.   python tools/wave_timeline.py [flight|ball] [batch]"""
 import ctypes as C, os, sys
 sys.path.insert(0, os.path.join(os.path.dirname(__file__), ".."))
-os.environ["FLYBODY_ENV_LIB"] = os.path.join(os.path.dirname(__file__), "..", "flybody_amd", "csrc", "variants", "libflybody_env_trace.so")
+os.environ.setdefault("FLYBODY_ENV_LIB", os.path.join(os.path.dirname(__file__), "..", "flybody_amd", "csrc", "variants", "libflybody_env_trace.so"))
 import numpy as np, torch
 from flybody_amd import _capi, fly_envs
 from flybody_amd.batched_env import BatchedFlyEnv
@@ -37,6 +37,8 @@ t0 = buf[:, 0].astype(np.int64); t1 = buf[:, 1].astype(np.int64); hw = buf[:, 2]
 b = t0.min(); t0 -= b; t1 -= b  # s_memrealtime: the 100 MHz reference clock, common to all XCDs (10 ns ticks)
 life = t1 - t0; span = t1.max()
 print(f"{which} B={B}: launch span {span} ticks (longest XCD; per XCD: {[int(t1[xcc == x].max()) for x in np.unique(xcc)]})")
+ends = np.array([int(t1[xcc == x].max()) for x in np.unique(xcc)])
+print(f"envs stepped per XCD: {[int((xcc == x).sum()) for x in np.unique(xcc)]} (B / 8 = {B / 8:g}); longest XCD / mean of the XCDs = {ends.max() / ends.mean():.4f}")
 print(f"wave lifetime mean {life.mean():.0f}  p10 {np.percentile(life, 10):.0f}  p50 {np.percentile(life, 50):.0f}  p90 {np.percentile(life, 90):.0f}  "
       f"max {life.max()};  sum(lifetimes) / span = {life.sum() / span:.0f} resident waves on average")
 cu = (hw >> 8) & 0xf; se = (hw >> 13) & 0x7; sh = (hw >> 12) & 1; simd = (hw >> 4) & 3; slot = hw & 0xf
