@@ -26,7 +26,8 @@ WALK_BLOB = os.path.join(_ASSETS, "fly_walk.ffmb")
 FFE_NO_LIMIT, FFE_NO_CONTACT = 2, 64  # include/flybody_env.h
 FFE_WALK_JOINT_LIMITS = 512  # ffe_create_walk_physics only: joint limits on (provisional opt-in, see the header)
 FFE_WALK_EPISODES = 1024  # ffe_create_walk_physics only: the walk_imitation environment with the floor off (provisional opt-in)
-FFE_WALK_FLOOR = 2048  # ffe_create_walk_physics only: the floor plane against the fly's sphere / capsule geoms, bare physics (opt-in)
+FFE_WALK_FLOOR = 2048  # ffe_create_walk_physics only: the floor plane against the fly's sphere / capsule geoms (opt-in; bare physics, or
+#                        with FFE_WALK_EPISODES the walk_imitation environment on the floor)
 
 
 # `env.validity()`: four int32 [B] views of one [B, 4] device buffer (include/flybody_env.h, ffe_get_validity)
@@ -386,12 +387,22 @@ class BatchedBallEnv(BatchedFlyEnv):
 
 
 class BatchedWalkEnv(BatchedFlyEnv):
-    """B independent `walk_imitation` environments (`fly_envs.py:75-122`) on one MI355X **with the floor off**: the free-root walking
-    fly (10 physics substeps with joint limits and filtered actuators per control step), the thorax IMU, the DeepMimic reward against
-    a reference clip, termination and auto-reset, all on the device.  Without floor contacts the fly falls freely (or floats with
-    FFE_NO_GRAVITY in `physics_flags`); force and touch read zero.  The float64 oracle does the same with contacts switched off, so
-    every row can be compared with it.  Same dm_env surface and hooks as `BatchedBallEnv`; one `step()` is five launches (DESIGN.md
-    section 12, step 4b).
+    """B independent `walk_imitation` environments (`fly_envs.py:75-122`) on one MI355X: the free-root walking fly (10 physics
+    substeps with joint limits and filtered actuators per control step), the thorax IMU, the DeepMimic reward against a reference
+    clip, termination and auto-reset, all on the device.  Same dm_env surface and hooks as `BatchedBallEnv`; one `step()` is five
+    launches.
+
+    `floor_contacts=False` (the default): **the floor is off**.  The fly falls freely (or floats with FFE_NO_GRAVITY in
+    `physics_flags`); force and touch read exact zeros.  The float64 oracle does the same with contacts switched off, so every row can
+    be compared with it.
+
+    `floor_contacts=True` adds FFE_WALK_FLOOR: the floor plane against the fly's 48 sphere / capsule geoms, as in
+    `BatchedWalkPhysics(floor_contacts=True)` (elliptic cones, the model's noslip sweeps, the adhesion actuators; `physics_flags` may
+    then also carry FFE_NO_NOSLIP / FFE_NO_ADHESION), with the 18 force and 6 touch columns live: the force sensors read the
+    interaction force on each tarsus (inertial without a contact, so not zero), touch the normal forces on each claw.  The fly's own
+    contacts, and the plane against ellipsoids and cylinders, stay off.  `get_task_state()` int 5 is then the floor contacts kept in the
+    last substep, reals 0 / 1 the sum of their normal forces and the smallest distance; `validity()`'s step_bits carry the floor's
+    overflow bits 1 / 2 / 4 next to the limit bit, sticky per episode in episode_bits.
 
     `refs`: a `tasks.walking.WalkRefSet`; `view`: the `WalkModelView` that names the tracked joints and sites (None: the default
     one).  `get_state` / `set_state` / `get_act` / `set_act` / `physics_step` are `BatchedWalkPhysics`'s."""
@@ -401,7 +412,7 @@ class BatchedWalkEnv(BatchedFlyEnv):
     def __init__(self, refs, view=None, *, batch_size: int, device: int = 0, seed: int = 0, env_id_base: int = 0, future_steps: int = 64,
                  time_limit: float = 10.0, terminal_com_dist: float = 0.3, control_timestep: float = 2e-3, pad_first_obs: bool = False,
                  physics_flags: int = 0, canonical_actions: bool = False, clip_actions: bool = False, double_buffer: bool = False,
-                 inference_mode: bool = False, blob_path: str = WALK_BLOB):
+                 inference_mode: bool = False, blob_path: str = WALK_BLOB, floor_contacts: bool = False):
         import json
 
         from .model.blob import read_blob
@@ -420,9 +431,14 @@ class BatchedWalkEnv(BatchedFlyEnv):
         wtask, self._keep = make_task(view, refs, future_steps=future_steps, terminal_com_dist=terminal_com_dist, time_limit=time_limit,
                                       control_timestep=control_timestep, inference_mode=inference_mode)
         force_switches = int(physics_flags) & (1 | 4 | 8 | 16 | 32)  # FFE_NO_FLUID / _DAMPER / _SPRING / _GRAVITY / _ACTUATION
-        if int(physics_flags) & ~(force_switches | FFE_NO_CONTACT | FFE_WALK_JOINT_LIMITS | FFE_WALK_EPISODES):
+        self.floor_contacts = bool(floor_contacts)
+        if self.floor_contacts:
+            force_switches |= int(physics_flags) & (128 | 256)  # FFE_NO_NOSLIP / FFE_NO_ADHESION
+            if int(physics_flags) & ~(force_switches | FFE_NO_CONTACT | FFE_WALK_JOINT_LIMITS | FFE_WALK_EPISODES | FFE_WALK_FLOOR):
+                raise ValueError("BatchedWalkEnv(floor_contacts=True): physics_flags takes the force switches, FFE_NO_NOSLIP and FFE_NO_ADHESION only")
+        elif int(physics_flags) & ~(force_switches | FFE_NO_CONTACT | FFE_WALK_JOINT_LIMITS | FFE_WALK_EPISODES):
             raise ValueError("BatchedWalkEnv: physics_flags takes the force switches only (floor contacts are not built; joint limits are on)")
-        self.physics_flags = force_switches | FFE_NO_CONTACT | FFE_WALK_JOINT_LIMITS | FFE_WALK_EPISODES
+        self.physics_flags = force_switches | FFE_NO_CONTACT | FFE_WALK_JOINT_LIMITS | FFE_WALK_EPISODES | (FFE_WALK_FLOOR if self.floor_contacts else 0)
         task = _capi.WalkPhysicsTask(physics_flags=self.physics_flags, task=C.pointer(wtask), seed=int(seed), env_id_base=int(env_id_base),
                                      time_limit_steps=time_limit_control_steps(time_limit, h_phys, nsub), pad_first_obs=int(pad_first_obs),
                                      canonical_actions=int(canonical_actions), clip_actions=int(clip_actions))

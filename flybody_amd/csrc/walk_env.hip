@@ -13,7 +13,9 @@
 // solution with it is the solution without it plus (0, R' g) on the root alone.  It is added there, in the world frame, after the
 // solve: free fall is exact, and no gravity torque about the root origin is rounded in float32 and divided by the small rotational
 // inertias of S (which cost 2e-3 rad/s^2 of root angular acceleration when gravity went through the solve).
-// Four kernels share the code below: three of bare physics (`ffe_physics_step`; the third, `floor_step`, collides the floor plane with
+// The device code of the substep lives in walk_substeps.hpp (stage 1 is the text fragment `#include "leg_stage1.inc"` inside its `stage1`),
+// shared with walk_floor_env.hip, which holds the fifth kernel: the environment on the floor.
+// Four kernels of this file share that code: three of bare physics (`ffe_physics_step`; the third, `floor_step`, collides the floor plane with
 // the fly's sphere / capsule geoms and is described where its code starts: "floor contacts") and
 // the walk_imitation environment with the floor off (`imitation_step_kernel`, at the end of the kernel section).  `walk_step_kernel` is the smooth dynamics alone (a handle created with FFE_NO_CONTACT |
 // FFE_NO_LIMIT).  `walk_limits_kernel` (FFE_NO_CONTACT | FFE_WALK_JOINT_LIMITS) adds the joint-limit
@@ -45,1136 +47,11 @@
 #include "row_newton.hpp"
 #include "walk_imu.hpp"
 #include "walk_floor.hpp"
+#include "walk_substeps.hpp"
 
 namespace ffw {
 using namespace dm;
 using namespace ffb;
-
-// State record of the free-root handle (the tethered handle's BState is untouched).  MuJoCo's free-joint conventions: position and
-// linear velocity in the world frame, angular velocity in the body frame.
-struct alignas(16) WState {
-  double pos[3];
-  float quat[4];
-  float vlin[3], wb[3];
-  float q[NDP], v[NDP], act[64];
-  // limits handle only (zero otherwise): limit rows and solver iterations of the last substep, overflow bits of the last launch
-  // (2: some substep instantiated more limits than RMAX rows; the rows beyond were dropped for that substep)
-  int nlim, iters, step_bits, pad;
-};
-static_assert(sizeof(WState) == 1168, "the four ints fill what used to be padding");
-
-constexpr int BF_WALK_JOINT_LIMITS = 512;  // FFE_WALK_JOINT_LIMITS: host side only, the kernels do not read it
-constexpr int BF_WALK_EPISODES = 1024;     // FFE_WALK_EPISODES: host side only
-constexpr int BF_WALK_FLOOR = 2048;        // FFE_WALK_FLOOR: host side only (it selects the floor kernel)
-constexpr int LCOL = 16;                  // solve columns per block of M: a block has at most NSTEP = 14 hinges, each with one limit row
-static_assert(NSTEP <= LCOL, "a block's limit rows must fit its columns");
-
-struct alignas(16) WTile {
-  union {
-    struct { float Q[NDP], V[NDP]; };  // joint state staged for the actuators (start of stage 2)
-    float4 X4[NDP];                     // right-hand sides / solutions of the block solves
-  };
-  float dadd[NDP];                      // h * damping: only read by the stage-1 factorisation
-  float Mq[NMMAX];                      // joint-space inertia of the hinges: only read by the stage-1 factorisation
-  union {
-    float F[NDP][6];                    // crb * cdof = the hinge's column of M_rj: written by the assembly, read by stage 2
-    float lk[NL][12];                   // link exchange of the tree passes (dead once the assembly starts)
-  };
-  float Lm[NMMAX], Lh[NMMAX];           // factors of M_jj and of M_jj + h B
-  float dinv_m[NDP], dinv_h[NDP];
-  float C[NDP][6];
-  float frc[64];
-  float Y[NDP][6];                      // (M_jj + h B)^-1 M_jr
-};
-static_assert(sizeof(WTile) <= 20480, "the tile must leave room for 8 waves per CU");
-
-// Tile of the limits kernel: WTile without Y (a row lane reads its hinge's Y_m straight from the solve), with the packed G over the
-// two arrays that are dead once stage 1 has factorised (G dies with the substep), and the row tables.
-struct alignas(16) WTileL {
-  union {
-    struct { float Q[NDP], V[NDP]; };
-    float4 X4[NDP];
-  };
-  union {
-    struct { float dadd[NDP]; float Mq[NMMAX]; };
-    float G[RMAX * (RMAX + 1) / 2];     // G = J M^-1 J' over the limit rows, lower triangle packed by rows (lane r owns row r)
-    float S[RMAX * (RMAX + 1) / 2];     // the Newton transposes its factor through the same floats once G sits in registers
-  };
-  union {
-    float F[NDP][6];
-    float lk[NL][12];
-  };
-  float Lm[NMMAX], Lh[NMMAX];
-  float dinv_m[NDP], dinv_h[NDP];
-  float C[NDP][6];
-  float frc[64];
-  float r_y0[RMAX], r_D[RMAX], r_f[RMAX], r_sgn[RMAX];
-  unsigned char r_dof[RMAX], r_blk[RMAX], r_col[RMAX], rowof[NBLK][LCOL];
-};
-static_assert(sizeof(WTileL) <= 20480, "the tile must leave room for 8 waves per CU");
-
-// Tile of the floor kernel (FFE_WALK_FLOOR): the limits kernel's with the tethered kernel's capacities (NC
-// contacts, KCOL columns per block), the contact tables, and the link poses of the collision pass over the floats of G, which are dead
-// between the factorisation of stage 1 and the G build of stage 2.  What a contact row needs of its geom is read from the model tables
-// through c_geom; the rows' Jacobian entries are evaluated where they are used, as in the tethered kernel.
-struct alignas(16) WTileF {
-  static constexpr bool kFloor = true;
-  union {
-    struct { float Q[NDP], V[NDP]; };
-    float4 X4[NDP];
-  };
-  union {
-    struct { float dadd[NDP]; float Mq[NMMAX]; };
-    float G[RMAX * (RMAX + 1) / 2];
-    float S[RMAX * (RMAX + 1) / 2];
-    float lp[NL][14];                   // collision pass: link position 3, quaternion 4, spatial velocity 6
-  };
-  union {
-    float F[NDP][6];
-    float lk[NL][12];
-  };
-  float Lm[NMMAX], Lh[NMMAX];
-  float dinv_m[NDP], dinv_h[NDP];
-  float C[NDP][6];
-  float frc[64];
-  float r_y0[RMAX], r_D[RMAX], r_f[RMAX], r_sgn[RMAX], r_lam[RMAX];
-  unsigned char r_dof[RMAX], r_blk[RMAX], r_col[RMAX], rowof[NBLK][KCOL];
-  float c_pos[NC][3], c_vel[NC][3], c_dist[NC], c_D[NC], c_mu[NC], c_w[NC];  // point, its velocity (root frame), distance; cone tables; adhesion pull
-  unsigned short c_amask[NC];
-  unsigned char c_geom[NC], c_excl[NC], c_link[NC], c_blk[NC];
-  // adhesion pull + constraint force on the root coordinates (w_b, v_b): joins the Euler solve's root right-hand side; [6] = the sum of
-  // the contacts' normal forces.  In the tile, not in registers: uniform values that live from the row build to the end of the substep
-  float rootf[8];
-  int step_bits;  // overflow bits of the launch so far (beyond the far substep's tile: both kinds of substep leave it alone)
-};
-static_assert(offsetof(WTileF, step_bits) >= sizeof(WTileL), "the far substep must not reach the launch's overflow bits");
-static_assert(sizeof(WTileF) <= 20480, "the tile must leave room for 8 waves per CU");
-static_assert(sizeof(float[NL][14]) <= sizeof(float[RMAX * (RMAX + 1) / 2]), "the link poses must fit over G");
-// The limits kernel's tile under a name of the floor kernel's own: a floor substep with no floor in reach runs the limits kernel's code
-// as an instantiation apart (sharing the limits kernel's own instantiation changed that kernel's register allocation).
-struct alignas(16) WTileFar : WTileL {};
-static_assert(sizeof(WTileFar) <= sizeof(WTileF), "the far substep runs inside the floor tile");
-template <class T, class = void>
-struct is_floor_tile : std::false_type {};
-template <class T>
-struct is_floor_tile<T, std::enable_if_t<T::kFloor>> : std::true_type {};
-// what a floor wave carries from stage to stage and reports (per env, in a buffer of the handle)
-struct FloorCtx {
-  int nc;          // contacts kept in this substep
-  float mind;      // smallest distance
-};
-struct FloorRec { int ncon; float fsum, mind; int pad; };
-
-// Tile of the episode kernel: the limits kernel's, plus the sensor sums of a control step (accelerometer 3, gyro 3, velocimeter 3,
-// force 18, touch 6: the order of the oracle's buffer)
-struct alignas(16) WTileE : WTileL {
-  float sens[36];
-  float qsave[3][64];  // the hinges' right-hand side, parked while the qacc solve runs (three fewer live registers per lane there)
-};
-static_assert(sizeof(WTileE) <= 20480, "the tile must leave room for 8 waves per CU");
-
-// What the episode kernel reads besides the model and the state: fixed at create, in device memory, fetched by scalar loads where it
-// is used (as kernel arguments its thirty dwords stayed in SGPRs over the whole substep loop and spilled into VGPR lanes).
-struct ImitArgs {
-  const double *pose;    // [B][109] qpos of ffe_walktask_reference_pose(clip, 0): what a reset row starts from
-  const int *flag;       // [B] 0 = step, 1 = reset, 2 = leave the env alone (ffe_reset_envs, mask byte 0)
-  double *qpos, *qvel;   // [B][109], [B][108] in the ffe_get_state layout, for the task layer
-  float *term;           // [B][4]: |velocimeter|, |gyro| and sum qacc^2 of the last substep (not the means), 0
-  int obs_dim, off_act, off_force, off_gyro, off_touch, off_velocimeter;  // (the accelerometer heads the row)
-  int canonical, clip, pad_first_obs;
-  float site_pos[3], site_quat[4];  // the IMU site in the root frame
-};
-// ... and what changes from call to call
-struct ImitCall {
-  const ImitArgs *a;
-  const float *action;   // [B][NACT] raw (or canonical) actions; not read by a reset row
-  float *obs;            // [B][obs_dim]: the 92 physics columns are written here
-};
-struct NoEpisode {};  // the bare-physics kernels: no episode code is compiled
-struct FloorCall { FloorRec *rec; };  // the floor kernel (bare physics too): where a wave reports its contacts
-
-template <class Tile>
-struct CtxT {
-  const BallModel *M;
-  const WalkExtra FFE_GLOBAL *X;
-  Tile *T;
-  int lane, flags;
-  unsigned lpack;
-  int sdof[3];
-  float q[3], v[3], fnb[3];
-  int xh;
-  V3 xp, xip;
-  Q4 xq;
-  S6 cvel, caccb;
-  float mass;
-  // root
-  Q4 rq;        // orientation
-  V3 vw, wb;    // linear velocity in the world frame, angular velocity in the body frame
-  double pos[3];
-  S6 V0;        // (w_b, R' v_w)
-  I10 Itree;    // spatial inertia of the whole tree about the root origin = M_rr
-  S6 Ftot;      // bias force of the whole tree without gravity = -(root rows of the smooth force)
-  int overflow; // limits kernel: overflow bits of this launch
-  std::conditional_t<is_floor_tile<Tile>::value, FloorCtx, NoEpisode> fl;
-};
-
-// ------------------------------------------------------------------------------------------------ stage 1
-template <class C>  // (a template so that the fragment's tethered branches are discarded, not compiled)
-__device__ __forceinline__ void stage1(C &c) {
-  constexpr bool FREE_ROOT = true;
-  auto &T = *c.T;
-  const BallModel FFE_GLOBAL &M = model(c);
-  {
-    const M3 R = q2m(c.rq);
-    c.V0 = mk6(c.wb, mtv(R, c.vw));
-  }
-#include "leg_stage1.inc"
-  (void)xmat;
-  // the root link itself: uniform across the wave
-  {
-    const WalkExtra FFE_GLOBAL &X = *c.X;
-    const I10 I0 = {X.r_cin[0], X.r_cin[1], X.r_cin[2], X.r_cin[3], X.r_cin[4], X.r_cin[5], X.r_cin[6], X.r_cin[7], X.r_cin[8], X.r_cin[9]};
-    S6 f0 = cross_force(c.V0, mul_inert(I0, c.V0));
-    if (!(c.flags & BF_NO_FLUID)) {
-      float fl[8];
-#pragma unroll
-      for (int k = 0; k < 8; k++) fl[k] = X.r_fl[k];
-      f0 = f0 - box_drag(fl, q2m(Q4{X.r_iquat[0], X.r_iquat[1], X.r_iquat[2], X.r_iquat[3]}), V3{X.r_ipos[0], X.r_ipos[1], X.r_ipos[2]}, c.V0);
-    }
-    c.Itree = add10(c.Itree, I0);
-    c.Ftot = c.Ftot + f0;
-  }
-}
-
-// ------------------------------------------------------------------------------------------------ 6 x 6 root system
-__device__ __forceinline__ float comp(const S6 &v, int k) { return k == 0 ? v.a0 : (k == 1 ? v.a1 : (k == 2 ? v.a2 : (k == 3 ? v.l0 : (k == 4 ? v.l1 : v.l2)))); }
-
-// Schur complement S = M_rr - M_rj Y (lower triangle) and right-hand side b_r = f_r - M_rj z: wave sums of the lanes' own hinges
-template <class C>
-__device__ __forceinline__ void schur(const C &c, const S6 (&mrj)[3], const S6 (&y)[3], const float (&z)[3], float (&Sm)[6][6], float (&br)[6]) {
-  // M_rr from the tree's spatial inertia: column k = I e_k
-#pragma unroll
-  for (int k = 0; k < 6; k++) {
-    const S6 e = {k == 0 ? 1.f : 0.f, k == 1 ? 1.f : 0.f, k == 2 ? 1.f : 0.f, k == 3 ? 1.f : 0.f, k == 4 ? 1.f : 0.f, k == 5 ? 1.f : 0.f};
-    const S6 col = mul_inert(c.Itree, e);
-#pragma unroll
-    for (int r = 0; r < 6; r++) Sm[r][k] = comp(col, r);
-  }
-#pragma unroll
-  for (int a = 0; a < 6; a++) {
-#pragma unroll
-    for (int b = 0; b <= a; b++) {
-      float p = 0.f;
-#pragma unroll
-      for (int s = 0; s < 3; s++) p += comp(mrj[s], a) * comp(y[s], b);
-      Sm[a][b] -= wave_sum(p);
-    }
-    float p = 0.f;
-#pragma unroll
-    for (int s = 0; s < 3; s++) p += comp(mrj[s], a) * z[s];
-    br[a] = -comp(c.Ftot, a) - wave_sum(p);
-  }
-}
-
-// S = L L' in place (lower triangle, in registers, uniform); id = 1 / diag(L)
-__device__ __forceinline__ void chol6(float (&Sm)[6][6], float (&id)[6]) {
-#pragma unroll
-  for (int j = 0; j < 6; j++) {
-    float d = Sm[j][j];
-#pragma unroll
-    for (int k = 0; k < j; k++) d -= Sm[j][k] * Sm[j][k];
-    const float r = __builtin_amdgcn_rsqf(d);
-    const float ir = r * (1.5f - 0.5f * d * r * r);  // 1 / sqrt(d), one Newton step
-    id[j] = ir;
-    Sm[j][j] = d * ir;
-#pragma unroll
-    for (int i = j + 1; i < 6; i++) {
-      float e = Sm[i][j];
-#pragma unroll
-      for (int k = 0; k < j; k++) e -= Sm[i][k] * Sm[j][k];
-      Sm[i][j] = e * ir;
-    }
-  }
-}
-__device__ __forceinline__ void chol6_forward(const float (&Sm)[6][6], const float (&id)[6], const float (&b)[6], float (&x)[6]) {  // L x = b
-#pragma unroll
-  for (int i = 0; i < 6; i++) {
-    float w = b[i];
-#pragma unroll
-    for (int k = 0; k < i; k++) w -= Sm[i][k] * x[k];
-    x[i] = w * id[i];
-  }
-}
-__device__ __forceinline__ void chol6_backward(const float (&Sm)[6][6], const float (&id)[6], float (&x)[6]) {  // L' x = w, in place
-#pragma unroll
-  for (int i = 5; i >= 0; i--) {
-    float w = x[i];
-#pragma unroll
-    for (int k = i + 1; k < 6; k++) w -= Sm[k][i] * x[k];
-    x[i] = w * id[i];
-  }
-}
-
-// ------------------------------------------------------------------------------------------------ joint-limit rows
-// The constraint block of a substep with R > 0 limit rows (rows already in T.r_sgn / r_D / r_dof / r_blk, -aref in T.r_y0): adds the
-// hinges' constraint forces to `qs`.  Returns the solver's iterations.
-template <class C>
-__device__ __forceinline__ int limit_forces(C &c, const int R, const int (&lrow)[3], const float (&lsgn)[3], const S6 (&mrj)[3], float (&qs)[3]) {
-  WTileL &T = *c.T;
-  const int lane = c.lane;
-  const bool row = lane < R;
-  // ---- z_m = M_jj^-1 f_j and Y_m = M_jj^-1 M_jr through M's own factor; a row lane keeps its hinge's Y_m
-  S6 ym[3], yr = zero6();
-  float zm[3];
-#pragma unroll
-  for (int s = 0; s < 3; s++) if (slot_on(c, s)) T.X4[opq(c.sdof[s])] = make_float4(qs[s], mrj[s].a0, mrj[s].a1, mrj[s].a2);
-  DM_SYNC();
-  solve4(c, T.Lm, T.dinv_m);
-#pragma unroll
-  for (int s = 0; s < 3; s++) {
-    const float4 x = slot_on(c, s) ? T.X4[opq(c.sdof[s])] : make_float4(0.f, 0.f, 0.f, 0.f);
-    zm[s] = x.x; ym[s].a0 = x.y; ym[s].a1 = x.z; ym[s].a2 = x.w;
-  }
-  const int rdof = row ? (int)T.r_dof[lane] : 0;
-  if (row) { const float4 x = T.X4[rdof]; yr.a0 = x.y; yr.a1 = x.z; yr.a2 = x.w; }
-  DM_SYNC();
-#pragma unroll
-  for (int s = 0; s < 3; s++) if (slot_on(c, s)) T.X4[opq(c.sdof[s])] = make_float4(mrj[s].l0, mrj[s].l1, mrj[s].l2, 0.f);
-  DM_SYNC();
-  solve4(c, T.Lm, T.dinv_m);
-#pragma unroll
-  for (int s = 0; s < 3; s++) {
-    const float4 x = slot_on(c, s) ? T.X4[opq(c.sdof[s])] : make_float4(0.f, 0.f, 0.f, 0.f);
-    ym[s].l0 = x.x; ym[s].l1 = x.y; ym[s].l2 = x.z;
-  }
-  if (row) { const float4 x = T.X4[rdof]; yr.l0 = x.x; yr.l1 = x.y; yr.l2 = x.z; }
-  DM_SYNC();
-  // ---- S_m = L L', x_r = S_m^-1 (b_r - M_rj z_m), the hinges' smooth acceleration a_s = z_m - Y_m x_r (gravity: zero on the hinges)
-  float Sm[6][6], br[6], id[6], xr[6];
-  schur(c, mrj, ym, zm, Sm, br);
-  chol6(Sm, id);
-  chol6_forward(Sm, id, br, xr);
-  chol6_backward(Sm, id, xr);
-  float sq = 0.f;
-#pragma unroll
-  for (int s = 0; s < 3; s++) {
-    if (slot_on(c, s)) {
-      float a = zm[s];
-#pragma unroll
-      for (int k = 0; k < 6; k++) a -= comp(ym[s], k) * xr[k];
-      T.X4[opq(c.sdof[s])].x = a;
-      sq += qs[s] * a;
-    }
-  }
-  float scale2 = wave_sum(sq);  // qfrc_smooth . qacc_smooth: the scale of the solver's stopping test
-#pragma unroll
-  for (int k = 0; k < 6; k++) scale2 += br[k] * xr[k];
-  DM_SYNC();
-  const float sg = row ? T.r_sgn[lane] : 0.f;
-  if (row) T.r_y0[lane] += sg * T.X4[rdof].x;  // y0 = J a_s - aref
-  // ---- the rank-6 part of G: u_i = s_i L^-1 Y_m[f_i], G_ik = u_i . u_k
-  const int gtri = lane * (lane + 1) / 2;  // G is symmetric: row `lane` keeps its columns r2 <= lane
-  {
-    float yv[6], u[6];
-#pragma unroll
-    for (int k = 0; k < 6; k++) yv[k] = sg * comp(yr, k);
-    chol6_forward(Sm, id, yv, u);
-    for (int r2 = 0; r2 < R; r2++) {
-      float gv = 0.f;
-#pragma unroll
-      for (int k = 0; k < 6; k++) gv += u[k] * rl_f(u[k], r2);
-      if (row && r2 <= lane) T.G[gtri + r2] = gv;
-    }
-  }
-  // ---- columns: a row's column is its rank among the rows of its block (M_jj^-1 is block diagonal)
-  for (int k = lane; k < NBLK * LCOL; k += 64) (&T.rowof[0][0])[k] = 255;
-  const int myb = row ? (int)T.r_blk[lane] : -1;
-  int mycol = 0, ncol = 0;
-  for (int b = 0; b < NBLK; b++) {
-    const unsigned long long mb = __ballot(myb == b);
-    if (myb == b) mycol = __popcll(mb & ((1ull << lane) - 1ull));
-    ncol = max(ncol, (int)__popcll(mb));
-  }
-  DM_SYNC();
-  if (row) T.rowof[myb][mycol] = (unsigned char)lane;  // (mycol < NSTEP <= LCOL: one row per hinge)
-  DM_SYNC();
-#pragma unroll 1
-  for (int cb = 0; cb < ncol; cb += 4) {
-    for (int f = lane; f < ND; f += 64) T.X4[f] = make_float4(0.f, 0.f, 0.f, 0.f);
-    DM_SYNC();
-    if (row) { const int col = mycol - cb; if (col >= 0 && col < 4) (&T.X4[rdof].x)[col] = sg; }
-    DM_SYNC();
-    solve4(c, T.Lm, T.dinv_m);
-    if (row) {
-      const float4 y = T.X4[rdof];
-#pragma unroll
-      for (int q2 = 0; q2 < 4; q2++) {
-        const float av = sg * (q2 == 0 ? y.x : (q2 == 1 ? y.y : (q2 == 2 ? y.z : y.w)));
-        const int r2 = cb + q2 < LCOL ? (int)T.rowof[myb][cb + q2] : 255;
-        if (r2 <= lane) T.G[gtri + r2] += av;  // (255 = no such row)
-      }
-    }
-    DM_SYNC();
-  }
-  // ---- solve, then qfrc_constraint = s f on the hinges
-  int iters;  // (ScalarRows reads no model table and ignores the contact-row count, the noslip sweeps and the warm-start flag)
-  if (R <= 8) iters = row_newton<8, ScalarRows>(c.T, nullptr, lane, R, 0, scale2, 0, 0);
-  else if (R <= 16) iters = row_newton<16, ScalarRows>(c.T, nullptr, lane, R, 0, scale2, 0, 0);
-  else if (R <= 32) iters = row_newton<32, ScalarRows>(c.T, nullptr, lane, R, 0, scale2, 0, 0);
-  else iters = row_newton<RMAX, ScalarRows>(c.T, nullptr, lane, R, 0, scale2, 0, 0);
-#pragma unroll
-  for (int s = 0; s < 3; s++) if (lrow[s] >= 0) qs[s] += lsgn[s] * T.r_f[lrow[s]];
-  DM_SYNC();
-  return iters;
-}
-
-// ------------------------------------------------------------------------------------------------ floor contacts
-// mj: mj_collision for the pairs (floor plane, sphere / capsule of the fly): mjc_PlaneSphere at the sphere centre or at both ends of a
-// capsule's segment (mjc_PlaneCapsule), in the root frame (walk_floor.hpp).  Lane g tests geom g of the floor table against the pose
-// its link published; a contact inside the margin takes a slot in (geom, end) order.  More than NC: the NC deepest are kept.  `n` is
-// the plane's normal in the root frame, `height` the root origin's distance from the plane (float64).  Returns contacts | overflow << 8.
-// Out of line and a leaf.
-__device__ __noinline__ int floor_collide(WTileF *Tp, const WalkExtra FFE_GLOBAL *Xp, const int lane, const float px, const float py, const float pz,
-                                          const float qw, const float qx, const float qy, const float qz, const float w0, const float w1, const float w2,
-                                          const float v0, const float v1, const float v2, const float nx, const float ny, const float nz, const double height) {
-  WTileF &T = *Tp;
-  const WalkExtra FFE_GLOBAL &X = *Xp;
-  {
-    float *o = T.lp[lane];
-    o[0] = px; o[1] = py; o[2] = pz; o[3] = qw; o[4] = qx; o[5] = qy; o[6] = qz;
-    o[7] = w0; o[8] = w1; o[9] = w2; o[10] = v0; o[11] = v1; o[12] = v2;
-  }
-  DM_SYNC();
-  const float n[3] = {nx, ny, nz};
-  bool h0 = false, h1 = false;
-  float d0 = 0.f, d1 = 0.f, rad = 0.f, incl = 0.f, e0[3] = {0.f, 0.f, 0.f}, e1[3] = {0.f, 0.f, 0.f};
-  int link = 0;
-  if (lane < X.f_n) {
-    link = X.f_link[lane];
-    const float *lp = T.lp[link];
-    const M3 R = q2m(Q4{lp[3], lp[4], lp[5], lp[6]});
-    const V3 c = V3{lp[0], lp[1], lp[2]} + mv(R, V3{X.f_pos[0][lane], X.f_pos[1][lane], X.f_pos[2][lane]});
-    const V3 a = mv(R, V3{X.f_axis[0][lane], X.f_axis[1][lane], X.f_axis[2][lane]});
-    const float half = X.f_half[lane], margin = X.f_margin[lane];
-    rad = X.f_rad[lane]; incl = margin - X.f_gap[lane];
-    e0[0] = c.x + half * a.x; e0[1] = c.y + half * a.y; e0[2] = c.z + half * a.z;
-    e1[0] = c.x - half * a.x; e1[1] = c.y - half * a.y; e1[2] = c.z - half * a.z;
-    d0 = wf::plane_distance<float>(height, n, e0, rad);
-    h0 = d0 <= margin;
-    if (half > 0.f) {  // (a sphere gives one contact)
-      d1 = wf::plane_distance<float>(height, n, e1, rad);
-      h1 = d1 <= margin;
-    }
-  }
-  unsigned long long b0 = __ballot(h0), b1 = __ballot(h1);
-  int over = 0;
-  if (__popcll(b0) + __popcll(b1) > NC) {
-    // the NC deepest, ties by (lane, end): dropping a deep one lets the leg sink in until a later substep answers with an enormous force
-    over = 1;
-    int r0 = 0, r1 = 0;
-    for (unsigned long long m = b0; m; m &= m - 1) {
-      const int j = __ffsll((long long)m) - 1;
-      const float dj = __shfl(d0, j);
-      if (dj < d0 || (dj == d0 && j < lane)) r0++;
-      if (dj < d1 || (dj == d1 && j <= lane)) r1++;
-    }
-    for (unsigned long long m = b1; m; m &= m - 1) {
-      const int j = __ffsll((long long)m) - 1;
-      const float dj = __shfl(d1, j);
-      if (dj < d0 || (dj == d0 && j < lane)) r0++;
-      if (dj < d1 || (dj == d1 && j < lane)) r1++;
-    }
-    h0 = h0 && r0 < NC; h1 = h1 && r1 < NC;
-    b0 = __ballot(h0); b1 = __ballot(h1);
-  }
-  const unsigned long long lt = (1ull << lane) - 1ull;
-  const int i0 = __popcll(b0 & lt) + __popcll(b1 & lt), i1 = i0 + (h0 ? 1 : 0);
-#pragma unroll
-  for (int e = 0; e < 2; e++) {
-    const bool hit = e == 0 ? h0 : h1;
-    const int idx = e == 0 ? i0 : i1;
-    if (hit && idx < NC) {
-      const float dist = e == 0 ? d0 : d1;
-      float p[3], v[3];
-      wf::contact_position<float>(e == 0 ? e0 : e1, n, rad, dist, p);
-      wf::point_velocity<float>(&T.lp[link][7], p, v);
-      T.c_pos[idx][0] = p[0]; T.c_pos[idx][1] = p[1]; T.c_pos[idx][2] = p[2];
-      T.c_vel[idx][0] = v[0]; T.c_vel[idx][1] = v[1]; T.c_vel[idx][2] = v[2];
-      T.c_dist[idx] = dist;
-      T.c_excl[idx] = dist >= incl ? 1 : 0;  // inside the margin but not inside margin - gap: kept, exerts nothing
-      T.c_geom[idx] = (unsigned char)lane; T.c_link[idx] = (unsigned char)link;
-      T.c_blk[idx] = (unsigned char)X.f_blk[lane]; T.c_amask[idx] = (unsigned short)X.f_amask[lane];
-    }
-  }
-  DM_SYNC();
-  return min((int)(__popcll(b0) + __popcll(b1)), NC) | (over << 8);
-}
-
-// row r (0 normal, 1 / 2 tangents) of contact k on hinge f: e_r . (velocity of the contact point per unit rate of f)
-__device__ __forceinline__ float fj_row(const WTileF &T, const float (&e)[3], int k, int f) { return wf::row_hinge<float>(T.C[f], T.c_pos[k], e); }
-// sum over the contacts whose chain contains hinge f of sum_r J[k][r][f] w[3 k + r] (w: the rows' forces) or J[k][0][f] w[k] (NORMAL)
-template <bool NORMAL>
-__device__ __forceinline__ float floor_gather(const WTileF &T, const BallModel FFE_GLOBAL &M, const float (&fr)[9], int nc, int f, const float *w) {
-  const int blk = M.d_blk[f], li = M.d_li[f];
-  float acc = 0.f;
-  for (int k = 0; k < nc; k++) {
-    if ((int)T.c_blk[k] == blk && (((unsigned)T.c_amask[k] >> li) & 1u)) {
-      float v[3];
-      wf::point_velocity<float>(T.C[f], T.c_pos[k], v);
-      if constexpr (NORMAL) acc += wf::dot3<float>(&fr[0], v) * w[k];
-      else acc += wf::dot3<float>(&fr[0], v) * w[3 * k] + wf::dot3<float>(&fr[3], v) * w[3 * k + 1] + wf::dot3<float>(&fr[6], v) * w[3 * k + 2];
-    }
-  }
-  return acc;
-}
-
-// the plane's frame (rows: normal, two tangents) in the root frame: uniform, recomputed where it is used rather than kept in registers
-template <class C>
-__device__ __forceinline__ void floor_frame(const C &c, float (&fr)[9]) {
-  const WalkExtra FFE_GLOBAL &X = *c.X;
-  Q4 q = c.rq;
-  asm volatile("" : "+v"(q.w));  // (an opaque copy: a second call is a second evaluation, not nine registers kept from the first)
-  const M3 Rr = q2m(q);
-  const float Rm[9] = {Rr.m0, Rr.m1, Rr.m2, Rr.m3, Rr.m4, Rr.m5, Rr.m6, Rr.m7, Rr.m8};
-  float fw[9];
-#pragma unroll
-  for (int k = 0; k < 9; k++) fw[k] = X.f_frame[k];
-  wf::frame_in_root<float>(Rm, fw, fr);
-}
-
-// The solver stops at |grad| <= 1e-4 sqrt(scale2) (row_newton.hpp).  The free thorax turns on rotational inertias far smaller than anything
-// the tethered fly moves, so the same relative force error shows up larger in the root's angular velocity: the floor solve stops ten
-// times closer (with FFE_NO_NOSLIP, where no sweep polishes the tangential forces, the one-substep error of root_ang was 3.6e-4 at 1).
-constexpr float kFloorScale = 1e-2f;
-
-// The constraint block of a floor substep with R > 0 rows: 3 per contact (rows 0 .. 3 nc - 1: the cone blocks come first), then the
-// instantiated joint limits (already in T.r_sgn / r_D / r_dof / r_blk, -aref in T.r_y0).  ball_env.hip's stage 2 with the ball's
-// rank-3 term replaced by the root's rank-6 term:
-//   G = J_j M_jj^-1 J_j' + w S_m^-1 w',  w = J_r - J_j Y_m  (J_r = (p x e, e) on a contact row, 0 on a limit row)
-// and the three root terms a limit row never needed: the adhesion pull enters the smooth force of hinges and root before y0 is formed;
-// y0 carries the root's share of J qacc_smooth with w_b x v_b and gravity added by hand (they are outside the arrowhead solve);
-// J_r' f joins the root's right-hand side of the Euler solve (c.fl.rootf) and J_j' f the hinges' (qs).  Returns the solver's iterations.
-template <class C>
-__device__ __forceinline__ int floor_forces(C &c, const int R, const int (&lrow)[3], const float (&lsgn)[3], float (&qs)[3]) {
-  WTileF &T = *c.T;
-  const BallModel FFE_GLOBAL &M = model(c);
-  const WalkExtra FFE_GLOBAL &X = *c.X;
-  const int lane = c.lane, nc = c.fl.nc, nrc = 3 * nc;
-  const bool row = lane < R, crow = lane < nrc;
-  float er[3] = {0.f, 0.f, 0.f};  // this row's direction (a contact row's normal or tangent)
-  {
-  float fr[9];
-  floor_frame(c, fr);
-  if (crow) { const int r3 = 3 * (lane - 3 * (lane / 3)); er[0] = fr[r3]; er[1] = fr[r3 + 1]; er[2] = fr[r3 + 2]; }
-  // ---- per contact: impedance, D, friction, -aref on its three rows, and the adhesion pull (mj: mj_transmission mjTRN_BODY: -force
-  //      along the normal row, the mean over the body's contacts, the ones inside the gap included)
-  if (lane < nc) {
-    const int g = T.c_geom[lane];
-    const float dist = T.c_dist[lane], incl = X.f_margin[g] - X.f_gap[g];
-    float si_[5];
-#pragma unroll
-    for (int q2 = 0; q2 < 5; q2++) si_[q2] = X.f_solimp[q2];
-    const float imp = impedance(si_, fabsf(dist - incl));
-    const float R0 = fmaxf(1e-15f, (1.f - imp) * X.f_invw[g] * frcp(imp));
-    T.c_D[lane] = T.c_excl[lane] ? 0.f : frcp(R0);
-    T.c_mu[lane] = X.f_fric[g];
-    const float B = X.f_B[g], K = X.f_K[g];
-    T.r_y0[3 * lane] = B * wf::dot3<float>(&fr[0], T.c_vel[lane]) + K * imp * (dist - incl);
-    T.r_y0[3 * lane + 1] = B * wf::dot3<float>(&fr[3], T.c_vel[lane]);
-    T.r_y0[3 * lane + 2] = B * wf::dot3<float>(&fr[6], T.c_vel[lane]);
-    const int adh = X.f_adh[g];
-    int cnt = 0;
-    for (int j = 0; j < nc; j++) cnt += T.c_link[j] == T.c_link[lane] ? 1 : 0;
-    T.c_w[lane] = adh >= 0 ? -T.frc[adh] / (float)cnt : 0.f;
-  }
-  if (lane < RMAX) T.r_lam[lane] = 0.f;  // no warm start: a substep's result depends on its state alone
-  if (crow) T.r_blk[lane] = T.c_blk[lane / 3];
-  for (int k = lane; k < NBLK * KCOL; k += 64) (&T.rowof[0][0])[k] = 255;
-  DM_SYNC();
-  // ---- adhesion into the smooth forces of the hinges and of the root
-  {
-    float fa[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    for (int k = 0; k < nc; k++) {
-      float jr[6];
-      wf::row_root<float>(T.c_pos[k], &fr[0], jr);
-#pragma unroll
-      for (int a = 0; a < 6; a++) fa[a] += jr[a] * T.c_w[k];
-    }
-    if (lane == 0) {
-#pragma unroll
-      for (int a = 0; a < 6; a++) T.rootf[a] = fa[a];
-    }
-  }
-#pragma unroll
-  for (int s = 0; s < 3; s++) if (slot_on(c, s)) qs[s] += floor_gather<true>(T, M, fr, nc, opq(c.sdof[s]), T.c_w);
-  }
-  // ---- columns: a row's column is its rank among the rows of its block (ball_env.hip); more than KCOL rows in a block: flagged, and
-  //      the rows without a column are switched off for this substep
-  const int myb = row ? (int)T.r_blk[lane] : -1;
-  int ncol;
-  {
-    int mycol = 0;
-    for (int b = 0; b < NBLK; b++) {
-      const unsigned long long mb = __ballot(myb == b);
-      if (myb == b) mycol = __popcll(mb & ((1ull << lane) - 1ull));
-    }
-    if (row) {
-      T.r_col[lane] = (unsigned char)mycol;
-      if (mycol < KCOL) T.rowof[myb][mycol] = (unsigned char)lane;
-      mycol += 1;
-    }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) mycol = max(mycol, __shfl_xor(mycol, off));
-    ncol = min(mycol, KCOL);
-    if (mycol > KCOL) {
-      c.overflow |= 4;
-      DM_SYNC();
-      if (row && (int)T.r_col[lane] >= KCOL) { if (crow) T.c_excl[lane / 3] = 1; else T.r_D[lane] = 0.f; }
-      DM_SYNC();
-      if (lane < nc && T.c_excl[lane]) T.c_D[lane] = 0.f;
-    }
-  }
-  DM_SYNC();
-  const int mycol = row ? (int)T.r_col[lane] : 0;
-  // this row: its point, its direction, its root Jacobian; a limit row's hinge
-  const int ck = crow ? lane / 3 : 0, cr = crow ? lane - 3 * (lane / 3) : 0;
-  const int clink = crow ? (int)T.c_link[ck] : 0, cnch = crow ? M.l_nchain[clink] : 0;
-  const int rdof = (row && !crow) ? (int)T.r_dof[lane] : 0;
-  const float sg = (row && !crow) ? T.r_sgn[lane] : 0.f;
-  // ---- z_m = M_jj^-1 f_j and Y_m = M_jj^-1 M_jr through M's own factor; a row lane keeps J_j z_m and J_j Y_m of its row
-  S6 ym[3];
-  float zm[3], jz = 0.f, jy[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-  for (int s = 0; s < 3; s++) if (slot_on(c, s)) { const float *m6 = T.F[opq(c.sdof[s])]; T.X4[opq(c.sdof[s])] = make_float4(qs[s], m6[0], m6[1], m6[2]); }
-  DM_SYNC();
-  solve4(c, T.Lm, T.dinv_m);
-#pragma unroll
-  for (int s = 0; s < 3; s++) {
-    const float4 x = slot_on(c, s) ? T.X4[opq(c.sdof[s])] : make_float4(0.f, 0.f, 0.f, 0.f);
-    zm[s] = x.x; ym[s].a0 = x.y; ym[s].a1 = x.z; ym[s].a2 = x.w;
-  }
-  if (crow) {
-    for (int p = 0; p < cnch; p++) {
-      const int f = M.l_chain[p][clink];
-      const float jv = fj_row(T, er, ck, f);
-      const float4 x = T.X4[f];
-      jz += jv * x.x; jy[0] += jv * x.y; jy[1] += jv * x.z; jy[2] += jv * x.w;
-    }
-  } else if (row) { const float4 x = T.X4[rdof]; jz = sg * x.x; jy[0] = sg * x.y; jy[1] = sg * x.z; jy[2] = sg * x.w; }
-  DM_SYNC();
-#pragma unroll
-  for (int s = 0; s < 3; s++) if (slot_on(c, s)) { const float *m6 = T.F[opq(c.sdof[s])]; T.X4[opq(c.sdof[s])] = make_float4(m6[3], m6[4], m6[5], 0.f); }
-  DM_SYNC();
-  solve4(c, T.Lm, T.dinv_m);
-#pragma unroll
-  for (int s = 0; s < 3; s++) {
-    const float4 x = slot_on(c, s) ? T.X4[opq(c.sdof[s])] : make_float4(0.f, 0.f, 0.f, 0.f);
-    ym[s].l0 = x.x; ym[s].l1 = x.y; ym[s].l2 = x.z;
-  }
-  if (crow) {
-    for (int p = 0; p < cnch; p++) {
-      const int f = M.l_chain[p][clink];
-      const float jv = fj_row(T, er, ck, f);
-      const float4 x = T.X4[f];
-      jy[3] += jv * x.x; jy[4] += jv * x.y; jy[5] += jv * x.z;
-    }
-  } else if (row) { const float4 x = T.X4[rdof]; jy[3] = sg * x.x; jy[4] = sg * x.y; jy[5] = sg * x.z; }
-  DM_SYNC();
-  // ---- S_m = L L', x_r = S_m^-1 (b_r + adhesion - M_rj z_m); qfrc_smooth . qacc_smooth for the solver's stopping test
-  float Sm[6][6], br[6], id[6], xr[6];
-  {
-    S6 m6[3];
-#pragma unroll
-    for (int s = 0; s < 3; s++) m6[s] = slot_on(c, s) ? ld6(T.F[opq(c.sdof[s])]) : zero6();
-    schur(c, m6, ym, zm, Sm, br);
-  }
-#pragma unroll
-  for (int k = 0; k < 6; k++) br[k] += T.rootf[k];
-  chol6(Sm, id);
-  chol6_forward(Sm, id, br, xr);
-  chol6_backward(Sm, id, xr);
-  float sq = 0.f;
-#pragma unroll
-  for (int s = 0; s < 3; s++) {
-    if (slot_on(c, s)) {
-      float a = zm[s];
-#pragma unroll
-      for (int k = 0; k < 6; k++) a -= comp(ym[s], k) * xr[k];
-      sq += qs[s] * a;
-    }
-  }
-  float scale2 = wave_sum(sq);
-#pragma unroll
-  for (int k = 0; k < 6; k++) scale2 += br[k] * xr[k];
-  scale2 *= kFloorScale;
-  // ---- y0 = J qacc_smooth - aref: the hinges' share J_j (z_m - Y_m x_r), the root's share with w_b x v_b and gravity by hand
-  if (row) {
-    float y = jz;
-#pragma unroll
-    for (int k = 0; k < 6; k++) y -= jy[k] * xr[k];
-    if (crow) {
-      const M3 Rr = q2m(c.rq);
-      const V3 g3 = (c.flags & BF_NO_GRAVITY) ? V3{0.f, 0.f, 0.f} : mtv(Rr, V3{0.f, 0.f, M.gz});
-      const float wb[3] = {c.V0.a0, c.V0.a1, c.V0.a2}, vb[3] = {c.V0.l0, c.V0.l1, c.V0.l2}, gb[3] = {g3.x, g3.y, g3.z};
-      float jr[6];
-      wf::row_root<float>(T.c_pos[ck], er, jr);
-      y += wf::root_y0<float>(jr, xr, wb, vb, gb);
-    }
-    T.r_y0[lane] += y;
-  }
-  // ---- the rank-6 part of G: u = L^-1 (J_r - J_j Y_m), G_ik = u_i . u_k
-  const int gtri = lane * (lane + 1) / 2;  // G is symmetric: row `lane` keeps its columns r2 <= lane
-  {
-    float u[6], jr[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    if (crow) wf::row_root<float>(T.c_pos[ck], er, jr);
-    wf::rank6_factor<float>(Sm, id, jr, jy, u);
-    for (int r2 = 0; r2 < R; r2++) {
-      float gv = 0.f;
-#pragma unroll
-      for (int k = 0; k < 6; k++) gv += u[k] * rl_f(u[k], r2);
-      if (row && r2 <= lane) T.G[gtri + r2] = gv;
-    }
-  }
-  // ---- the block part J_j M_jj^-1 J_j': four columns per block solve, rows of different blocks sharing a column
-#pragma unroll 1
-  for (int cb = 0; cb < ncol; cb += 4) {
-    for (int f = lane; f < ND; f += 64) T.X4[f] = make_float4(0.f, 0.f, 0.f, 0.f);
-    DM_SYNC();
-    {
-      const int col = mycol - cb;
-      if (row && col >= 0 && col < 4) {
-        if (crow) { for (int p = 0; p < cnch; p++) { const int f = M.l_chain[p][clink]; (&T.X4[f].x)[col] = fj_row(T, er, ck, f); } }
-        else (&T.X4[rdof].x)[col] = sg;
-      }
-    }
-    DM_SYNC();
-    solve4(c, T.Lm, T.dinv_m);
-    if (row) {
-      float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
-      if (crow) {
-        for (int p = 0; p < cnch; p++) {
-          const int f = M.l_chain[p][clink];
-          const float jv = fj_row(T, er, ck, f);
-          const float4 y = T.X4[f];
-          acc.x += jv * y.x; acc.y += jv * y.y; acc.z += jv * y.z; acc.w += jv * y.w;
-        }
-      } else { const float4 y = T.X4[rdof]; acc = make_float4(sg * y.x, sg * y.y, sg * y.z, sg * y.w); }
-#pragma unroll
-      for (int q2 = 0; q2 < 4; q2++) {
-        const float av = q2 == 0 ? acc.x : (q2 == 1 ? acc.y : (q2 == 2 ? acc.z : acc.w));
-        const int r2 = cb + q2 < KCOL ? (int)T.rowof[myb][cb + q2] : 255;
-        if (r2 <= lane) T.G[gtri + r2] += av;  // (255 = no such row)
-      }
-    }
-    DM_SYNC();
-  }
-  // ---- solve: contact blocks first, limit rows after them, the model's noslip sweeps
-  int nact = 0;
-  for (int k = 0; k < nc; k++) nact += T.c_excl[k] ? 0 : 1;
-  const int nslip = (nact > 0 && !(c.flags & BF_NO_NOSLIP)) ? M.noslip_iterations : 0;
-  ModelPtr mp_ = (ModelPtr)c.M;
-  int iters;
-  if (R <= 12) iters = row_newton<12, ConeRows>(c.T, mp_, lane, R, nrc, scale2, nslip, 0);
-  else if (R <= 18) iters = row_newton<18, ConeRows>(c.T, mp_, lane, R, nrc, scale2, nslip, 0);
-  else if (R <= 24) iters = row_newton<24, ConeRows>(c.T, mp_, lane, R, nrc, scale2, nslip, 0);
-  else if (R <= 32) iters = row_newton<32, ConeRows>(c.T, mp_, lane, R, nrc, scale2, nslip, 0);
-  else iters = row_newton<RMAX, ConeRows>(c.T, mp_, lane, R, nrc, scale2, nslip, 0);
-  // ---- qfrc_constraint: J_j' f on the hinges, J_r' f (and the adhesion pull) on the root
-  float fr[9];
-  floor_frame(c, fr);
-  {
-    float fsum = 0.f, fa[6];
-#pragma unroll
-    for (int a = 0; a < 6; a++) fa[a] = T.rootf[a];
-    for (int k = 0; k < nc; k++) {
-      fsum += T.r_f[3 * k];
-#pragma unroll
-      for (int r = 0; r < 3; r++) {
-        float j6[6];
-        wf::row_root<float>(T.c_pos[k], &fr[3 * r], j6);
-        const float f = T.r_f[3 * k + r];
-#pragma unroll
-        for (int a = 0; a < 6; a++) fa[a] += j6[a] * f;
-      }
-    }
-    DM_SYNC();
-    if (lane == 0) {
-#pragma unroll
-      for (int a = 0; a < 6; a++) T.rootf[a] = fa[a];
-      T.rootf[6] = fsum;
-    }
-  }
-#pragma unroll
-  for (int s = 0; s < 3; s++) {
-    if (slot_on(c, s)) qs[s] += floor_gather<false>(T, M, fr, nc, opq(c.sdof[s]), T.r_f);
-    if (lrow[s] >= 0) qs[s] += lsgn[s] * T.r_f[lrow[s]];
-  }
-  DM_SYNC();
-  return iters;
-}
-
-// ------------------------------------------------------------------------------------------------ stage 2
-// EP (the episode kernel): also mj's qacc = M^-1 (qfrc_smooth + qfrc_constraint) through M's own factor - the Euler solve below is
-// implicit in the joint damping, so its solution is not qacc - for the accelerometer of this substep (`acc`, from the state before the
-// integration) and for sum qacc^2 (`qn2`); `integrate` false stops there (mj_forward of a reset: nothing is advanced).
-template <bool LIMITS, bool EP = false, class C>
-__device__ __forceinline__ void stage2(C &c, float act_reg, float ctrl_reg, float &act_out, int &nlim_out, int &iters_out,
-                                       const ImitArgs *ep = nullptr, bool integrate = true, float *acc = nullptr, float *qn2 = nullptr) {
-  auto &T = *c.T;
-  constexpr bool FLOOR = is_floor_tile<std::remove_reference_t<decltype(T)>>::value;  // the floor kernel: everything it adds is under this switch
-  const BallModel FFE_GLOBAL &M = model(c);
-  const int lane = c.lane;
-  const float h = M.h;
-#pragma unroll
-  for (int s = 0; s < 3; s++) if (slot_on(c, s)) { T.Q[opq(c.sdof[s])] = c.q[s]; T.V[opq(c.sdof[s])] = c.v[s]; }
-  DM_SYNC();
-  // ---- mj: mj_fwdActuation: first-order activation filter, affine position servo on the activation (as ball_env.hip; an adhesion
-  //      actuator has nothing to pull on without contacts)
-  float act_dot = 0.f;
-  if (lane < NU) {
-    float force = 0.f;
-    if (!(c.flags & BF_NO_ACTUATION)) {
-      float ctrl = ctrl_reg;
-      if (M.a_climited[lane]) ctrl = fminf(fmaxf(ctrl, M.a_clo[lane]), M.a_chi[lane]);
-      act_dot = (ctrl - act_reg) * frcp(M.a_tau[lane]);
-      float length = 0.f, vel = 0.f;
-      const int nw = M.a_nwrap[lane];
-      for (int w = 0; w < nw; w++) { const int f = M.a_wdof[w][lane]; const float cf = M.a_wcoef[w][lane]; length += cf * T.Q[f]; vel += cf * T.V[f]; }
-      force = M.a_gain[lane] * act_reg + M.a_b0[lane] + M.a_b1[lane] * length + M.a_b2[lane] * vel;
-      if (M.a_flimited[lane]) force = fminf(fmaxf(force, M.a_flo[lane]), M.a_fhi[lane]);
-      if constexpr (FLOOR) { if (M.a_trn[lane] == 2 && (c.flags & BF_NO_ADHESION)) force = 0.f; }
-    }
-    T.frc[lane] = force;
-  }
-  act_out = act_reg + h * act_dot;
-  DM_SYNC();
-  // ---- smooth forces of the hinges (mj: mj_fwdAcceleration's right-hand side)
-  float qs[3];
-#pragma unroll
-  for (int s = 0; s < 3; s++) {
-    qs[s] = 0.f;
-    if (slot_on(c, s)) {
-      float f = c.fnb[s];
-      const int a0 = M.s_act[0][s][lane], a1 = M.s_act[1][s][lane];
-      if (a0 >= 0) f += M.s_actcoef[0][s][lane] * T.frc[a0];
-      if (a1 >= 0) f += M.s_actcoef[1][s][lane] * T.frc[a1];
-      qs[s] = f;
-    }
-  }
-  // ---- z = A^-1 f_j and Y = A^-1 M_jr, A = M_jj + h B: seven right-hand sides through two four-wide block solves.  M_jr's column of
-  //      hinge f is T.F[f] (the 6-vector crb * cdof of the assembly: the root's motion axes are the unit vectors of this frame).
-  S6 mrj[3], y[3];
-  float z[3];
-#pragma unroll
-  for (int s = 0; s < 3; s++) mrj[s] = slot_on(c, s) ? ld6(T.F[opq(c.sdof[s])]) : zero6();
-  DM_SYNC();  // (Q / V have been read: X4 lies over them)
-  if constexpr (LIMITS) {
-    // ---- joint-limit rows (mj: mj_instantiateLimit, margin 0): sign, D, aref per slot, exactly as ball_env.hip's stage 2; one row
-    //      per instantiated limit in (slot, lane) order; beyond RMAX the rows are dropped for this substep and the env is flagged
-    float lsgn[3];
-    int lrow[3] = {-1, -1, -1};
-    int R = 0;
-    if constexpr (FLOOR) {  // the contact rows come first: three per contact of the collision pass
-      R = 3 * c.fl.nc;
-      if (lane < 8) T.rootf[lane] = 0.f;
-    }
-#pragma unroll
-    for (int s = 0; s < 3; s++) {
-      float lD = 0.f, laref = 0.f;
-      lsgn[s] = 0.f;
-      if (slot_on(c, s) && M.s_limited[s][lane]) {
-        const float dlo = c.q[s] - M.s_lo[s][lane], dhi = M.s_hi[s][lane] - c.q[s];
-        float dist = 0.f;
-        if (dlo < 0.f) { lsgn[s] = 1.f; dist = dlo; }
-        else if (dhi < 0.f) { lsgn[s] = -1.f; dist = dhi; }
-        if (lsgn[s] != 0.f) {
-          float si_[5];
-#pragma unroll
-          for (int q2 = 0; q2 < 5; q2++) si_[q2] = M.j_solimp[q2];
-          const float imp = impedance(si_, fabsf(dist));
-          lD = frcp(fmaxf(1e-15f, (1.f - imp) * M.s_invw[s][lane] * frcp(imp)));
-          laref = -M.s_B[s][lane] * (lsgn[s] * c.v[s]) - M.s_K[s][lane] * imp * dist;
-        }
-      }
-      const bool on = lsgn[s] != 0.f;
-      const unsigned long long bal = __ballot(on);
-      const int idx = R + __popcll(bal & ((1ull << lane) - 1ull));
-      if (on && idx < RMAX) {
-        lrow[s] = idx;
-        T.r_sgn[idx] = lsgn[s]; T.r_D[idx] = lD; T.r_y0[idx] = -laref;
-        T.r_dof[idx] = (unsigned char)c.sdof[s]; T.r_blk[idx] = (unsigned char)M.d_blk[c.sdof[s]];
-      }
-      R += __popcll(bal);
-    }
-    if (R > RMAX) { R = RMAX; c.overflow |= 2; }
-    nlim_out = R;
-    if constexpr (FLOOR) nlim_out = R - 3 * c.fl.nc;
-    iters_out = 0;
-    if (R > 0) {  // wave-uniform: a substep without a row pays the ballots only
-      DM_SYNC();
-      if constexpr (FLOOR) iters_out = floor_forces(c, R, lrow, lsgn, qs);  // (limit rows alone too: the cone solver with no cone block)
-      else iters_out = limit_forces(c, R, lrow, lsgn, mrj, qs);
-      // (read again rather than kept in registers across the solver's call: 18 fewer live values there)
-#pragma unroll
-      for (int s = 0; s < 3; s++) mrj[s] = slot_on(c, s) ? ld6(T.F[opq(c.sdof[s])]) : zero6();
-    }
-  }
-  if constexpr (EP) {
-    S6 ym[3];
-    float zm[3];
-#pragma unroll
-    for (int s = 0; s < 3; s++) T.qsave[s][lane] = qs[s];
-#pragma unroll
-    for (int s = 0; s < 3; s++) if (slot_on(c, s)) T.X4[opq(c.sdof[s])] = make_float4(qs[s], mrj[s].a0, mrj[s].a1, mrj[s].a2);
-    DM_SYNC();
-    solve4(c, T.Lm, T.dinv_m);
-#pragma unroll
-    for (int s = 0; s < 3; s++) {
-      const float4 x = slot_on(c, s) ? T.X4[opq(c.sdof[s])] : make_float4(0.f, 0.f, 0.f, 0.f);
-      zm[s] = x.x; ym[s].a0 = x.y; ym[s].a1 = x.z; ym[s].a2 = x.w;
-    }
-    DM_SYNC();
-#pragma unroll
-    for (int s = 0; s < 3; s++) if (slot_on(c, s)) T.X4[opq(c.sdof[s])] = make_float4(mrj[s].l0, mrj[s].l1, mrj[s].l2, 0.f);
-    DM_SYNC();
-    solve4(c, T.Lm, T.dinv_m);
-#pragma unroll
-    for (int s = 0; s < 3; s++) {
-      const float4 x = slot_on(c, s) ? T.X4[opq(c.sdof[s])] : make_float4(0.f, 0.f, 0.f, 0.f);
-      ym[s].l0 = x.x; ym[s].l1 = x.y; ym[s].l2 = x.z;
-    }
-    DM_SYNC();
-    float Sm[6][6], br[6], id[6], xr[6];
-    schur(c, mrj, ym, zm, Sm, br);
-    chol6(Sm, id);
-    chol6_forward(Sm, id, br, xr);
-    chol6_backward(Sm, id, xr);
-    float sq = 0.f;
-#pragma unroll
-    for (int s = 0; s < 3; s++) {
-      if (slot_on(c, s)) {
-        float a = zm[s];
-#pragma unroll
-        for (int k = 0; k < 6; k++) a -= comp(ym[s], k) * xr[k];
-        sq += a * a;
-      }
-    }
-    const M3 R = q2m(c.rq);
-    const bool grav = !(c.flags & BF_NO_GRAVITY);
-    V3 aw = mv(R, V3{xr[3], xr[4], xr[5]} + cross(ang(c.V0), lin(c.V0)));
-    if (grav) aw.z += M.gz;
-    *qn2 = wave_sum(sq) + dot(aw, aw) + xr[0] * xr[0] + xr[1] * xr[1] + xr[2] * xr[2];
-    const float qr[4] = {c.rq.w, c.rq.x, c.rq.y, c.rq.z}, wb[3] = {c.wb.x, c.wb.y, c.wb.z}, al[3] = {aw.x, aw.y, aw.z}, wd[3] = {xr[0], xr[1], xr[2]};
-    wi::imu_acceleration<float>(qr, wb, al, wd, grav ? M.gz : 0.f, ep->site_pos, ep->site_quat, acc);
-    if (!integrate) { act_out = act_reg; return; }
-#pragma unroll
-    for (int s = 0; s < 3; s++) { qs[s] = T.qsave[s][lane]; mrj[s] = slot_on(c, s) ? ld6(T.F[opq(c.sdof[s])]) : zero6(); }
-  }
-#pragma unroll
-  for (int s = 0; s < 3; s++) if (slot_on(c, s)) T.X4[opq(c.sdof[s])] = make_float4(qs[s], mrj[s].a0, mrj[s].a1, mrj[s].a2);
-  DM_SYNC();
-  solve4(c, T.Lh, T.dinv_h);
-#pragma unroll
-  for (int s = 0; s < 3; s++) {
-    const float4 x = slot_on(c, s) ? T.X4[opq(c.sdof[s])] : make_float4(0.f, 0.f, 0.f, 0.f);
-    z[s] = x.x; y[s].a0 = x.y; y[s].a1 = x.z; y[s].a2 = x.w;
-  }
-  DM_SYNC();
-#pragma unroll
-  for (int s = 0; s < 3; s++) if (slot_on(c, s)) T.X4[opq(c.sdof[s])] = make_float4(mrj[s].l0, mrj[s].l1, mrj[s].l2, 0.f);
-  DM_SYNC();
-  solve4(c, T.Lh, T.dinv_h);
-#pragma unroll
-  for (int s = 0; s < 3; s++) {
-    const float4 x = slot_on(c, s) ? T.X4[opq(c.sdof[s])] : make_float4(0.f, 0.f, 0.f, 0.f);
-    y[s].l0 = x.x; y[s].l1 = x.y; y[s].l2 = x.z;
-  }
-  DM_SYNC();
-  if constexpr (!LIMITS) {
-#pragma unroll
-    for (int s = 0; s < 3; s++) if (slot_on(c, s)) st6(T.Y[opq(c.sdof[s])], y[s]);  // (the limits kernel reads its rows' Y_m from the solve instead)
-  }
-  // ---- Schur complement S = M_rr - M_rj Y and right-hand side f_r - M_rj z; 6 x 6 Cholesky S = L L', x_r = S^-1 b_r
-  float Sm[6][6], br[6], id[6], xr[6];
-  schur(c, mrj, y, z, Sm, br);
-  if constexpr (FLOOR) {
-#pragma unroll
-    for (int k = 0; k < 6; k++) br[k] += T.rootf[k];
-  }
-  chol6(Sm, id);
-  chol6_forward(Sm, id, br, xr);
-  chol6_backward(Sm, id, xr);
-  // ---- back substitution of the hinges, integration (mj: mj_Euler, implicit in the joint damping)
-#pragma unroll
-  for (int s = 0; s < 3; s++) {
-    if (slot_on(c, s)) {
-      float a = z[s];
-#pragma unroll
-      for (int k = 0; k < 6; k++) a -= comp(y[s], k) * xr[k];
-      c.v[s] += h * a;
-      c.q[s] += h * c.v[s];
-    }
-  }
-  {
-    // free joint: qacc = (R (vdot_b + w_b x v_b) + g, wdot_b), gravity added here (see the head of this file); mj_integratePos: position with the new velocity, quaternion by mju_quatIntegrate
-    const M3 R = q2m(c.rq);
-    const V3 wd = {xr[0], xr[1], xr[2]}, vd = {xr[3], xr[4], xr[5]};
-    V3 aw = mv(R, vd + cross(ang(c.V0), lin(c.V0)));
-    if (!(c.flags & BF_NO_GRAVITY)) aw.z += M.gz;
-    c.vw = c.vw + h * aw;
-    c.wb = c.wb + h * wd;
-    c.pos[0] += (double)h * (double)c.vw.x; c.pos[1] += (double)h * (double)c.vw.y; c.pos[2] += (double)h * (double)c.vw.z;
-    const float wn = fsqrt(dot(c.wb, c.wb));
-    Q4 q = qnormalize(c.rq);
-    if (wn >= 1e-15f) q = qnormalize(qmul(q, axis_angle(frcp(wn) * c.wb, wn * h)));
-    c.rq = q;
-  }
-}
-
-// ------------------------------------------------------------------------------------------------ kernels
-// the state in the ffe_get_state layout, from the registers of the wave that holds it
-template <class C>
-__device__ __forceinline__ void export_state(const C &c, double *__restrict__ qp, double *__restrict__ qv) {
-#pragma unroll
-  for (int s = 0; s < 3; s++) if (slot_on(c, s)) { qp[7 + c.sdof[s]] = (double)c.q[s]; qv[6 + c.sdof[s]] = (double)c.v[s]; }
-  if (c.lane == 0) {
-    qp[0] = c.pos[0]; qp[1] = c.pos[1]; qp[2] = c.pos[2];
-    qp[3] = (double)c.rq.w; qp[4] = (double)c.rq.x; qp[5] = (double)c.rq.y; qp[6] = (double)c.rq.z;
-    qv[0] = (double)c.vw.x; qv[1] = (double)c.vw.y; qv[2] = (double)c.vw.z;
-    qv[3] = (double)c.wb.x; qv[4] = (double)c.wb.y; qv[5] = (double)c.wb.z;
-  }
-}
-
-// `ep` (the episode kernel alone, `Ep` = ImitCall): one control step of the env, or its reset, in place of `nphys` bare substeps - see
-// imitation_step_kernel below.  With `Ep` = NoEpisode none of it is compiled.
-template <bool LIMITS, class Tile, class Ep = NoEpisode>
-__device__ __forceinline__ void walk_substeps(Tile &T, const WalkModel *__restrict__ Wp, int flags, WState *__restrict__ states,
-                                              const float *__restrict__ ctrl, int nphys, const Ep &ep = Ep()) {
-  constexpr bool EP = !std::is_same<Ep, NoEpisode>::value && !std::is_same<Ep, FloorCall>::value;
-  const int env = blockIdx.x, lane = threadIdx.x;
-  const BallModel &M = Wp->b;
-  WState &S = states[env];
-  CtxT<Tile> c;
-  c.M = &Wp->b; c.X = (const WalkExtra FFE_GLOBAL *)&Wp->x; c.T = &T; c.lane = lane; c.flags = flags; c.overflow = 0;
-  c.lpack = M.l_pack[lane]; c.xh = M.x_on[lane];
-#pragma unroll
-  for (int s = 0; s < 3; s++) c.sdof[s] = M.s_dof[s][lane];
-#pragma unroll
-  for (int s = 0; s < 3; s++) { c.q[s] = slot_on(c, s) ? S.q[c.sdof[s]] : 0.f; c.v[s] = slot_on(c, s) ? S.v[c.sdof[s]] : 0.f; }
-  c.rq = {S.quat[0], S.quat[1], S.quat[2], S.quat[3]};
-  c.vw = {S.vlin[0], S.vlin[1], S.vlin[2]}; c.wb = {S.wb[0], S.wb[1], S.wb[2]};
-  c.pos[0] = S.pos[0]; c.pos[1] = S.pos[1]; c.pos[2] = S.pos[2];
-  float act_reg = lane < NU ? S.act[lane] : 0.f;
-  float ctrl_reg = 0.f;
-  int row = 0;  // episode kernel: 0 step, 1 reset
-  if constexpr (EP) {
-    row = ep.a->flag[env];
-    if (row == 2) {  // not this call's env: the task layer still reads its state
-      export_state(c, ep.a->qpos + (size_t)env * 109, ep.a->qvel + (size_t)env * 108);
-      return;
-    }
-    if (row == 1) {
-      // mj: walk_imitation.py:112-121 initialize_episode: the pose of row 0 of the clip (qpos0, root, tracked joints, retracted wings),
-      // zero velocity, activation and ctrl; rounded to float32 as ffe_set_state rounds it
-      const double *qp = ep.a->pose + (size_t)env * 109;
-#pragma unroll
-      for (int s = 0; s < 3; s++) { c.q[s] = slot_on(c, s) ? (float)qp[7 + c.sdof[s]] : 0.f; c.v[s] = 0.f; }
-      c.rq = qnormalize(Q4{(float)qp[3], (float)qp[4], (float)qp[5], (float)qp[6]});
-      c.vw = {0.f, 0.f, 0.f}; c.wb = {0.f, 0.f, 0.f};
-      c.pos[0] = qp[0]; c.pos[1] = qp[1]; c.pos[2] = qp[2];
-      act_reg = 0.f;
-      c.flags |= BF_NO_ACTUATION;  // dm_control's after_reset: mj_forward with actuation disabled
-    } else if (lane < NU) {
-      // ref: fruitfly.py:480-492 apply_action (+ the CanonicalSpecWrapper the reference wraps every env in), as ball_env.hip
-      const int ai = M.a_action[lane];
-      float av = ai >= 0 ? ep.action[(size_t)env * NACT + ai] : 0.f;
-      if (!(av == av)) av = 0.f;
-      if (ep.a->canonical && ai >= 0) {
-        if (ep.a->clip) av = fminf(fmaxf(av, -1.f), 1.f);
-        av = M.act_lo[ai] + 0.5f * (av + 1.f) * (M.act_hi[ai] - M.act_lo[ai]);
-      }
-      ctrl_reg = av;
-    }
-    nphys = row == 1 ? 1 : M.nsub;
-    if (lane < 36) T.sens[lane] = 0.f;  // (the sums are cleared at substep 0)
-    DM_SYNC();
-  } else {
-    ctrl_reg = lane < NU ? ctrl[(size_t)env * NU + lane] : 0.f;
-  }
-  int nlim = 0, iters = 0;
-  float qn2 = 0.f;
-  constexpr bool FLOOR = is_floor_tile<Tile>::value;
-#pragma unroll 1
-  for (int s = 0; s < nphys; s++) {
-    stage1(c);
-    if constexpr (FLOOR) {
-      // ---- collision pass: the plane's normal in the root frame, the root origin's height over the plane in float64
-      const WalkExtra FFE_GLOBAL &X = *c.X;
-      const V3 nw = {X.f_frame[0], X.f_frame[1], X.f_frame[2]}, nb = mtv(q2m(c.rq), nw);
-      const double height = (double)nw.x * c.pos[0] + (double)nw.y * c.pos[1] + (double)nw.z * c.pos[2] - (double)X.f_off;
-      const int fc = __builtin_amdgcn_readfirstlane(floor_collide(c.T, c.X, lane, c.xp.x, c.xp.y, c.xp.z, c.xq.w, c.xq.x, c.xq.y, c.xq.z, c.cvel.a0, c.cvel.a1,
-                                                                  c.cvel.a2, c.cvel.l0, c.cvel.l1, c.cvel.l2, nb.x, nb.y, nb.z, height));
-      c.fl.nc = fc & 0xff;
-      if (fc >> 8) c.overflow |= 1;
-      float md = 0.f;
-      for (int k = 0; k < c.fl.nc; k++) md = k == 0 ? T.c_dist[0] : fminf(md, T.c_dist[k]);
-      c.fl.mind = md;
-    }
-    float act_new;
-    if constexpr (EP) {
-      // dm_control runs mj_step2 ; mj_step1 and samples: the accelerometer is the acceleration stage's (the state before the
-      // integration, this substep's qacc), gyro and velocimeter belong to the state after it.  Force and touch stay zero: no contacts.
-      float acc[3], gy[3], ve[3];
-      stage2<LIMITS, true>(c, act_reg, ctrl_reg, act_new, nlim, iters, ep.a, row == 0, acc, &qn2);
-      const float qr[4] = {c.rq.w, c.rq.x, c.rq.y, c.rq.z}, vl[3] = {c.vw.x, c.vw.y, c.vw.z}, wb[3] = {c.wb.x, c.wb.y, c.wb.z};
-      wi::imu_velocity<float>(qr, vl, wb, ep.a->site_pos, ep.a->site_quat, gy, ve);
-      if (lane < 3) {
-        T.sens[lane] += lane == 0 ? acc[0] : (lane == 1 ? acc[1] : acc[2]);
-        T.sens[3 + lane] += lane == 0 ? gy[0] : (lane == 1 ? gy[1] : gy[2]);
-        T.sens[6 + lane] += lane == 0 ? ve[0] : (lane == 1 ? ve[1] : ve[2]);
-      }
-    } else {
-      stage2<LIMITS>(c, act_reg, ctrl_reg, act_new, nlim, iters);
-    }
-    act_reg = act_new;
-  }
-#pragma unroll
-  for (int s = 0; s < 3; s++) if (slot_on(c, s)) { S.q[c.sdof[s]] = c.q[s]; S.v[c.sdof[s]] = c.v[s]; }
-  if (lane < NU) S.act[lane] = act_reg;
-  if (lane == 0) {
-    S.quat[0] = c.rq.w; S.quat[1] = c.rq.x; S.quat[2] = c.rq.y; S.quat[3] = c.rq.z;
-    S.vlin[0] = c.vw.x; S.vlin[1] = c.vw.y; S.vlin[2] = c.vw.z;
-    S.wb[0] = c.wb.x; S.wb[1] = c.wb.y; S.wb[2] = c.wb.z;
-    S.pos[0] = c.pos[0]; S.pos[1] = c.pos[1]; S.pos[2] = c.pos[2];
-    if constexpr (LIMITS) { S.nlim = nlim; S.iters = iters; S.step_bits = c.overflow; }
-    if constexpr (FLOOR) ep.rec[env] = FloorRec{c.fl.nc, T.rootf[6], c.fl.mind, 0};
-  }
-  if constexpr (EP) {
-    // ---- the 92 physics columns of the observation row (the task layer writes the kinematic ones), the state for the task layer, and
-    //      what check_termination reads of the last substep
-    DM_SYNC();
-    float *ob = ep.obs + (size_t)env * (size_t)ep.a->obs_dim;
-    const float inv = (row == 1 && ep.a->pad_first_obs) ? 1.f : 1.f / (float)M.nsub;
-    if (lane < 3) {
-      ob[lane] = T.sens[lane] * inv;
-      ob[ep.a->off_gyro + lane] = T.sens[3 + lane] * inv;
-      ob[ep.a->off_velocimeter + lane] = T.sens[6 + lane] * inv;
-    }
-    if (lane < NU) ob[ep.a->off_act + lane] = act_reg;
-    if (lane < 18) ob[ep.a->off_force + lane] = T.sens[9 + lane] * inv;
-    if (lane < 6) ob[ep.a->off_touch + lane] = T.sens[27 + lane] * inv;
-    export_state(c, ep.a->qpos + (size_t)env * 109, ep.a->qvel + (size_t)env * 108);
-    if (lane == 0) {
-      float gy[3], ve[3];
-      const float qr[4] = {c.rq.w, c.rq.x, c.rq.y, c.rq.z}, vl[3] = {c.vw.x, c.vw.y, c.vw.z}, wb[3] = {c.wb.x, c.wb.y, c.wb.z};
-      wi::imu_velocity<float>(qr, vl, wb, ep.a->site_pos, ep.a->site_quat, gy, ve);
-      float *t = ep.a->term + (size_t)env * 4;
-      t[0] = fsqrt(ve[0] * ve[0] + ve[1] * ve[1] + ve[2] * ve[2]);
-      t[1] = fsqrt(gy[0] * gy[0] + gy[1] * gy[1] + gy[2] * gy[2]);
-      t[2] = qn2; t[3] = 0.f;
-    }
-  }
-}
 
 // smooth dynamics alone (FFE_NO_CONTACT | FFE_NO_LIMIT)
 __global__ __launch_bounds__(64, 2) void walk_step_kernel(const WalkModel *__restrict__ Wp, int flags, WState *__restrict__ states,
@@ -1324,16 +201,16 @@ __global__ void episode_init_kernel(EpState *eps, int batch) {
 }
 // episode handle: task state {clip, step counter, episode (low 32 bits), needs_reset, limit rows of the last substep, 0, solver
 // iterations of the last substep, overflow bits of the last launch}, reals zero; validity {step_bits, episode_flagged_steps,
-// episode_bits, episode_steps}
-__global__ void episode_report_kernel(const EpState *eps, const WState *states, int *ints, double *reals, int *info, int batch) {
+// episode_bits, episode_steps}.  On the floor (`rec` not null) int 5 and reals 0 / 1 are the floor handle's.
+__global__ void episode_report_kernel(const EpState *eps, const WState *states, const FloorRec *rec, int *ints, double *reals, int *info, int batch) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= batch) return;
   const WState &S = states[i];
   const EpState &e = eps[i];
   if (ints) {
     int *o = ints + (size_t)i * 8;
-    o[0] = e.clip; o[1] = e.step; o[2] = (int)(unsigned)e.episode; o[3] = e.needs_reset; o[4] = S.nlim; o[5] = 0; o[6] = S.iters; o[7] = S.step_bits;
-    for (int k = 0; k < 8; k++) reals[(size_t)i * 8 + k] = 0.0;
+    o[0] = e.clip; o[1] = e.step; o[2] = (int)(unsigned)e.episode; o[3] = e.needs_reset; o[4] = S.nlim; o[5] = rec ? rec[i].ncon : 0; o[6] = S.iters; o[7] = S.step_bits;
+    for (int k = 0; k < 8; k++) reals[(size_t)i * 8 + k] = !rec ? 0.0 : (k == 0 ? (double)rec[i].fsum : (k == 1 ? (double)rec[i].mind : 0.0));
   }
   if (info) *reinterpret_cast<int4 *>(info + (size_t)i * 4) = make_int4(S.step_bits, e.ep_flagged, e.ep_bits, e.step);
 }
@@ -1407,12 +284,13 @@ __global__ void walk_act_kernel(WState *states, double *act, int batch, int set)
 
 // ================================================================================================ host side
 // Bare physics (reset, step, forced episodes and the timers are refused) or, created with FFE_WALK_EPISODES, the walk_imitation
-// environment with the floor off.
+// environment with the floor off or, with FFE_WALK_FLOOR too, on the floor (step 4c: the third of the five
+// launches is then `imitation_floor_step` of walk_floor_env.hip).
 struct WalkEnv final : ffe::EnvBackend {
   int flags = 0;
   bool limits = false;    // FFE_WALK_JOINT_LIMITS: walk_limits_kernel steps this handle
   bool episodes = false;  // FFE_WALK_EPISODES: ffe_step / ffe_reset / ... work, imitation_step_kernel steps them
-  bool floor = false;     // FFE_WALK_FLOOR: floor_step steps this handle
+  bool floor = false;     // FFE_WALK_FLOOR: floor_step steps this handle (with `episodes`: imitation_floor_step)
   FloorRec *rec = nullptr;  // floor handle only: contacts, normal-force sum and smallest distance of the last substep
   WalkHost host;
   ffe::DeviceBuffers mem{"ffe_create_walk_physics"};  // everything below lives here
@@ -1479,7 +357,8 @@ struct WalkEnv final : ffe::EnvBackend {
     task_ok(ffe_walktask_reference_pose(task, clip, zero, batch, const_cast<double *>(args.pose), nullptr, stream), "walk_imitation");
     const ImitArgs &a = args;
     tm.start(s);
-    hipLaunchKernelGGL(imitation_step_kernel, dim3(batch), dim3(64), 0, s, model_dev, flags, states, args_dev, act, obs, batch);
+    if (floor) launch_imitation_floor_step(model_dev, flags, states, args_dev, act, obs, batch, s);
+    else hipLaunchKernelGGL(imitation_step_kernel, dim3(batch), dim3(64), 0, s, model_dev, flags, states, args_dev, act, obs, batch);
     HIP_OK(hipGetLastError());
     tm.stop(s);
     task_ok(ffe_walktask_evaluate(task, a.qpos, a.qvel, clip, step, batch, nullptr, reward_tmp, bits, obs, a.obs_dim, stream), "walk_imitation");
@@ -1517,7 +396,7 @@ struct WalkEnv final : ffe::EnvBackend {
   }
   void get_task_state(int32_t *ints, double *reals, void *stream) override {  // int32[B][8] and float64[B][8]: zeros on a plain handle
     if (episodes) {
-      hipLaunchKernelGGL(episode_report_kernel, dim3((batch + 63) / 64), dim3(64), 0, (hipStream_t)stream, eps, states, ints, reals, (int *)nullptr, batch);
+      hipLaunchKernelGGL(episode_report_kernel, dim3((batch + 63) / 64), dim3(64), 0, (hipStream_t)stream, eps, states, rec, ints, reals, (int *)nullptr, batch);
       HIP_OK(hipGetLastError());
       return;
     }
@@ -1536,7 +415,7 @@ struct WalkEnv final : ffe::EnvBackend {
   }
   void get_validity(int32_t *info, void *stream) override {  // int32[B][4]: zeros on a plain handle
     if (episodes) {
-      hipLaunchKernelGGL(episode_report_kernel, dim3((batch + 63) / 64), dim3(64), 0, (hipStream_t)stream, eps, states, (int *)nullptr, (double *)nullptr, info, batch);
+      hipLaunchKernelGGL(episode_report_kernel, dim3((batch + 63) / 64), dim3(64), 0, (hipStream_t)stream, eps, states, rec, (int *)nullptr, (double *)nullptr, info, batch);
       HIP_OK(hipGetLastError());
       return;
     }
@@ -1590,6 +469,7 @@ static void make_episodes(WalkEnv &e, const Blob &b, const void *blob, size_t bl
   e.reward_tmp = e.mem.zeroed<float>((size_t)B);
   e.clip_steps = e.mem.zeroed<int>((size_t)e.ntraj);
   a.flag = e.flag;
+  a.rec = e.rec;  // (null without FFE_WALK_FLOOR)
   e.args_dev = e.mem.zeroed<ImitArgs>(1);
   HIP_OK(hipMemcpy(e.args_dev, &a, sizeof(ImitArgs), hipMemcpyHostToDevice));
   HIP_OK(hipMemcpy(e.clip_steps, ep.data(), sizeof(int32_t) * (size_t)e.ntraj, hipMemcpyHostToDevice));
@@ -1603,7 +483,16 @@ std::unique_ptr<ffe::EnvBackend> walk_create(const void *blob, size_t blob_size,
   if (!blob || batch <= 0) throw std::runtime_error("ffe_create_walk_physics: bad arguments");
   const bool limits = (physics_flags & BF_WALK_JOINT_LIMITS) != 0, no_limit = (physics_flags & BF_NO_LIMIT) != 0;
   const bool episodes = (physics_flags & BF_WALK_EPISODES) != 0, floor = (physics_flags & BF_WALK_FLOOR) != 0;
-  if (floor) {
+  if (floor && episodes) {
+    const int switches = BF_NO_FLUID | BF_NO_DAMPER | BF_NO_SPRING | BF_NO_GRAVITY | BF_NO_ACTUATION | BF_NO_NOSLIP | BF_NO_ADHESION;
+    if ((physics_flags & ~switches) != (BF_NO_CONTACT | BF_WALK_JOINT_LIMITS | BF_WALK_EPISODES | BF_WALK_FLOOR))
+      throw std::runtime_error("ffe_create_walk_physics: FFE_WALK_EPISODES | FFE_WALK_FLOOR (the walk_imitation environment on the floor plane) needs "
+                               "FFE_NO_CONTACT | FFE_WALK_JOINT_LIMITS and takes the force switches, FFE_NO_NOSLIP and FFE_NO_ADHESION only: it excludes "
+                               "FFE_NO_LIMIT");
+    if (!task.task)
+      throw std::runtime_error("ffe_create_walk_physics: FFE_WALK_EPISODES | FFE_WALK_FLOOR needs the task (a null ffe_walk_task pointer); FFE_WALK_FLOOR "
+                               "without FFE_WALK_EPISODES is the bare-physics floor handle");
+  } else if (floor) {
     const int switches = BF_NO_FLUID | BF_NO_DAMPER | BF_NO_SPRING | BF_NO_GRAVITY | BF_NO_ACTUATION | BF_NO_NOSLIP | BF_NO_ADHESION;
     if ((physics_flags & ~switches) != (BF_NO_CONTACT | BF_WALK_JOINT_LIMITS | BF_WALK_FLOOR))
       throw std::runtime_error("ffe_create_walk_physics: FFE_WALK_FLOOR (the floor plane against the fly's sphere and capsule geoms, bare physics) needs "

@@ -62,14 +62,16 @@ enum {
    * exists because plain FFE_NO_CONTACT is a pinned refusal of that create call while floor contacts are missing; when the step
    * kernel lands it folds into "FFE_NO_LIMIT absent". */
   FFE_WALK_JOINT_LIMITS = 512,
-  /* ffe_create_walk_physics only: the handle is the walk_imitation environment with the floor off (sensors, episode protocol, task
-   * layer; the third step kernel of csrc/walk_env.hip).  Accepted only as FFE_NO_CONTACT | FFE_WALK_JOINT_LIMITS | FFE_WALK_EPISODES
-   * plus force switches.  An opt-in bit and provisional for the same reason: it goes when floor contacts land. */
+  /* ffe_create_walk_physics only: the handle is the walk_imitation environment (sensors, episode protocol, task layer): with the floor
+   * off as FFE_NO_CONTACT | FFE_WALK_JOINT_LIMITS | FFE_WALK_EPISODES plus force switches (the third step kernel of csrc/walk_env.hip),
+   * on the floor plane with FFE_WALK_FLOOR on top of that (csrc/walk_floor_env.hip).  An opt-in bit and provisional for the same
+   * reason: it goes when every contact of the reference's task is built. */
   FFE_WALK_EPISODES = 1024,
   /* ffe_create_walk_physics only: the floor plane against the fly's sphere and capsule geoms, on the bare-physics handle (the fourth
-   * step kernel of csrc/walk_env.hip).  Accepted only as FFE_NO_CONTACT | FFE_WALK_JOINT_LIMITS | FFE_WALK_FLOOR plus force switches,
-   * FFE_NO_NOSLIP and FFE_NO_ADHESION; on such a handle FFE_NO_CONTACT keeps meaning "the fly's own contacts are off" (they are not
-   * built).  An opt-in bit and provisional as the two above. */
+   * step kernel of csrc/walk_env.hip) or, with FFE_WALK_EPISODES and the task, under the environment (csrc/walk_floor_env.hip).  Accepted
+   * only as FFE_NO_CONTACT | FFE_WALK_JOINT_LIMITS | FFE_WALK_FLOOR [| FFE_WALK_EPISODES] plus force switches, FFE_NO_NOSLIP and
+   * FFE_NO_ADHESION; on such a handle FFE_NO_CONTACT keeps meaning "the fly's own contacts are off" (they are not built).  An opt-in
+   * bit and provisional as the two above. */
   FFE_WALK_FLOOR = 2048
 };
 
@@ -151,17 +153,24 @@ int ffe_create_walk_on_ball(const void *model_blob, size_t blob_size, const ffe_
  * filtered actuators) as bare physics: smooth dynamics on the device with constraints off ("dynamics only", as ffe_physics_step offers
  * for the other two tasks), or with the joint limits of its 102 hinges on (FFE_WALK_JOINT_LIMITS); and, with FFE_WALK_EPISODES on top
  * of that, the walk_imitation environment itself with the floor off: sensors, observation row, reward, termination and the episode
- * protocol on the device, a fly that falls freely (or floats with FFE_NO_GRAVITY).  Floor contacts exist on the bare-physics handle
- * alone (FFE_WALK_FLOOR): the floor plane against the fly's 48 sphere / capsule geoms, elliptic cones, noslip and adhesion; the fly's
- * own contacts, the floor against ellipsoids and cylinders, and the floor under FFE_WALK_EPISODES are not built yet. */
+ * protocol on the device, a fly that falls freely (or floats with FFE_NO_GRAVITY).  FFE_WALK_FLOOR adds the floor plane against the
+ * fly's 48 sphere / capsule geoms (elliptic cones, noslip, adhesion) to the bare-physics handle or, together with FFE_WALK_EPISODES,
+ * to the environment, whose force and touch columns are then live; the fly's own contacts and the floor against ellipsoids and
+ * cylinders are not built yet. */
 typedef struct {
   /* FFE_NO_CONTACT and exactly one of FFE_NO_LIMIT (smooth dynamics alone) or FFE_WALK_JOINT_LIMITS (joint limits on: up to 48 limit
    * rows per env and substep), plus any of the force switches FFE_NO_FLUID / _DAMPER / _SPRING / _GRAVITY / _ACTUATION; every other
    * set is refused (the text names FFE_WALK_JOINT_LIMITS when that bit was passed).  FFE_WALK_EPISODES is accepted only together with
    * FFE_NO_CONTACT | FFE_WALK_JOINT_LIMITS (plus force switches); every other set with it is refused with a text naming it.
    * FFE_WALK_FLOOR is accepted only as FFE_NO_CONTACT | FFE_WALK_JOINT_LIMITS | FFE_WALK_FLOOR plus force switches, FFE_NO_NOSLIP and
-   * FFE_NO_ADHESION (meaningful only with this bit); every other set with it - with FFE_WALK_EPISODES, with FFE_NO_LIMIT, without
-   * FFE_WALK_JOINT_LIMITS - is refused with a text naming FFE_WALK_FLOOR */
+   * FFE_NO_ADHESION (meaningful only with this bit), with or without FFE_WALK_EPISODES; every other set with it - with FFE_NO_LIMIT,
+   * without FFE_WALK_JOINT_LIMITS, with FFE_WALK_EPISODES and a null `task` - is refused with a text naming FFE_WALK_FLOOR (and
+   * FFE_WALK_EPISODES when that bit was passed too).  The accepted sets:
+   *   FFE_NO_CONTACT | FFE_NO_LIMIT                                                   smooth dynamics
+   *   FFE_NO_CONTACT | FFE_WALK_JOINT_LIMITS                                          + joint limits
+   *   FFE_NO_CONTACT | FFE_WALK_JOINT_LIMITS | FFE_WALK_FLOOR                         + the floor plane (bare physics)
+   *   FFE_NO_CONTACT | FFE_WALK_JOINT_LIMITS | FFE_WALK_EPISODES                      walk_imitation, floor off
+   *   FFE_NO_CONTACT | FFE_WALK_JOINT_LIMITS | FFE_WALK_EPISODES | FFE_WALK_FLOOR     walk_imitation on the floor plane */
   int32_t physics_flags;
   /* read only when physics_flags has FFE_WALK_EPISODES (a caller without the bit may pass the one int above alone) */
   const ffe_walk_task *task;  /* clips, tracked joints / sites, reward and termination constants: a float32 task layer of the env's
@@ -197,7 +206,9 @@ typedef struct {
  * ffe_force_next_episode (the clip; the phase array is ignored), ffe_time_steps and ffe_time_kernel work as on a walk_on_ball handle,
  * and ffe_spec reports obs_dim 741 with the offsets of the row: accelerometer 3 | actuator_activation 59 | appendages_pos 21 |
  * force 18 | gyro 3 | joints_pos 85 | joints_vel 85 | ref_displacement 195 | ref_root_quat 260 | touch 6 | velocimeter 3 |
- * world_zaxis 3.  Force and touch are zero (no contacts).  A step is five launches on `stream` (episode bookkeeping, the reset pose,
+ * world_zaxis 3.  Force and touch are zero without FFE_WALK_FLOOR (no contacts); with it force is the interaction force on each
+ * tarsus in its site's frame (inertial when nothing touches, so not zero) and touch the sum of the positive normal forces on each claw,
+ * both sampled in every substep's acceleration stage and averaged like the accelerometer.  A step is five launches on `stream` (episode bookkeeping, the reset pose,
  * the step kernel, the task layer, the closing rule), with no allocation and no synchronisation, so it can be captured into a HIP
  * graph.  Episode rules (walk_imitation.py:89-177): a reset takes the forced clip or draws one, starts at row 0 of it with zero
  * velocity and activation; a step ends the episode when |velocimeter| > 50, |gyro| > 200, the root is further than terminal_com_dist
@@ -205,7 +216,8 @@ typedef struct {
  *   ffe_get_validity    {step_bits, episode_flagged_steps, episode_bits, episode_steps}, the limit-overflow bit (value 2) sticky over
  *                       the episode in episode_bits, as on a walk_on_ball handle
  *   ffe_get_task_state  int 0 = clip, int 1 = step counter, int 2 = episodes started (low 32 bits), int 3 = needs_reset (the next
- *                       ffe_step resets this env), ints 4, 6, 7 as on a limits handle, int 5 and every real zero
+ *                       ffe_step resets this env), ints 4, 6, 7 as on a limits handle, int 5 and every real zero; with FFE_WALK_FLOOR
+ *                       int 5, real 0 and real 1 as on a floor handle, and the floor's bits 1 / 4 in step_bits and episode_bits too
  * A failure of the env's task layer is the env handle's error text. */
 int ffe_create_walk_physics(const void *model_blob, size_t blob_size, const ffe_walk_physics_task *task, int batch, int device,
                             ffe_handle *out);

@@ -1,13 +1,15 @@
-"""Control steps/s of the walk_imitation environment with the floor off (`BatchedWalkEnv`, csrc/walk_env.hip `imitation_step_kernel` and
-the four launches around it) at B = 4 096, and the share of each launch in a step.  Nothing is asserted and there is no target: the path
-has not been measured before, and the launch count is expected to matter more than any one kernel.
+"""Control steps/s of the walk_imitation environment (`BatchedWalkEnv`) at B = 4 096, and the share of each launch in a step: with the
+floor off (csrc/walk_env.hip `imitation_step_kernel` and the four launches around it) or, with `--floor`, on the floor plane
+(csrc/walk_floor_env.hip `imitation_floor_step` in its place; `walk_imitation(floor_contacts="primitives")`).  Nothing is asserted and
+there is no target.
 
-    python tools/bench_walk_env.py [--batch 4096] [--windows 5] [--iters 50] [--log profiles/bench_walk_env.log] [--no-trace]
+    python tools/bench_walk_env.py [--floor] [--batch 4096] [--windows 5] [--iters 50] [--log profiles/bench_walk_env.log] [--no-trace]
 
 Timing: `ffe_time_steps` (device events around `iters` step launches on the env's stream) per window; the cases - zero actions and
 uniform +-0.5 actions - alternate window by window so that clock and neighbours act on both alike; window 0 of each case warms up and
 is not counted; the summary is the median and the best window.  Every window starts from a reset (a fly without a floor falls, and an
-episode ends on its 13th step when the root has left the reference by 0.3 cm, so auto-resets are part of the steady state measured).
+episode ends on its 13th step when the root has left the reference by 0.3 cm, so auto-resets are part of the steady state measured;
+on the floor the states are the reset poses standing on it and what 50 steps make of them: the episodes run to the end of their clips).
 
 Shares: a run of its own under `rocprofv3 --kernel-trace --stats` (a fresh child process, `--trace-child`, 200 steps at +-0.5), whose
 kernel statistics are folded by launch."""
@@ -23,13 +25,15 @@ import tempfile
 
 sys.path.insert(0, os.path.join(os.path.dirname(__file__), ".."))
 
-LAUNCHES = ("episode_begin_kernel", "walk_reference_pose_kernel", "imitation_step_kernel", "walk_evaluate_kernel", "episode_close_kernel")
+def launches(floor):
+    return ("episode_begin_kernel", "walk_reference_pose_kernel", "imitation_floor_step" if floor else "imitation_step_kernel", "walk_evaluate_kernel",
+            "episode_close_kernel")
 
 
-def make_env(batch):
+def make_env(batch, floor=False):
     from flybody_amd import fly_envs
 
-    return fly_envs.walk_imitation(floor_contacts=False, batch_size=batch)
+    return fly_envs.walk_imitation(floor_contacts="primitives" if floor else False, batch_size=batch)
 
 
 def action_cases(torch, batch):
@@ -37,10 +41,10 @@ def action_cases(torch, batch):
     return {"zero": torch.zeros(batch, 59, device="cuda"), "uniform_0.5": (torch.rand(batch, 59, device="cuda", generator=g) - 0.5).contiguous()}
 
 
-def trace_child(batch, steps):
+def trace_child(batch, steps, floor):
     import torch
 
-    env = make_env(batch)
+    env = make_env(batch, floor)
     act = action_cases(torch, batch)["uniform_0.5"]
     env.reset()
     for _ in range(steps):
@@ -49,11 +53,11 @@ def trace_child(batch, steps):
     env.close()
 
 
-def launch_shares(batch, steps):
+def launch_shares(batch, steps, floor):
     """{launch: {"calls", "mean_us", "share"}} from a rocprofv3 run of `trace_child`."""
     with tempfile.TemporaryDirectory() as tmp:
         cmd = ["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", tmp, "-o", "walk_env", "--", sys.executable,
-               os.path.abspath(__file__), "--trace-child", "--batch", str(batch), "--trace-steps", str(steps)]
+               os.path.abspath(__file__), "--trace-child", "--batch", str(batch), "--trace-steps", str(steps)] + (["--floor"] if floor else [])
         r = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
         if r.returncode != 0:
             raise RuntimeError("rocprofv3 failed: " + (r.stderr or r.stdout)[-2000:])
@@ -61,6 +65,7 @@ def launch_shares(batch, steps):
         if not files:
             raise RuntimeError("rocprofv3 wrote no kernel statistics")
         rows = list(csv.DictReader(open(files[0])))
+    LAUNCHES = launches(floor)
     out, total = {}, 0.0
     for name in LAUNCHES:
         mine = [r for r in rows if name in r["Name"]]
@@ -79,12 +84,13 @@ def main():
     ap.add_argument("--windows", type=int, default=5)
     ap.add_argument("--iters", type=int, default=50)
     ap.add_argument("--trace-steps", type=int, default=200)
+    ap.add_argument("--floor", action="store_true", help="the environment on the floor plane instead of the one with the floor off")
     ap.add_argument("--no-trace", action="store_true", help="skip the rocprofv3 run")
     ap.add_argument("--trace-child", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--log", default=None, help="append the printed lines to this file")
     args = ap.parse_args()
     if args.trace_child:
-        trace_child(args.batch, args.trace_steps)
+        trace_child(args.batch, args.trace_steps, args.floor)
         return
     lines = []
 
@@ -94,11 +100,12 @@ def main():
         lines.append(line)
 
     if not args.no_trace:  # first, while this process has not touched the device
-        say({"batch": args.batch, "trace_steps": args.trace_steps, "launch_shares": launch_shares(args.batch, args.trace_steps)})
+        say({"batch": args.batch, "floor": args.floor, "trace_steps": args.trace_steps,
+             "launch_shares": launch_shares(args.batch, args.trace_steps, args.floor)})
     import torch
 
     B = args.batch
-    env = make_env(B)
+    env = make_env(B, args.floor)
     cases = action_cases(torch, B)
     ms = {k: [] for k in cases}
     for w in range(args.windows + 1):  # window 0 warms up
@@ -106,11 +113,11 @@ def main():
             env.reset()
             t = env.time_steps(act, args.iters)
             finite = bool(torch.isfinite(env.flat_observation).all())
-            say({"case": name, "window": w, "warmup": w == 0, "ms_per_step": t, "env_steps_per_s": B / t * 1e3, "finite": finite})
+            say({"case": name, "floor": args.floor, "window": w, "warmup": w == 0, "ms_per_step": t, "env_steps_per_s": B / t * 1e3, "finite": finite})
             if w > 0:
                 ms[name].append(t)
     kernel_ms = {name: env.time_kernel(act, args.iters) for name, act in cases.items()}
-    out = {"batch": B, "iters_per_window": args.iters, "windows": args.windows, "launches_per_step": len(LAUNCHES)}
+    out = {"batch": B, "floor": args.floor, "iters_per_window": args.iters, "windows": args.windows, "launches_per_step": len(launches(args.floor))}
     for name, t in ms.items():
         out[name] = {"median_ms_per_step": statistics.median(t), "best_ms_per_step": min(t), "median_env_steps_per_s": B / statistics.median(t) * 1e3,
                      "step_kernel_alone_ms": kernel_ms[name]}
