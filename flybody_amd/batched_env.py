@@ -28,6 +28,7 @@ FFE_WALK_JOINT_LIMITS = 512  # ffe_create_walk_physics only: joint limits on (pr
 FFE_WALK_EPISODES = 1024  # ffe_create_walk_physics only: the walk_imitation environment with the floor off (provisional opt-in)
 FFE_WALK_FLOOR = 2048  # ffe_create_walk_physics only: the floor plane against the fly's sphere / capsule geoms (opt-in; bare physics, or
 #                        with FFE_WALK_EPISODES the walk_imitation environment on the floor)
+FFE_WALK_SELF = 4096  # ffe_create_walk_physics only: the fly's own contacts on the bare-physics floor handle (provisional opt-in)
 
 
 # `env.validity()`: four int32 [B] views of one [B, 4] device buffer (include/flybody_env.h, ffe_get_validity)
@@ -487,6 +488,12 @@ class BatchedWalkPhysics(EnvHandle):
     step_bits carry 1 / 2 / 4.  `get_task_state()` then also gives int 5 = floor contacts of the last substep, real 0 = the sum of
     their normal forces, real 1 = the smallest contact distance.
 
+    `self_contacts=True` (step 3c; it needs `floor_contacts=True`) adds FFE_WALK_SELF: the fly's own contacts, its 48 sphere / capsule
+    geoms against each other and every candidate pair with an ellipsoid or a cylinder on one side, as frictionless normal rows between
+    the floor's cone blocks and the joint limits.  The 16 contact slots hold the floor's contacts first and the fly-fly ones behind
+    them.  `get_task_state()` int 5 then counts both kinds, int 3 the fly-fly ones among them, real 1 is taken over both kinds, and
+    step_bits bit value 8 says that a convex candidate pair was left out because a pair list of the substep was full.
+
     Tensor conventions are `BatchedBallEnv`'s: `get_state` returns float64 cuda tensors qpos[B, 109] = root position (float64 on the
     device too), root quaternion, 102 hinges and qvel[B, 108] = root linear velocity (world frame), root angular velocity (body
     frame), hinges; `set_state` takes the same and normalises the quaternion; `physics_step` takes float32 ctrl[B, 59]."""
@@ -494,11 +501,15 @@ class BatchedWalkPhysics(EnvHandle):
     task_kind = "walk_physics"
 
     def __init__(self, *, batch_size: int, device: int = 0, physics_flags: int = FFE_NO_CONTACT | FFE_NO_LIMIT, blob_path: str = WALK_BLOB,
-                 joint_limits: bool = False, floor_contacts: bool = False):
+                 joint_limits: bool = False, floor_contacts: bool = False, self_contacts: bool = False):
+        if self_contacts and not floor_contacts:
+            raise ValueError("BatchedWalkPhysics: self_contacts=True needs floor_contacts=True (the fly's own contacts are built on the floor handle)")
         if joint_limits or floor_contacts:
             physics_flags = (int(physics_flags) & ~(FFE_NO_CONTACT | FFE_NO_LIMIT)) | FFE_NO_CONTACT | FFE_WALK_JOINT_LIMITS
         if floor_contacts:
             physics_flags |= FFE_WALK_FLOOR
+        if self_contacts:
+            physics_flags |= FFE_WALK_SELF
         self._open(batch_size, device)
         with open(blob_path, "rb") as f:
             blob = f.read()

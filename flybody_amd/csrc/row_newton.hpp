@@ -29,6 +29,17 @@ struct ConeRows {
   static constexpr bool kWarmStart = true;      // lambda from / to T.r_lam; the first iteration is only tested when `have_ws`
   static constexpr bool kSyncAfterLoad = false;
   static constexpr int kMaxNewton = 12;
+  static constexpr bool kRevertByResidual = false;  // the noslip sweep's revert test: see ConeRowsResidual
+};
+// ConeRows with the noslip sweep's revert test scaled by what its rounding error scales with.  mj's costChange reverts an update whose
+// cost change is positive (a failed QCQP).  The change is d . res + d' A d / 2 with d the difference of two forces of size |f|, known
+// to ~1e-7 |f| in float32, so its error is ~1e-7 |res| |f| whatever the size of the change itself.  ConeRows' threshold, 1e-4 of
+// (|d . res| + |d' A d / 2|), is below that error once a sweep's genuine gain is small: on a sliding contact of the free-root fly the
+// third sweep then reverts or not by rounding (walk_self_env.hip, R10 state 8: 3e-4 ... 8e-4 rad/s of root angular velocity).  Here the
+// threshold is 1e-5 (|res_1| + |res_2|) (|new| + |old|): a hundred times the error, and four orders below the change of a QCQP
+// that fails and returns zero.  A policy of its own so that the instantiations of ConeRows compile to the instructions they had.
+struct ConeRowsResidual : ConeRows {
+  static constexpr bool kRevertByResidual = true;
 };
 struct ScalarRows {
   static constexpr bool kCones = false;
@@ -321,7 +332,8 @@ __device__ __noinline__ int row_newton(Tile *Tp, const BallModel FFE_GLOBAL *Mp,
             // cancel to ~1e-7 of their size, so the threshold is taken relative to them; a genuine failure is far above it.
             const float lin_ = d0 * res0 + d1 * res1, quad_ = 0.5f * (d0 * (A00 * d0 + A01 * d1) + d1 * (A01 * d0 + A11 * d1));
             float change = lin_ + quad_;
-            if (change > 1e-10f + 1e-4f * (fabsf(lin_) + fabsf(quad_))) { v0 = o0; v1 = o1; d0 = d1 = 0.f; change = 0.f; }
+            if (change > 1e-10f + (P::kRevertByResidual ? 1e-5f * (fabsf(res0) + fabsf(res1)) * (fabsf(v0) + fabsf(v1) + fabsf(o0) + fabsf(o1))
+                                                        : 1e-4f * (fabsf(lin_) + fabsf(quad_)))) { v0 = o0; v1 = o1; d0 = d1 = 0.f; change = 0.f; }
             improvement -= fminf(change, 0.f);
             fv = lane == r0 ? v0 : (lane == r1 ? v1 : fv);
             res += G_(r0) * d0 + G_(r1) * d1;

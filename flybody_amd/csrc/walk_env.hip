@@ -43,6 +43,7 @@
 
 #include "walk_env.hpp"
 #include "walk_model.hpp"
+#include "walk_self_model.hpp"
 #include "leg_dyn.hpp"
 #include "row_newton.hpp"
 #include "walk_imu.hpp"
@@ -263,14 +264,16 @@ __global__ void walk_limits_report_kernel(const WState *states, int *ints, doubl
 }
 // floor handle: the limits handle's report with int 5 = floor contacts kept in the last substep, real 0 = the sum of their normal
 // forces, real 1 = the smallest contact distance (0 without a contact); validity {overflow bits of the last launch (1 more contacts
-// than slots, 2 more rows than RMAX, 4 more rows in a block than columns), 0, 0, 0}
+// than slots, 2 more rows than RMAX, 4 more rows in a block than columns), 0, 0, 0}.  With FFE_WALK_SELF int 5 counts the floor and the
+// fly-fly contacts kept, int 3 the fly-fly ones among them (0 otherwise), real 1 is taken over both kinds, and bit value 8 says that a
+// convex candidate pair was left out because a pair list of the substep was full
 __global__ void floor_report_kernel(const WState *states, const FloorRec *rec, int *ints, double *reals, int *info, int batch) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= batch) return;
   const WState &S = states[i];
   if (ints) {
     int *o = ints + (size_t)i * 8;
-    o[0] = o[1] = o[2] = o[3] = 0; o[4] = S.nlim; o[5] = rec[i].ncon; o[6] = S.iters; o[7] = S.step_bits;
+    o[0] = o[1] = o[2] = 0; o[3] = rec[i].nself; o[4] = S.nlim; o[5] = rec[i].ncon; o[6] = S.iters; o[7] = S.step_bits;
     for (int k = 0; k < 8; k++) reals[(size_t)i * 8 + k] = k == 0 ? (double)rec[i].fsum : (k == 1 ? (double)rec[i].mind : 0.0);
   }
   if (info) *reinterpret_cast<int4 *>(info + (size_t)i * 4) = make_int4(S.step_bits, 0, 0, 0);
@@ -291,6 +294,7 @@ struct WalkEnv final : ffe::EnvBackend {
   bool limits = false;    // FFE_WALK_JOINT_LIMITS: walk_limits_kernel steps this handle
   bool episodes = false;  // FFE_WALK_EPISODES: ffe_step / ffe_reset / ... work, imitation_step_kernel steps them
   bool floor = false;     // FFE_WALK_FLOOR: floor_step steps this handle (with `episodes`: imitation_floor_step)
+  bool self = false;      // FFE_WALK_SELF (with `floor`, without `episodes`): floor_self_step of walk_self_env.hip steps this handle
   FloorRec *rec = nullptr;  // floor handle only: contacts, normal-force sum and smallest distance of the last substep
   WalkHost host;
   ffe::DeviceBuffers mem{"ffe_create_walk_physics"};  // everything below lives here
@@ -342,7 +346,8 @@ struct WalkEnv final : ffe::EnvBackend {
     hipStream_t s = (hipStream_t)stream;
     if (mode == 2) {  // bare physics: act = ctrl[B][59]
       if (!act || nphys <= 0) throw std::runtime_error("walk physics: null control buffer or no steps");
-      if (floor) hipLaunchKernelGGL(floor_step, dim3(batch), dim3(64), 0, s, model_dev, flags, states, act, rec, batch, nphys);
+      if (self) launch_floor_self_step(model_dev, flags, states, act, rec, batch, nphys, s);
+      else if (floor) hipLaunchKernelGGL(floor_step, dim3(batch), dim3(64), 0, s, model_dev, flags, states, act, rec, batch, nphys);
       else if (limits) hipLaunchKernelGGL(walk_limits_kernel, dim3(batch), dim3(64), 0, s, model_dev, flags, states, act, batch, nphys);
       else hipLaunchKernelGGL(walk_step_kernel, dim3(batch), dim3(64), 0, s, model_dev, flags, states, act, batch, nphys);
       HIP_OK(hipGetLastError());
@@ -483,7 +488,18 @@ std::unique_ptr<ffe::EnvBackend> walk_create(const void *blob, size_t blob_size,
   if (!blob || batch <= 0) throw std::runtime_error("ffe_create_walk_physics: bad arguments");
   const bool limits = (physics_flags & BF_WALK_JOINT_LIMITS) != 0, no_limit = (physics_flags & BF_NO_LIMIT) != 0;
   const bool episodes = (physics_flags & BF_WALK_EPISODES) != 0, floor = (physics_flags & BF_WALK_FLOOR) != 0;
-  if (floor && episodes) {
+  const bool self = (physics_flags & BF_WALK_SELF) != 0;
+  if (self) {
+    const int switches = BF_NO_FLUID | BF_NO_DAMPER | BF_NO_SPRING | BF_NO_GRAVITY | BF_NO_ACTUATION | BF_NO_NOSLIP | BF_NO_ADHESION;
+    if (episodes)
+      throw std::runtime_error("ffe_create_walk_physics: FFE_WALK_SELF (the fly's own contacts) with FFE_WALK_EPISODES: the walk_imitation environment "
+                               "(FFE_WALK_EPISODES, with or without FFE_WALK_FLOOR) does not carry the fly's own contacts yet; the bit is accepted on "
+                               "the bare-physics floor handle only");
+    if ((physics_flags & ~switches) != (BF_NO_CONTACT | BF_WALK_JOINT_LIMITS | BF_WALK_FLOOR | BF_WALK_SELF))
+      throw std::runtime_error("ffe_create_walk_physics: FFE_WALK_SELF (the fly's own contacts on the bare-physics floor handle) is accepted only as "
+                               "FFE_NO_CONTACT | FFE_WALK_JOINT_LIMITS | FFE_WALK_FLOOR | FFE_WALK_SELF plus the force switches, FFE_NO_NOSLIP and "
+                               "FFE_NO_ADHESION");
+  } else if (floor && episodes) {
     const int switches = BF_NO_FLUID | BF_NO_DAMPER | BF_NO_SPRING | BF_NO_GRAVITY | BF_NO_ACTUATION | BF_NO_NOSLIP | BF_NO_ADHESION;
     if ((physics_flags & ~switches) != (BF_NO_CONTACT | BF_WALK_JOINT_LIMITS | BF_WALK_EPISODES | BF_WALK_FLOOR))
       throw std::runtime_error("ffe_create_walk_physics: FFE_WALK_EPISODES | FFE_WALK_FLOOR (the walk_imitation environment on the floor plane) needs "
@@ -513,7 +529,8 @@ std::unique_ptr<ffe::EnvBackend> walk_create(const void *blob, size_t blob_size,
   std::unique_ptr<WalkEnv> e(new WalkEnv());  // frees the device allocations made so far if a later step throws
   Blob b(blob, blob_size);
   e->host = build_walk_model(b);
-  e->device = device; e->batch = batch; e->flags = physics_flags & ~BF_WALK_EPISODES; e->limits = limits; e->episodes = episodes; e->floor = floor;
+  e->device = device; e->batch = batch; e->flags = physics_flags & ~BF_WALK_EPISODES; e->limits = limits; e->episodes = episodes; e->floor = floor; e->self = self;
+  if (self) build_walk_self(b, e->host);  // (before the model goes to the device)
   if (floor && !e->host.m.x.f_ok)
     throw std::runtime_error("ffe_create_walk_physics: FFE_WALK_FLOOR: the floor's contacts are expected to be condim 3 with one solimp");
   e->host.m.b.nsub = 10;  // the reference's control step of 2 ms over the model's 0.2 ms (bare physics: ffe_spec's figure alone)

@@ -1,7 +1,8 @@
 // walk_substeps.hpp - the device code of the free-root substep that more than one translation unit compiles: the state record, the LDS
 // tiles, the wave's context, stage 1 / stage 2 with the limit and floor constraint blocks, the substep loop and the state export.
-// walk_env.hip (the four kernels of bare physics and of the floor-off environment) and walk_floor_env.hip (the environment on the floor)
-// include it; what the code does is described at the head of walk_env.hip and where each part starts.
+// walk_env.hip (the four kernels of bare physics and of the floor-off environment), walk_floor_env.hip (the environment on the floor) and
+// walk_self_env.hip (bare physics with the fly's own contacts) include it; what the code does is described at the head of walk_env.hip
+// and where each part starts.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -16,6 +17,7 @@
 #include "walk_imu.hpp"
 #include "walk_floor.hpp"
 #include "walk_sense.hpp"
+#include "walk_self.hpp"
 
 
 namespace ffw {
@@ -38,6 +40,7 @@ static_assert(sizeof(WState) == 1168, "the four ints fill what used to be paddin
 constexpr int BF_WALK_JOINT_LIMITS = 512;  // FFE_WALK_JOINT_LIMITS: host side only, the kernels do not read it
 constexpr int BF_WALK_EPISODES = 1024;     // FFE_WALK_EPISODES: host side only
 constexpr int BF_WALK_FLOOR = 2048;        // FFE_WALK_FLOOR: host side only (it selects the floor kernel)
+constexpr int BF_WALK_SELF = 4096;         // FFE_WALK_SELF: host side only (it selects the kernel with the fly's own contacts)
 constexpr int LCOL = 16;                  // solve columns per block of M: a block has at most NSTEP = 14 hinges, each with one limit row
 static_assert(NSTEP <= LCOL, "a block's limit rows must fit its columns");
 
@@ -135,7 +138,7 @@ struct FloorCtx {
   int nc;          // contacts kept in this substep
   float mind;      // smallest distance
 };
-struct FloorRec { int ncon; float fsum, mind; int pad; };
+struct FloorRec { int ncon; float fsum, mind; int nself; };  // (nself: the fly-fly contacts among ncon; 0 without FFE_WALK_SELF)
 
 // Tile of the episode kernel: the limits kernel's, plus the sensor sums of a control step (accelerometer 3, gyro 3, velocimeter 3,
 // force 18, touch 6: the order of the oracle's buffer)
@@ -164,6 +167,35 @@ template <class T, class = void>
 struct is_sense_tile : std::false_type {};
 template <class T>
 struct is_sense_tile<T, std::enable_if_t<T::kSense>> : std::true_type {};
+
+// Tile of the kernel with the fly's own contacts (walk_self_env.hip `floor_self_step`, FFE_WALK_SELF): the
+// floor kernel's, whose contact tables now hold the floor contacts in the first slots and the fly-fly contacts behind them (NC in all).
+// A fly-fly slot k keeps the link of geom2 in c_link / c_blk / c_amask (entries +n . u of its row), the link of geom1 in c_link1 /
+// c_blk1 / c_amask1 (entries -n . u; 255: a geom of the thorax, which is the root and has no chain), its normal in c_nrm, -aref of its
+// row in c_vel[k][0] and its D in c_D; c_col1 is the solve column of geom1's chain when that lies in another block of M.  A floor slot has
+// c_link1 = 255.  The scratch of the two collision passes lies over floats that are dead between stage 1 and stage 2:
+//   sphere / capsule pairs   centre | bounding radius and axis | half length of the 48 slots over X4, their radii over the tail of G
+//                            (behind the link poses `lp`)
+//   convex pairs             centre | bounding radius of the 70 geoms, then the two pair lists, over X4 (the orientation of a geom is
+//                            composed from its link's pose where it is needed)
+// F is read by stage 2 on a walker, so - unlike on the tethered fly - the link exchange `lk` over it is not free here.
+struct alignas(16) WTileX : WTileF {
+  static constexpr bool kSelf = true;
+  float c_nrm[NC][3];
+  unsigned short c_amask1[NC];
+  unsigned char c_link1[NC], c_blk1[NC], c_col1[NC];
+  float sv0[8];  // the root's spatial velocity (w_b, v_b): what a geom of the thorax moves with
+};
+static_assert(sizeof(WTileX) <= 20480, "the tile must leave room for 8 waves per CU");
+static_assert(2 * NPG <= NDP && NL * 14 + NPG <= RMAX * (RMAX + 1) / 2, "the primitive slots must fit over X4 and the tail of G");
+static_assert((NG + (CL1 * 2 + 15) / 16 + (CL2 * 2 + 15) / 16) <= NDP, "the geom centres and the pair lists must fit over X4");
+template <class T, class = void>
+struct is_self_tile : std::false_type {};
+template <class T>
+struct is_self_tile<T, std::enable_if_t<T::kSelf>> : std::true_type {};
+struct SelfCtx : FloorCtx {
+  int ns;          // fly-fly contacts kept in this substep: slots nc .. nc + ns - 1
+};
 
 // What the episode kernel reads besides the model and the state: fixed at create, in device memory, fetched by scalar loads where it
 // is used (as kernel arguments its thirty dwords stayed in SGPRs over the whole substep loop and spilled into VGPR lanes).
@@ -208,7 +240,7 @@ struct CtxT {
   I10 Itree;    // spatial inertia of the whole tree about the root origin = M_rr
   S6 Ftot;      // bias force of the whole tree without gravity = -(root rows of the smooth force)
   int overflow; // limits kernel: overflow bits of this launch
-  std::conditional_t<is_floor_tile<Tile>::value, FloorCtx, NoEpisode> fl;
+  std::conditional_t<is_self_tile<Tile>::value, SelfCtx, std::conditional_t<is_floor_tile<Tile>::value, FloorCtx, NoEpisode>> fl;
 };
 
 // ------------------------------------------------------------------------------------------------ stage 1
@@ -806,6 +838,560 @@ __device__ __forceinline__ int floor_forces(C &c, const int R, const int (&lrow)
   return iters;
 }
 
+// ------------------------------------------------------------------------------------------------ the fly's own contacts
+// (FFE_WALK_SELF)  ball_env.hip's `self_collide` and `convex_collide` restated on the walker's tile, in
+// the root frame: the geoms' frames come from the link poses `floor_collide` has published (T.lp), the narrow phase of the convex pairs
+// is cvx:: of convex.hpp as it is.  Both run after `floor_collide`, whose contacts keep the first slots; the fly-fly contacts follow.
+// Templates on the tile so that only the kernel that calls them instantiates them.
+//
+// Stores fly-fly contact `at`: geom1 on link l1, geom2 on link l2 (-1: the thorax), normal n from geom1 to geom2.  A pair whose geom2
+// is the thorax's is stored the other way round with the normal turned, so that c_link always names a link with a chain.
+template <class TileX>
+__device__ __forceinline__ void self_put(TileX &T, const BallModel FFE_GLOBAL &M, const int at, const int l1, const int l2, V3 n, const V3 p, const float dist,
+                                         const float margin, const float invw) {
+  const float incl = margin - (margin != 0.f ? M.sc_gap : 0.f);
+  int lpos = l2, lneg = l1;
+  if (lpos < 0) { lpos = l1; lneg = -1; n = V3{-n.x, -n.y, -n.z}; }
+  const float pp[3] = {p.x, p.y, p.z}, nn[3] = {n.x, n.y, n.z};
+  const float vel = wsf::row_velocity<float>(&T.lp[lpos][7], lneg >= 0 ? &T.lp[lneg][7] : T.sv0, pp, nn);
+  float si_[5];
+#pragma unroll
+  for (int q2 = 0; q2 < 5; q2++) si_[q2] = M.sc_solimp[q2];
+  const float imp = impedance(si_, fabsf(dist - incl));
+  const bool excl = dist >= incl;  // inside the margin but not inside margin - gap: kept (an adhesion actuator counts it), exerts nothing
+  T.c_pos[at][0] = p.x; T.c_pos[at][1] = p.y; T.c_pos[at][2] = p.z;
+  T.c_nrm[at][0] = n.x; T.c_nrm[at][1] = n.y; T.c_nrm[at][2] = n.z;
+  T.c_dist[at] = dist; T.c_excl[at] = excl ? 1 : 0;
+  T.c_D[at] = excl ? 0.f : wsf::row_D<float>(imp, invw);
+  T.c_vel[at][0] = wsf::row_neg_aref<float>(M.sc_K, M.sc_B, imp, dist, incl, vel); T.c_vel[at][1] = 0.f; T.c_vel[at][2] = 0.f;
+  T.c_mu[at] = 0.f; T.c_geom[at] = 0;
+  const int fp = M.l_chain[M.l_nchain[lpos] - 1][lpos];
+  T.c_link[at] = (unsigned char)lpos; T.c_blk[at] = (unsigned char)M.d_blk[fp]; T.c_amask[at] = (unsigned short)M.d_amask[fp];
+  if (lneg >= 0) {
+    const int fn = M.l_chain[M.l_nchain[lneg] - 1][lneg];
+    T.c_link1[at] = (unsigned char)lneg; T.c_blk1[at] = (unsigned char)M.d_blk[fn]; T.c_amask1[at] = (unsigned short)M.d_amask[fn];
+  } else { T.c_link1[at] = 255; T.c_blk1[at] = 255; T.c_amask1[at] = 0; }
+}
+
+// mj: mj_collision over the fly's own sphere / capsule pairs (mjc_CapsuleCapsule; a sphere is a capsule of zero length), condim 1: see
+// ball_env.hip `self_collide`.  Lane s makes slot s from the floor table's geom s (the same 48 geoms) and then meets slots s + 1 .. s +
+// NPG / 2 (mod NPG).  A detected contact takes the next slot after the `nprev` contacts stored so far; beyond NC the deepest fly-fly
+// contacts are kept.  A contact inside its margin but outside margin - gap with no adhesion actuator on either link takes no slot and is
+// counted apart.  Returns contacts stored | overflow << 8 | contacts without a slot << 16.  Out of line and a leaf.
+template <class TileX>
+__device__ __noinline__ int self_prim_collide(TileX *Tp, ModelPtr Mp, const WalkExtra FFE_GLOBAL *Xp, const int lane, const int nprev) {
+  TileX &T = *Tp;
+  const BallModel FFE_GLOBAL &M = *Mp;
+  const WalkExtra FFE_GLOBAL &X = *Xp;
+  float4 *pgc = &T.X4[0], *pga = pgc + NPG;  // (centre, bounding radius), (axis, half length)
+  float *pgr = &T.G[NL * 14];                // radius: behind the link poses
+  const bool own = lane < NPG;
+  if (own) {
+    const float *lp = T.lp[X.f_link[lane]];
+    const M3 R = q2m(Q4{lp[3], lp[4], lp[5], lp[6]});
+    const V3 gc = V3{lp[0], lp[1], lp[2]} + mv(R, V3{X.f_pos[0][lane], X.f_pos[1][lane], X.f_pos[2][lane]});
+    const V3 ga = mv(R, V3{X.f_axis[0][lane], X.f_axis[1][lane], X.f_axis[2][lane]});
+    const float half = X.f_half[lane], rad = X.f_rad[lane];
+    pgc[lane] = make_float4(gc.x, gc.y, gc.z, half + rad);
+    pga[lane] = make_float4(ga.x, ga.y, ga.z, half);
+    pgr[lane] = rad;
+  }
+  DM_SYNC();
+  const float mclaw = M.sc_margin;
+  const unsigned long long claws = M.sp_claw;
+  const int sphere = M.sp_sphere;
+  const unsigned long long partners = own ? M.sp_mask[lane] : 0ull;
+  const float4 o0 = own ? pgc[lane] : make_float4(0.f, 0.f, 0.f, 0.f);
+  const float oreach = o0.w + (((claws >> lane) & 1ull) ? mclaw : 0.f);
+  unsigned near = 0u;  // bit t - 1: the pair (lane, lane + t) passed the bounding-sphere test
+#pragma unroll 4
+  for (int t = 1; t <= NPG / 2; t++) {
+    int j = lane + t;
+    j = j >= NPG ? j - NPG : j;
+    if (own && ((partners >> j) & 1ull) && (t < NPG / 2 || lane < NPG / 2)) {
+      const float4 p0 = pgc[j];
+      const float dx = p0.x - o0.x, dy = p0.y - o0.y, dz = p0.z - o0.z;
+      const float reach = oreach + p0.w + mclaw;
+      if (dx * dx + dy * dy + dz * dz <= reach * reach) near |= 1u << (t - 1);
+    }
+  }
+  int nsc = 0, ovf = 0, ndrop = 0;
+#pragma unroll 1
+  while (__ballot(near != 0u) != 0ull) {
+    bool hit = false;
+    float dist = 0.f, margin = 0.f;
+    V3 nrm = {1.f, 0.f, 0.f}, cpos = {0.f, 0.f, 0.f};
+    int s1 = 0, s2 = 0;
+    if (near) {
+      const int t = __ffs(near);
+      near &= near - 1u;
+      int j = lane + t;
+      j = j >= NPG ? j - NPG : j;
+      // mj: geom1 is the one with the lower type code (the sphere), else the one that comes first in the model
+      const bool swap = j == sphere || (lane != sphere && j < lane);
+      s1 = swap ? j : lane; s2 = swap ? lane : j;
+      const float4 ca = pgc[s1], aa = pga[s1], cb_ = pgc[s2], ab = pga[s2];
+      const V3 p1 = {ca.x, ca.y, ca.z}, a1 = {aa.x, aa.y, aa.z}, p2 = {cb_.x, cb_.y, cb_.z}, a2 = {ab.x, ab.y, ab.z};
+      const float l1 = aa.w, r1 = pgr[s1], l2 = ab.w, r2 = pgr[s2];
+      margin = (((claws >> s1) | (claws >> s2)) & 1ull) ? mclaw : 0.f;
+      const V3 dif = p1 - p2;
+      const float mb = -dot(a1, a2), u = -dot(a1, dif), v = dot(a2, dif), det = 1.f - mb * mb;
+      float x1, x2;
+      if (fabsf(det) >= 1e-6f) {
+        const float idet = 1.f / det;
+        x1 = (u - mb * v) * idet; x2 = (v - mb * u) * idet;
+        if (x1 > l1) { x1 = l1; x2 = v - mb * l1; } else if (x1 < -l1) { x1 = -l1; x2 = v + mb * l1; }
+        if (x2 > l2) { x2 = l2; x1 = fminf(fmaxf(u - mb * l2, -l1), l1); }
+        else if (x2 < -l2) { x2 = -l2; x1 = fminf(fmaxf(u + mb * l2, -l1), l1); }
+      } else {  // parallel axes: centre of the overlapping stretch
+        const float c2 = u, lo = fmaxf(-l1, c2 - l2), hi = fminf(l1, c2 + l2);
+        x1 = lo <= hi ? 0.5f * (lo + hi) : (c2 > 0.f ? l1 : -l1);
+        x2 = fminf(fmaxf((x1 - c2) * (mb < 0.f ? 1.f : -1.f), -l2), l2);
+      }
+      const V3 q1 = p1 + x1 * a1, q2 = p2 + x2 * a2, d12 = q2 - q1;
+      const float cd = fsqrt(dot(d12, d12));
+      hit = cd <= margin + r1 + r2;
+      if (cd >= 1e-15f) nrm = frcp(cd) * d12;
+      dist = cd - r1 - r2;
+      cpos = q1 + (r1 + 0.5f * dist) * nrm;
+    }
+    const bool dropped = hit && dist >= margin - (margin != 0.f ? M.sc_gap : 0.f) && M.l_adh[M.pgs_link[s1]] < 0 && M.l_adh[M.pgs_link[s2]] < 0;
+    hit = hit && !dropped;
+    ndrop += __popcll(__ballot(dropped));
+    const unsigned long long bal = __ballot(hit);
+    if (bal) {
+      const int idx = nprev + nsc + __popcll(bal & ((1ull << lane) - 1ull));
+      auto store = [&](int at) { self_put(T, M, at, M.pgs_link[s1], M.pgs_link[s2], nrm, cpos, dist, margin, M.pgs_invw[s1] + M.pgs_invw[s2]); };
+      if (hit && idx < NC) store(idx);
+      const int n = __popcll(bal);
+      const bool over = nprev + nsc + n > NC;
+      nsc = min(nsc + n, NC - nprev);
+      if (over && nprev < NC) {
+        // a hit without a slot takes the place of the shallowest fly-fly contact held so far if it is deeper
+        ovf = 1;
+        DM_SYNC();
+        for (unsigned long long left = __ballot(hit && idx >= NC); left; left &= left - 1) {
+          const int j = __ffsll((long long)left) - 1;
+          float shallow = -1e30f;
+          int at = -1;
+          for (int k = nprev; k < NC; k++) { const float dk = T.c_dist[k]; if (dk > shallow) { shallow = dk; at = k; } }
+          if (__shfl(dist, j) < shallow) { if (lane == j) store(at); DM_SYNC(); }
+        }
+      } else if (over) ovf = 1;
+    }
+  }
+  DM_SYNC();
+  return nsc | (ovf << 8) | (ndrop << 16);
+}
+
+// the world (here: root) frame of fly geom g: its centre from the table the convex pass has made, its orientation from its link's pose
+template <class TileX>
+__device__ __forceinline__ cvx::Geom self_geom(const TileX &T, const BallModel FFE_GLOBAL &M, const float4 *gc, const int g) {
+  const float4 cc = gc[g];
+  Q4 q = {M.cg_quat[0][g], M.cg_quat[1][g], M.cg_quat[2][g], M.cg_quat[3][g]};
+  const int l = M.cg_link[g];
+  if (l >= 0) { const float *lp = T.lp[l]; q = qnormalize(qmul(Q4{lp[3], lp[4], lp[5], lp[6]}, q)); }
+  return cvx::Geom{V3{cc.x, cc.y, cc.z}, q, M.cg_size[0][g], M.cg_size[1][g], M.cg_size[2][g], M.cg_type[g]};
+}
+
+// The fly's own pairs with an ellipsoid or a cylinder on one side (mj: mjc_Convex): see ball_env.hip `convex_collide`.  Bounding-sphere
+// test over the static candidate list, a separating-direction bound on the survivors, then one lane per remaining pair in the narrow
+// phase (cvx::collide).  No separating direction is remembered from substep to substep: a launch's result is a function of its state
+// alone, and the narrow phase always starts cold.  Returns contacts stored | overflow << 8 | (a pair list was full: candidates were
+// left out) << 9 | contacts without a slot << 16.  Out of line and a leaf.
+template <class TileX>
+__device__ __noinline__ int self_convex_collide(TileX *Tp, ModelPtr Mp, const int lane, const int nprev) {
+  TileX &T = *Tp;
+  const BallModel FFE_GLOBAL &M = *Mp;
+  float4 *gc = &T.X4[0];
+  unsigned short *cl1 = reinterpret_cast<unsigned short *>(gc + NG), *cl2 = cl1 + ((CL1 + 7) / 8) * 8;
+  const int ncg = M.ncg;
+  for (int g = lane; g < ncg; g += 64) {
+    const int l = M.cg_link[g];
+    V3 gp = {M.cg_pos[0][g], M.cg_pos[1][g], M.cg_pos[2][g]};
+    if (l >= 0) { const float *lp = T.lp[l]; gp = V3{lp[0], lp[1], lp[2]} + qrot(Q4{lp[3], lp[4], lp[5], lp[6]}, gp); }
+    gc[g] = make_float4(gp.x, gp.y, gp.z, M.cg_brad[g]);
+  }
+  DM_SYNC();
+  const unsigned long long mm0 = M.cg_mmask[0], mm1 = M.cg_mmask[1];
+  const float mclaw = M.sc_margin;
+  auto pair_margin = [&](int a, int b) {
+    const bool ma = a < 64 ? ((mm0 >> a) & 1ull) : ((mm1 >> (a - 64)) & 1ull), mb = b < 64 ? ((mm0 >> b) & 1ull) : ((mm1 >> (b - 64)) & 1ull);
+    return (ma || mb) ? mclaw : 0.f;
+  };
+  auto no_adhesion = [&](int a, int b) {
+    const int la_ = M.cg_link[a], lb_ = M.cg_link[b];
+    return (la_ < 0 || M.l_adh[la_] < 0) && (lb_ < 0 || M.l_adh[lb_] < 0);
+  };
+  int n1 = 0, full = 0;
+  const int ncp = M.ncp;
+#pragma unroll 1
+  for (int base = 0; base < ncp; base += 64) {
+    const unsigned w = M.cp_pair[base + lane];
+    bool pass = false;
+    if (w != 0xffffu) {
+      const int a = w & 255, b = w >> 8;
+      const float4 ca = gc[a], cb = gc[b];
+      const float dx = cb.x - ca.x, dy = cb.y - ca.y, dz = cb.z - ca.z, reach = ca.w + cb.w + pair_margin(a, b);
+      pass = dx * dx + dy * dy + dz * dz <= reach * reach;
+    }
+    const unsigned long long bal = __ballot(pass);
+    const int idx = n1 + __popcll(bal & ((1ull << lane) - 1ull));
+    if (pass && idx < CL1) cl1[idx] = (unsigned short)w;
+    n1 += __popcll(bal);
+  }
+  if (n1 > CL1) { n1 = CL1; full = 1; }
+  DM_SYNC();
+  int n2 = 0;
+#pragma unroll 1
+  for (int base = 0; base < n1; base += 64) {
+    bool pass = false;
+    unsigned w = 0u;
+    if (base + lane < n1) {
+      w = cl1[base + lane];
+      const int a = w & 255, b = w >> 8;
+      // the distance that matters: the margin where an adhesion actuator shares its pull over every detected contact of its body,
+      // margin - gap (a contact beyond it exerts no force and gets no slot) otherwise
+      float thr = pair_margin(a, b);
+      if (thr != 0.f && no_adhesion(a, b)) thr -= M.sc_gap;
+      pass = cvx::separation_bound(self_geom(T, M, gc, a), self_geom(T, M, gc, b)) <= thr;
+    }
+    const unsigned long long bal = __ballot(pass);
+    const int idx = n2 + __popcll(bal & ((1ull << lane) - 1ull));
+    if (pass && idx < CL2) cl2[idx] = (unsigned short)w;
+    n2 += __popcll(bal);
+  }
+  if (n2 > CL2) { n2 = CL2; full = 1; }
+  DM_SYNC();
+  bool hit = false, dropped = false;
+  float dist = 0.f, margin = 0.f;
+  V3 nrm = {1.f, 0.f, 0.f}, cpos = {0.f, 0.f, 0.f};
+  int a = 0, b = 0;
+  if (lane < n2) {
+    const unsigned w = cl2[lane];
+    a = w & 255; b = w >> 8;
+    margin = pair_margin(a, b);
+    const cvx::Contact ct = cvx::collide(self_geom(T, M, gc, a), self_geom(T, M, gc, b));
+    dist = ct.dist; nrm = ct.n; cpos = ct.pos;
+    hit = dist <= margin;
+    if (hit && dist >= margin - (margin != 0.f ? M.sc_gap : 0.f)) {  // (inactive and no adhesion actuator takes part: no slot)
+      dropped = no_adhesion(a, b);
+      hit = !dropped;
+    }
+  }
+  unsigned long long bal = __ballot(hit);
+  int ovf = 0;
+  if (nprev + __popcll(bal) > NC) {  // more than the free slots: the env is flagged and the deepest are kept
+    ovf = 1;
+    int rank = 0;
+    for (unsigned long long m = bal; m; m &= m - 1) {
+      const int j = __ffsll((long long)m) - 1;
+      const float dj = __shfl(dist, j);
+      if (dj < dist || (dj == dist && j < lane)) rank++;
+    }
+    hit = hit && rank < NC - nprev;
+    bal = __ballot(hit);
+  }
+  const int n = __popcll(bal), idx = nprev + __popcll(bal & ((1ull << lane) - 1ull));
+  if (hit && idx < NC) self_put(T, M, idx, M.cg_link[a], M.cg_link[b], nrm, cpos, dist, margin, M.cg_invw[a] + M.cg_invw[b]);
+  DM_SYNC();
+  return n | (ovf << 8) | (full << 9) | (__popcll(__ballot(dropped)) << 16);
+}
+
+// sum over the fly-fly contacts whose row touches hinge f of J[k][f] w[k - nc] (w: the rows' forces or the adhesion pulls)
+template <class TileX>
+__device__ __forceinline__ float self_gather(const TileX &T, const BallModel FFE_GLOBAL &M, const int nc, const int ns, const int f, const float *w) {
+  const int blk = M.d_blk[f], li = M.d_li[f];
+  float acc = 0.f;
+  for (int j = 0; j < ns; j++) {
+    const int k = nc + j;
+    const bool on_pos = (int)T.c_blk[k] == blk && (((unsigned)T.c_amask[k] >> li) & 1u);
+    const bool on_neg = (int)T.c_blk1[k] == blk && (((unsigned)T.c_amask1[k] >> li) & 1u);
+    if (on_pos != on_neg) acc += wsf::row_hinge<float>(T.C[f], T.c_pos[k], T.c_nrm[k], on_pos, on_neg) * w[j];
+  }
+  return acc;
+}
+
+// The constraint block of a substep with the fly's own contacts: `floor_forces` with one more kind of row between the floor's cone blocks
+// and the joint limits - rows 0 .. 3 nc - 1 the floor contacts, then one normal row per fly-fly contact, then the limits (the oracle
+// lists limits first and the contacts in pair order; the solution of the convex problem does not depend on the order of its rows).  A
+// fly-fly row is a scalar row of the solver, like a limit row, over the hinges of two chains (walk_self.hpp): no entry on the root, so
+//   w = -J_j Y_m in the rank-6 term, no w_b x v_b / gravity term in y0, nothing on the root's right-hand side.
+// Its two chains may lie in two blocks of M: it then owns a column in each.  The adhesion pull of a body is the mean over all of its
+// contacts, fly-fly ones included (mjTRN_BODY).  Returns the solver's iterations.
+template <class C>
+__device__ __forceinline__ int self_forces(C &c, const int R, const int (&lrow)[3], const float (&lsgn)[3], float (&qs)[3]) {
+  WTileX &T = *c.T;
+  const BallModel FFE_GLOBAL &M = model(c);
+  const WalkExtra FFE_GLOBAL &X = *c.X;
+  const int lane = c.lane, nc = c.fl.nc, ns = c.fl.ns, nrc = 3 * nc, nrs = nrc + ns, ncs = nc + ns;
+  const bool row = lane < R, crow = lane < nrc, srow = lane >= nrc && lane < nrs, jrow = lane < nrs;
+  float er[3] = {0.f, 0.f, 0.f};  // this row's direction: a floor row's normal or tangent, a fly-fly row's normal
+  // contacts of link `l`, on either side
+  auto contacts_of = [&](int l) { int n = 0; for (int j = 0; j < ncs; j++) n += ((int)T.c_link[j] == l || (int)T.c_link1[j] == l) ? 1 : 0; return n; };
+  {
+  float fr[9];
+  floor_frame(c, fr);
+  if (crow) { const int r3 = 3 * (lane - 3 * (lane / 3)); er[0] = fr[r3]; er[1] = fr[r3 + 1]; er[2] = fr[r3 + 2]; }
+  if (srow) { const float *n = T.c_nrm[nc + lane - nrc]; er[0] = n[0]; er[1] = n[1]; er[2] = n[2]; }
+  if (lane < nc) {  // a floor contact: as floor_forces, the adhesion pull shared with the body's fly-fly contacts
+    const int g = T.c_geom[lane];
+    const float dist = T.c_dist[lane], incl = X.f_margin[g] - X.f_gap[g];
+    float si_[5];
+#pragma unroll
+    for (int q2 = 0; q2 < 5; q2++) si_[q2] = X.f_solimp[q2];
+    const float imp = impedance(si_, fabsf(dist - incl));
+    const float R0 = fmaxf(1e-15f, (1.f - imp) * X.f_invw[g] * frcp(imp));
+    T.c_D[lane] = T.c_excl[lane] ? 0.f : frcp(R0);
+    T.c_mu[lane] = X.f_fric[g];
+    const float B = X.f_B[g], K = X.f_K[g];
+    T.r_y0[3 * lane] = B * wf::dot3<float>(&fr[0], T.c_vel[lane]) + K * imp * (dist - incl);
+    T.r_y0[3 * lane + 1] = B * wf::dot3<float>(&fr[3], T.c_vel[lane]);
+    T.r_y0[3 * lane + 2] = B * wf::dot3<float>(&fr[6], T.c_vel[lane]);
+    const int adh = X.f_adh[g];
+    T.c_w[lane] = adh >= 0 ? -T.frc[adh] / (float)contacts_of(T.c_link[lane]) : 0.f;
+  } else if (lane < ncs) {  // a fly-fly contact: D and -aref are the collision pass's; the pull of both bodies' adhesion actuators
+    const int ri = nrc + lane - nc, lp_ = T.c_link[lane], ln_ = T.c_link1[lane];
+    T.r_y0[ri] = T.c_vel[lane][0]; T.r_D[ri] = T.c_D[lane]; T.r_sgn[ri] = 0.f; T.r_dof[ri] = 0;
+    float w = 0.f;
+    const int ap = M.l_adh[lp_], an = ln_ != 255 ? M.l_adh[ln_] : -1;
+    if (ap >= 0) w -= T.frc[ap] / (float)contacts_of(lp_);
+    if (an >= 0) w -= T.frc[an] / (float)contacts_of(ln_);
+    T.c_w[lane] = w;
+  }
+  if (lane < RMAX) T.r_lam[lane] = 0.f;  // no warm start: a substep's result depends on its state alone
+  if (crow) T.r_blk[lane] = T.c_blk[lane / 3];
+  if (srow) T.r_blk[lane] = T.c_blk[nc + lane - nrc];
+  for (int k = lane; k < NBLK * KCOL; k += 64) (&T.rowof[0][0])[k] = 255;
+  DM_SYNC();
+  // ---- adhesion into the smooth forces of the hinges and of the root (a fly-fly row has no entry on the root)
+  {
+    float fa[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    for (int k = 0; k < nc; k++) {
+      float jr[6];
+      wf::row_root<float>(T.c_pos[k], &fr[0], jr);
+#pragma unroll
+      for (int a = 0; a < 6; a++) fa[a] += jr[a] * T.c_w[k];
+    }
+    if (lane == 0) {
+#pragma unroll
+      for (int a = 0; a < 6; a++) T.rootf[a] = fa[a];
+    }
+  }
+#pragma unroll
+  for (int s = 0; s < 3; s++)
+    if (slot_on(c, s)) qs[s] += floor_gather<true>(T, M, fr, nc, opq(c.sdof[s]), T.c_w) + self_gather(T, M, nc, ns, opq(c.sdof[s]), &T.c_w[nc]);
+  }
+  // ---- columns: a row's column is its rank among the rows of its block; a fly-fly row whose chains sit in two blocks takes a column
+  //      in each (ball_env.hip).  More than KCOL rows in a block: flagged, the rows without a column are switched off for this substep
+  const int myb = row ? (int)T.r_blk[lane] : -1;
+  int myb2 = -1;
+  if (srow) { const int b1 = T.c_blk1[nc + lane - nrc]; if (b1 != 255 && b1 != myb) myb2 = b1; }
+  int ncol, mycol2 = 0;
+  {
+    int mycol = 0;
+    for (int b = 0; b < NBLK; b++) {
+      const unsigned long long mb = __ballot(myb == b || myb2 == b);
+      if (myb == b) mycol = __popcll(mb & ((1ull << lane) - 1ull));
+      if (myb2 == b) mycol2 = __popcll(mb & ((1ull << lane) - 1ull));
+    }
+    if (row) {
+      T.r_col[lane] = (unsigned char)mycol;
+      if (mycol < KCOL) T.rowof[myb][mycol] = (unsigned char)lane;
+      if (myb2 >= 0 && mycol2 < KCOL) T.rowof[myb2][mycol2] = (unsigned char)lane;
+      if (myb2 < 0) mycol2 = mycol;
+      if (srow) T.c_col1[nc + lane - nrc] = (unsigned char)mycol2;
+      mycol = max(mycol, mycol2) + 1;
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) mycol = max(mycol, __shfl_xor(mycol, off));
+    ncol = min(mycol, KCOL);
+    if (mycol > KCOL) {
+      c.overflow |= 4;
+      DM_SYNC();
+      if (row && ((int)T.r_col[lane] >= KCOL || mycol2 >= KCOL)) { if (crow) T.c_excl[lane / 3] = 1; else T.r_D[lane] = 0.f; }
+      DM_SYNC();
+      if (lane < nc && T.c_excl[lane]) T.c_D[lane] = 0.f;
+    }
+  }
+  DM_SYNC();
+  const int mycol = row ? (int)T.r_col[lane] : 0;
+  // this row: its contact, the two links whose chains it spans (a floor row: one), a limit row's hinge
+  const int ck = crow ? lane / 3 : (srow ? nc + lane - nrc : 0);
+  const int lpos = jrow ? (int)T.c_link[ck] : 0, lneg = jrow ? (int)T.c_link1[ck] : 255;
+  const int npos = jrow ? M.l_nchain[lpos] : 0, nneg = lneg != 255 ? M.l_nchain[lneg] : 0;
+  const int rdof = (row && !jrow) ? (int)T.r_dof[lane] : 0;
+  const float sg = (row && !jrow) ? T.r_sgn[lane] : 0.f;
+  // fn(hinge, J entry, 0 = geom2's chain / 1 = geom1's): a hinge on both chains is visited twice and the entries cancel
+  auto each = [&](auto &&fn) {
+    for (int p = 0; p < npos; p++) { const int f = M.l_chain[p][lpos]; fn(f, fj_row(T, er, ck, f), 0); }
+    for (int p = 0; p < nneg; p++) { const int f = M.l_chain[p][lneg]; fn(f, -fj_row(T, er, ck, f), 1); }
+  };
+  // ---- z_m = M_jj^-1 f_j and Y_m = M_jj^-1 M_jr through M's own factor; a row lane keeps J_j z_m and J_j Y_m of its row
+  S6 ym[3];
+  float zm[3], jz = 0.f, jy[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+  for (int s = 0; s < 3; s++) if (slot_on(c, s)) { const float *m6 = T.F[opq(c.sdof[s])]; T.X4[opq(c.sdof[s])] = make_float4(qs[s], m6[0], m6[1], m6[2]); }
+  DM_SYNC();
+  solve4(c, T.Lm, T.dinv_m);
+#pragma unroll
+  for (int s = 0; s < 3; s++) {
+    const float4 x = slot_on(c, s) ? T.X4[opq(c.sdof[s])] : make_float4(0.f, 0.f, 0.f, 0.f);
+    zm[s] = x.x; ym[s].a0 = x.y; ym[s].a1 = x.z; ym[s].a2 = x.w;
+  }
+  if (jrow) each([&](int f, float jv, int) { const float4 x = T.X4[f]; jz += jv * x.x; jy[0] += jv * x.y; jy[1] += jv * x.z; jy[2] += jv * x.w; });
+  else if (row) { const float4 x = T.X4[rdof]; jz = sg * x.x; jy[0] = sg * x.y; jy[1] = sg * x.z; jy[2] = sg * x.w; }
+  DM_SYNC();
+#pragma unroll
+  for (int s = 0; s < 3; s++) if (slot_on(c, s)) { const float *m6 = T.F[opq(c.sdof[s])]; T.X4[opq(c.sdof[s])] = make_float4(m6[3], m6[4], m6[5], 0.f); }
+  DM_SYNC();
+  solve4(c, T.Lm, T.dinv_m);
+#pragma unroll
+  for (int s = 0; s < 3; s++) {
+    const float4 x = slot_on(c, s) ? T.X4[opq(c.sdof[s])] : make_float4(0.f, 0.f, 0.f, 0.f);
+    ym[s].l0 = x.x; ym[s].l1 = x.y; ym[s].l2 = x.z;
+  }
+  if (jrow) each([&](int f, float jv, int) { const float4 x = T.X4[f]; jy[3] += jv * x.x; jy[4] += jv * x.y; jy[5] += jv * x.z; });
+  else if (row) { const float4 x = T.X4[rdof]; jy[3] = sg * x.x; jy[4] = sg * x.y; jy[5] = sg * x.z; }
+  DM_SYNC();
+  // ---- S_m = L L', x_r = S_m^-1 (b_r + adhesion - M_rj z_m); qfrc_smooth . qacc_smooth for the solver's stopping test
+  float Sm[6][6], br[6], id[6], xr[6];
+  {
+    S6 m6[3];
+#pragma unroll
+    for (int s = 0; s < 3; s++) m6[s] = slot_on(c, s) ? ld6(T.F[opq(c.sdof[s])]) : zero6();
+    schur(c, m6, ym, zm, Sm, br);
+  }
+#pragma unroll
+  for (int k = 0; k < 6; k++) br[k] += T.rootf[k];
+  chol6(Sm, id);
+  chol6_forward(Sm, id, br, xr);
+  chol6_backward(Sm, id, xr);
+  float sq = 0.f;
+#pragma unroll
+  for (int s = 0; s < 3; s++) {
+    if (slot_on(c, s)) {
+      float a = zm[s];
+#pragma unroll
+      for (int k = 0; k < 6; k++) a -= comp(ym[s], k) * xr[k];
+      sq += qs[s] * a;
+    }
+  }
+  float scale2 = wave_sum(sq);
+#pragma unroll
+  for (int k = 0; k < 6; k++) scale2 += br[k] * xr[k];
+  scale2 *= kFloorScale;
+  // ---- y0 = J qacc_smooth - aref: the hinges' share J_j (z_m - Y_m x_r); a floor row adds the root's share, a fly-fly row has none
+  if (row) {
+    float y = wsf::row_y0<float>(jz, jy, xr, 0.f);
+    if (crow) {
+      const M3 Rr = q2m(c.rq);
+      const V3 g3 = (c.flags & BF_NO_GRAVITY) ? V3{0.f, 0.f, 0.f} : mtv(Rr, V3{0.f, 0.f, M.gz});
+      const float wb[3] = {c.V0.a0, c.V0.a1, c.V0.a2}, vb[3] = {c.V0.l0, c.V0.l1, c.V0.l2}, gb[3] = {g3.x, g3.y, g3.z};
+      float jr[6];
+      wf::row_root<float>(T.c_pos[ck], er, jr);
+      y += wf::root_y0<float>(jr, xr, wb, vb, gb);
+    }
+    T.r_y0[lane] += y;
+  }
+  // ---- the rank-6 part of G: u = L^-1 (J_r - J_j Y_m), G_ik = u_i . u_k
+  const int gtri = lane * (lane + 1) / 2;  // G is symmetric: row `lane` keeps its columns r2 <= lane
+  {
+    float u[6], jr[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    if (crow) wf::row_root<float>(T.c_pos[ck], er, jr);
+    wf::rank6_factor<float>(Sm, id, jr, jy, u);
+    for (int r2 = 0; r2 < R; r2++) {
+      float gv = 0.f;
+#pragma unroll
+      for (int k = 0; k < 6; k++) gv += u[k] * rl_f(u[k], r2);
+      if (row && r2 <= lane) T.G[gtri + r2] = gv;
+    }
+  }
+  // ---- the block part J_j M_jj^-1 J_j': four columns per block solve, rows of different blocks sharing a column
+  auto g_add = [&](const float4 &acc, const int b, const int cb) {
+#pragma unroll
+    for (int q2 = 0; q2 < 4; q2++) {
+      const float av = q2 == 0 ? acc.x : (q2 == 1 ? acc.y : (q2 == 2 ? acc.z : acc.w));
+      const int r2 = cb + q2 < KCOL ? (int)T.rowof[b][cb + q2] : 255;
+      if (r2 <= lane) T.G[gtri + r2] += av;  // (255 = no such row)
+    }
+  };
+#pragma unroll 1
+  for (int cb = 0; cb < ncol; cb += 4) {
+    for (int f = lane; f < ND; f += 64) T.X4[f] = make_float4(0.f, 0.f, 0.f, 0.f);
+    DM_SYNC();
+    if (jrow) {
+      each([&](int f, float jv, int half) {
+        const int col = (half == 0 ? mycol : mycol2) - cb;
+        if (col >= 0 && col < 4) (&T.X4[f].x)[col] += jv;  // (its own lane alone writes this column of this block)
+      });
+    } else if (row) {
+      const int col = mycol - cb;
+      if (col >= 0 && col < 4) (&T.X4[rdof].x)[col] = sg;
+    }
+    DM_SYNC();
+    solve4(c, T.Lm, T.dinv_m);
+    if (jrow) {
+      float4 a0 = make_float4(0.f, 0.f, 0.f, 0.f), a1 = make_float4(0.f, 0.f, 0.f, 0.f);
+      each([&](int f, float jv, int half) {
+        const float4 y = T.X4[f];
+        if (half == 0) { a0.x += jv * y.x; a0.y += jv * y.y; a0.z += jv * y.z; a0.w += jv * y.w; }
+        else { a1.x += jv * y.x; a1.y += jv * y.y; a1.z += jv * y.z; a1.w += jv * y.w; }
+      });
+      g_add(a0, myb, cb);
+      if (nneg) g_add(a1, myb2 >= 0 ? myb2 : myb, cb);
+    } else if (row) {
+      const float4 y = T.X4[rdof];
+      g_add(make_float4(sg * y.x, sg * y.y, sg * y.z, sg * y.w), myb, cb);
+    }
+    DM_SYNC();
+  }
+  // ---- solve: floor cone blocks first, the scalar rows (fly-fly, limits) after them, the model's noslip sweeps (with the revert
+  //      test of ConeRowsResidual: on the fly's own contacts ConeRows' test flipped by rounding, row_newton.hpp)
+  int nact = 0;
+  for (int k = 0; k < nc; k++) nact += T.c_excl[k] ? 0 : 1;
+  const int nslip = (nact > 0 && !(c.flags & BF_NO_NOSLIP)) ? M.noslip_iterations : 0;
+  ModelPtr mp_ = (ModelPtr)c.M;
+  int iters;
+  if (R <= 12) iters = row_newton<12, ConeRowsResidual>(c.T, mp_, lane, R, nrc, scale2, nslip, 0);
+  else if (R <= 18) iters = row_newton<18, ConeRowsResidual>(c.T, mp_, lane, R, nrc, scale2, nslip, 0);
+  else if (R <= 24) iters = row_newton<24, ConeRowsResidual>(c.T, mp_, lane, R, nrc, scale2, nslip, 0);
+  else if (R <= 32) iters = row_newton<32, ConeRowsResidual>(c.T, mp_, lane, R, nrc, scale2, nslip, 0);
+  else iters = row_newton<RMAX, ConeRowsResidual>(c.T, mp_, lane, R, nrc, scale2, nslip, 0);
+  // ---- qfrc_constraint: J_j' f on the hinges, J_r' f (floor rows alone, and the adhesion pull) on the root
+  float fr[9];
+  floor_frame(c, fr);
+  {
+    float fsum = 0.f, fa[6];
+#pragma unroll
+    for (int a = 0; a < 6; a++) fa[a] = T.rootf[a];
+    for (int k = 0; k < nc; k++) {
+      fsum += T.r_f[3 * k];
+#pragma unroll
+      for (int r = 0; r < 3; r++) {
+        float j6[6];
+        wf::row_root<float>(T.c_pos[k], &fr[3 * r], j6);
+        const float f = T.r_f[3 * k + r];
+#pragma unroll
+        for (int a = 0; a < 6; a++) fa[a] += j6[a] * f;
+      }
+    }
+    DM_SYNC();
+    if (lane == 0) {
+#pragma unroll
+      for (int a = 0; a < 6; a++) T.rootf[a] = fa[a];
+      T.rootf[6] = fsum;
+    }
+  }
+#pragma unroll
+  for (int s = 0; s < 3; s++) {
+    if (slot_on(c, s)) qs[s] += floor_gather<false>(T, M, fr, nc, opq(c.sdof[s]), T.r_f) + self_gather(T, M, nc, ns, opq(c.sdof[s]), &T.r_f[nrc]);
+    if (lrow[s] >= 0) qs[s] += lsgn[s] * T.r_f[lrow[s]];
+  }
+  DM_SYNC();
+  return iters;
+}
+
 // ------------------------------------------------------------------------------------------------ force and touch
 // mj: mj_rnePostConstraint + mj_sensorAcc for the force and touch sensors, on the free root (walk_sense.hpp): called from the
 // acceleration stage with this substep's qacc (the hinges' in T.X4[.].x; `xr`: the root rows of the arrowhead solve, gravity not yet
@@ -893,6 +1479,7 @@ __device__ __forceinline__ void stage2(C &c, float act_reg, float ctrl_reg, floa
   auto &T = *c.T;
   constexpr bool FLOOR = is_floor_tile<std::remove_reference_t<decltype(T)>>::value;  // the floor kernel: everything it adds is under this switch
   constexpr bool SENSE = is_sense_tile<std::remove_reference_t<decltype(T)>>::value;  // the episode kernel on the floor: likewise
+  constexpr bool SELF = is_self_tile<std::remove_reference_t<decltype(T)>>::value;    // the kernel with the fly's own contacts: likewise
   const BallModel FFE_GLOBAL &M = model(c);
   const int lane = c.lane;
   const float h = M.h;
@@ -949,6 +1536,7 @@ __device__ __forceinline__ void stage2(C &c, float act_reg, float ctrl_reg, floa
       R = 3 * c.fl.nc;
       if (lane < 8) T.rootf[lane] = 0.f;
     }
+    if constexpr (SELF) R += c.fl.ns;  // ... then one per fly-fly contact
 #pragma unroll
     for (int s = 0; s < 3; s++) {
       float lD = 0.f, laref = 0.f;
@@ -980,10 +1568,12 @@ __device__ __forceinline__ void stage2(C &c, float act_reg, float ctrl_reg, floa
     if (R > RMAX) { R = RMAX; c.overflow |= 2; }
     nlim_out = R;
     if constexpr (FLOOR) nlim_out = R - 3 * c.fl.nc;
+    if constexpr (SELF) nlim_out -= c.fl.ns;
     iters_out = 0;
     if (R > 0) {  // wave-uniform: a substep without a row pays the ballots only
       DM_SYNC();
-      if constexpr (FLOOR) iters_out = floor_forces(c, R, lrow, lsgn, qs);  // (limit rows alone too: the cone solver with no cone block)
+      if constexpr (SELF) iters_out = self_forces(c, R, lrow, lsgn, qs);
+      else if constexpr (FLOOR) iters_out = floor_forces(c, R, lrow, lsgn, qs);  // (limit rows alone too: the cone solver with no cone block)
       else iters_out = limit_forces(c, R, lrow, lsgn, mrj, qs);
       // (read again rather than kept in registers across the solver's call: 18 fewer live values there)
 #pragma unroll
@@ -1247,6 +1837,19 @@ __device__ __forceinline__ void walk_substeps(Tile &T, const WalkModel *__restri
       float md = 0.f;
       for (int k = 0; k < c.fl.nc; k++) md = k == 0 ? T.c_dist[0] : fminf(md, T.c_dist[k]);
       c.fl.mind = md;
+      if constexpr (is_self_tile<Tile>::value) {
+        // ---- the fly's own contacts behind the floor's: sphere / capsule pairs, then the pairs with an ellipsoid or a cylinder.
+        //      Every substep runs both passes (the mouth parts touch in every pose: there is no "nothing in reach" shortcut).
+        if (lane < 6) T.sv0[lane] = comp(c.V0, lane);  // (visible after the first pass's own barrier, as the three stores below)
+        if (lane < c.fl.nc) { T.c_link1[lane] = 255; T.c_blk1[lane] = 255; T.c_amask1[lane] = 0; }  // a floor slot: one chain
+        const int sc = __builtin_amdgcn_readfirstlane(self_prim_collide(c.T, (ModelPtr)c.M, c.X, lane, c.fl.nc));
+        const int cc = __builtin_amdgcn_readfirstlane(self_convex_collide(c.T, (ModelPtr)c.M, lane, c.fl.nc + (sc & 0xff)));
+        c.fl.ns = (sc & 0xff) + (cc & 0xff);
+        if (((sc | cc) >> 8) & 1) c.overflow |= 1;
+        if ((cc >> 9) & 1) c.overflow |= 8;
+        for (int k = c.fl.nc; k < c.fl.nc + c.fl.ns; k++) md = k == 0 ? T.c_dist[0] : fminf(md, T.c_dist[k]);
+        c.fl.mind = md;
+      }
     }
     float act_new;
     if constexpr (EP) {
@@ -1277,6 +1880,7 @@ __device__ __forceinline__ void walk_substeps(Tile &T, const WalkModel *__restri
     S.pos[0] = c.pos[0]; S.pos[1] = c.pos[1]; S.pos[2] = c.pos[2];
     if constexpr (LIMITS) { S.nlim = nlim; S.iters = iters; S.step_bits = c.overflow; }
     if constexpr (FLOOR && EP) ep.a->rec[env] = FloorRec{c.fl.nc, T.rootf[6], c.fl.mind, 0};
+    else if constexpr (is_self_tile<Tile>::value) ep.rec[env] = FloorRec{c.fl.nc + c.fl.ns, T.rootf[6], c.fl.mind, c.fl.ns};
     else if constexpr (FLOOR) ep.rec[env] = FloorRec{c.fl.nc, T.rootf[6], c.fl.mind, 0};
   }
   if constexpr (EP) {
@@ -1310,5 +1914,8 @@ __device__ __forceinline__ void walk_substeps(Tile &T, const WalkModel *__restri
 // hipGetLastError.
 void launch_imitation_floor_step(const WalkModel *model, int flags, WState *states, const ImitArgs *args, const float *action, float *obs, int batch,
                                  hipStream_t stream);
+// `nphys` substeps of bare physics with the floor and the fly's own contacts (walk_self_env.hip): launches `floor_self_step` on `stream`;
+// the caller checks hipGetLastError.
+void launch_floor_self_step(const WalkModel *model, int flags, WState *states, const float *ctrl, FloorRec *rec, int batch, int nphys, hipStream_t stream);
 
 }  // namespace ffw

@@ -70,9 +70,16 @@ enum {
   /* ffe_create_walk_physics only: the floor plane against the fly's sphere and capsule geoms, on the bare-physics handle (the fourth
    * step kernel of csrc/walk_env.hip) or, with FFE_WALK_EPISODES and the task, under the environment (csrc/walk_floor_env.hip).  Accepted
    * only as FFE_NO_CONTACT | FFE_WALK_JOINT_LIMITS | FFE_WALK_FLOOR [| FFE_WALK_EPISODES] plus force switches, FFE_NO_NOSLIP and
-   * FFE_NO_ADHESION; on such a handle FFE_NO_CONTACT keeps meaning "the fly's own contacts are off" (they are not built).  An opt-in
-   * bit and provisional as the two above. */
-  FFE_WALK_FLOOR = 2048
+   * FFE_NO_ADHESION; on such a handle FFE_NO_CONTACT keeps meaning "the fly's own contacts are off" unless FFE_WALK_SELF switches them
+   * on.  An opt-in bit and provisional as the two above. */
+  FFE_WALK_FLOOR = 2048,
+  /* ffe_create_walk_physics only: the fly's own contacts (its 48 sphere / capsule geoms against each other, and every candidate pair
+   * with an ellipsoid or a cylinder on one side) on the bare-physics floor handle (csrc/walk_self_env.hip).  Accepted only as
+   * FFE_NO_CONTACT | FFE_WALK_JOINT_LIMITS | FFE_WALK_FLOOR | FFE_WALK_SELF plus force switches, FFE_NO_NOSLIP and FFE_NO_ADHESION;
+   * FFE_NO_CONTACT is then only the marker every accepted set of that create call carries (plain "contacts on" stays a pinned refusal
+   * while the floor against ellipsoids and cylinders is missing): the contacts that are built are all on.  Not yet carried by the
+   * environment: with FFE_WALK_EPISODES the bit is refused.  An opt-in bit and provisional as the three above. */
+  FFE_WALK_SELF = 4096
 };
 
 typedef struct ffe_walk_task_s ffe_walk_task; /* the walk_imitation task layer's inputs, defined with ffe_walktask_create below */
@@ -155,8 +162,8 @@ int ffe_create_walk_on_ball(const void *model_blob, size_t blob_size, const ffe_
  * of that, the walk_imitation environment itself with the floor off: sensors, observation row, reward, termination and the episode
  * protocol on the device, a fly that falls freely (or floats with FFE_NO_GRAVITY).  FFE_WALK_FLOOR adds the floor plane against the
  * fly's 48 sphere / capsule geoms (elliptic cones, noslip, adhesion) to the bare-physics handle or, together with FFE_WALK_EPISODES,
- * to the environment, whose force and touch columns are then live; the fly's own contacts and the floor against ellipsoids and
- * cylinders are not built yet. */
+ * to the environment, whose force and touch columns are then live; FFE_WALK_SELF adds the fly's own contacts to the bare-physics floor
+ * handle.  The fly's own contacts under the environment and the floor against ellipsoids and cylinders are not built yet. */
 typedef struct {
   /* FFE_NO_CONTACT and exactly one of FFE_NO_LIMIT (smooth dynamics alone) or FFE_WALK_JOINT_LIMITS (joint limits on: up to 48 limit
    * rows per env and substep), plus any of the force switches FFE_NO_FLUID / _DAMPER / _SPRING / _GRAVITY / _ACTUATION; every other
@@ -165,10 +172,14 @@ typedef struct {
    * FFE_WALK_FLOOR is accepted only as FFE_NO_CONTACT | FFE_WALK_JOINT_LIMITS | FFE_WALK_FLOOR plus force switches, FFE_NO_NOSLIP and
    * FFE_NO_ADHESION (meaningful only with this bit), with or without FFE_WALK_EPISODES; every other set with it - with FFE_NO_LIMIT,
    * without FFE_WALK_JOINT_LIMITS, with FFE_WALK_EPISODES and a null `task` - is refused with a text naming FFE_WALK_FLOOR (and
-   * FFE_WALK_EPISODES when that bit was passed too).  The accepted sets:
+   * FFE_WALK_EPISODES when that bit was passed too).  FFE_WALK_SELF is accepted only as FFE_NO_CONTACT | FFE_WALK_JOINT_LIMITS |
+   * FFE_WALK_FLOOR | FFE_WALK_SELF plus the same switches; every other set with it - without FFE_WALK_FLOOR, with FFE_NO_LIMIT, with
+   * FFE_WALK_EPISODES (the environment does not carry the fly's own contacts yet) - is refused with a text naming FFE_WALK_SELF.  The
+   * accepted sets:
    *   FFE_NO_CONTACT | FFE_NO_LIMIT                                                   smooth dynamics
    *   FFE_NO_CONTACT | FFE_WALK_JOINT_LIMITS                                          + joint limits
    *   FFE_NO_CONTACT | FFE_WALK_JOINT_LIMITS | FFE_WALK_FLOOR                         + the floor plane (bare physics)
+   *   FFE_NO_CONTACT | FFE_WALK_JOINT_LIMITS | FFE_WALK_FLOOR | FFE_WALK_SELF         + the fly's own contacts (bare physics)
    *   FFE_NO_CONTACT | FFE_WALK_JOINT_LIMITS | FFE_WALK_EPISODES                      walk_imitation, floor off
    *   FFE_NO_CONTACT | FFE_WALK_JOINT_LIMITS | FFE_WALK_EPISODES | FFE_WALK_FLOOR     walk_imitation on the floor plane */
   int32_t physics_flags;
@@ -202,6 +213,13 @@ typedef struct {
  *                       off for that substep); bit value 2 counts contact and limit rows together (48)
  *   ffe_get_task_state  int 5 = floor contacts kept in the last substep, real 0 = the sum of their normal forces, real 1 = the
  *                       smallest contact distance (0 without a contact)
+ * A handle created with FFE_WALK_SELF reports what a floor handle reports, every column keeping its meaning, with these additions:
+ *   ffe_get_validity    column 0 bit value 1 = more contacts, floor and fly-fly together, than slots (16; the floor's keep the first
+ *                       slots, the deepest fly-fly ones were kept behind them); bit value 8 = a convex candidate pair was left out of a
+ *                       substep because one of its pair lists was full (192 pairs past the bounding spheres, 24 into the narrow phase)
+ *   ffe_get_task_state  int 5 = all contacts kept in the last substep, floor and fly-fly (a contact inside its margin but outside
+ *                       margin - gap is kept only where an adhesion actuator counts it), int 3 = the fly-fly contacts among them,
+ *                       real 0 = the sum of the floor contacts' normal forces as before, real 1 = the smallest distance over both kinds
  * A handle created with FFE_WALK_EPISODES is an environment (everything above still works on it): ffe_reset, ffe_reset_envs, ffe_step,
  * ffe_force_next_episode (the clip; the phase array is ignored), ffe_time_steps and ffe_time_kernel work as on a walk_on_ball handle,
  * and ffe_spec reports obs_dim 741 with the offsets of the row: accelerometer 3 | actuator_activation 59 | appendages_pos 21 |
