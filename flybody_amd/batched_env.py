@@ -28,7 +28,8 @@ FFE_WALK_JOINT_LIMITS = 512  # ffe_create_walk_physics only: joint limits on (pr
 FFE_WALK_EPISODES = 1024  # ffe_create_walk_physics only: the walk_imitation environment with the floor off (provisional opt-in)
 FFE_WALK_FLOOR = 2048  # ffe_create_walk_physics only: the floor plane against the fly's sphere / capsule geoms (opt-in; bare physics, or
 #                        with FFE_WALK_EPISODES the walk_imitation environment on the floor)
-FFE_WALK_SELF = 4096  # ffe_create_walk_physics only: the fly's own contacts on the bare-physics floor handle (provisional opt-in)
+FFE_WALK_SELF = 4096  # ffe_create_walk_physics only: the fly's own contacts on the floor handle, bare physics or environment (provisional opt-in)
+FFE_WALK_SELF_EPISODES = 8192  # ffe_create_walk_physics only: next to FFE_WALK_SELF under the environment (the three bits alone stay refused)
 
 
 # `env.validity()`: four int32 [B] views of one [B, 4] device buffer (include/flybody_env.h, ffe_get_validity)
@@ -405,6 +406,14 @@ class BatchedWalkEnv(BatchedFlyEnv):
     last substep, reals 0 / 1 the sum of their normal forces and the smallest distance; `validity()`'s step_bits carry the floor's
     overflow bits 1 / 2 / 4 next to the limit bit, sticky per episode in episode_bits.
 
+    `self_contacts=True` (keyword-only; it needs `floor_contacts=True`) adds FFE_WALK_SELF | FFE_WALK_SELF_EPISODES: the fly's own
+    contacts as in `BatchedWalkPhysics(floor_contacts=True, self_contacts=True)` - its 48 sphere / capsule geoms against each other and
+    every candidate pair with an ellipsoid or a cylinder on one side, frictionless normal rows between the floor's cone blocks and the
+    joint limits - with their forces in the force and touch columns (a fly-fly contact pushes both of its links).  The env can then be
+    compared with the float64 oracle on the shipped model.  int 5 counts both kinds of contact, reals[:, 2] the fly-fly ones among them
+    (int 3 is needs_reset on an env), real 1 is taken over both kinds, and step_bits bit value 8 says that a convex candidate pair was
+    left out because a pair list of the substep was full.  The plane against ellipsoids and cylinders stays off.
+
     `refs`: a `tasks.walking.WalkRefSet`; `view`: the `WalkModelView` that names the tracked joints and sites (None: the default
     one).  `get_state` / `set_state` / `get_act` / `set_act` / `physics_step` are `BatchedWalkPhysics`'s."""
 
@@ -413,8 +422,11 @@ class BatchedWalkEnv(BatchedFlyEnv):
     def __init__(self, refs, view=None, *, batch_size: int, device: int = 0, seed: int = 0, env_id_base: int = 0, future_steps: int = 64,
                  time_limit: float = 10.0, terminal_com_dist: float = 0.3, control_timestep: float = 2e-3, pad_first_obs: bool = False,
                  physics_flags: int = 0, canonical_actions: bool = False, clip_actions: bool = False, double_buffer: bool = False,
-                 inference_mode: bool = False, blob_path: str = WALK_BLOB, floor_contacts: bool = False):
+                 inference_mode: bool = False, blob_path: str = WALK_BLOB, floor_contacts: bool = False, self_contacts: bool = False):
         import json
+
+        if self_contacts and not floor_contacts:
+            raise ValueError("BatchedWalkEnv: self_contacts=True needs floor_contacts=True (the fly's own contacts are built on the floor env)")
 
         from .model.blob import read_blob
         from .tasks.walk_tracker import make_task
@@ -435,11 +447,14 @@ class BatchedWalkEnv(BatchedFlyEnv):
         self.floor_contacts = bool(floor_contacts)
         if self.floor_contacts:
             force_switches |= int(physics_flags) & (128 | 256)  # FFE_NO_NOSLIP / FFE_NO_ADHESION
-            if int(physics_flags) & ~(force_switches | FFE_NO_CONTACT | FFE_WALK_JOINT_LIMITS | FFE_WALK_EPISODES | FFE_WALK_FLOOR):
+            if int(physics_flags) & ~(force_switches | FFE_NO_CONTACT | FFE_WALK_JOINT_LIMITS | FFE_WALK_EPISODES | FFE_WALK_FLOOR
+                                      | (FFE_WALK_SELF | FFE_WALK_SELF_EPISODES if self_contacts else 0)):
                 raise ValueError("BatchedWalkEnv(floor_contacts=True): physics_flags takes the force switches, FFE_NO_NOSLIP and FFE_NO_ADHESION only")
         elif int(physics_flags) & ~(force_switches | FFE_NO_CONTACT | FFE_WALK_JOINT_LIMITS | FFE_WALK_EPISODES):
             raise ValueError("BatchedWalkEnv: physics_flags takes the force switches only (floor contacts are not built; joint limits are on)")
-        self.physics_flags = force_switches | FFE_NO_CONTACT | FFE_WALK_JOINT_LIMITS | FFE_WALK_EPISODES | (FFE_WALK_FLOOR if self.floor_contacts else 0)
+        self.self_contacts = bool(self_contacts)
+        self.physics_flags = (force_switches | FFE_NO_CONTACT | FFE_WALK_JOINT_LIMITS | FFE_WALK_EPISODES | (FFE_WALK_FLOOR if self.floor_contacts else 0)
+                              | (FFE_WALK_SELF | FFE_WALK_SELF_EPISODES if self.self_contacts else 0))
         task = _capi.WalkPhysicsTask(physics_flags=self.physics_flags, task=C.pointer(wtask), seed=int(seed), env_id_base=int(env_id_base),
                                      time_limit_steps=time_limit_control_steps(time_limit, h_phys, nsub), pad_first_obs=int(pad_first_obs),
                                      canonical_actions=int(canonical_actions), clip_actions=int(clip_actions))

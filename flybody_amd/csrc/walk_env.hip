@@ -202,7 +202,9 @@ __global__ void episode_init_kernel(EpState *eps, int batch) {
 }
 // episode handle: task state {clip, step counter, episode (low 32 bits), needs_reset, limit rows of the last substep, 0, solver
 // iterations of the last substep, overflow bits of the last launch}, reals zero; validity {step_bits, episode_flagged_steps,
-// episode_bits, episode_steps}.  On the floor (`rec` not null) int 5 and reals 0 / 1 are the floor handle's.
+// episode_bits, episode_steps}.  On the floor (`rec` not null) int 5 and reals 0 / 1 are the floor handle's.  With FFE_WALK_SELF int 5
+// counts the floor and the fly-fly contacts kept, real 1 is taken over both kinds, and real 2 is the fly-fly count (int 3, where the
+// bare-physics handle reports it, is needs_reset here; real 2 is zero on every other handle).
 __global__ void episode_report_kernel(const EpState *eps, const WState *states, const FloorRec *rec, int *ints, double *reals, int *info, int batch) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= batch) return;
@@ -211,7 +213,7 @@ __global__ void episode_report_kernel(const EpState *eps, const WState *states, 
   if (ints) {
     int *o = ints + (size_t)i * 8;
     o[0] = e.clip; o[1] = e.step; o[2] = (int)(unsigned)e.episode; o[3] = e.needs_reset; o[4] = S.nlim; o[5] = rec ? rec[i].ncon : 0; o[6] = S.iters; o[7] = S.step_bits;
-    for (int k = 0; k < 8; k++) reals[(size_t)i * 8 + k] = !rec ? 0.0 : (k == 0 ? (double)rec[i].fsum : (k == 1 ? (double)rec[i].mind : 0.0));
+    for (int k = 0; k < 8; k++) reals[(size_t)i * 8 + k] = !rec ? 0.0 : (k == 0 ? (double)rec[i].fsum : (k == 1 ? (double)rec[i].mind : (k == 2 ? (double)rec[i].nself : 0.0)));
   }
   if (info) *reinterpret_cast<int4 *>(info + (size_t)i * 4) = make_int4(S.step_bits, e.ep_flagged, e.ep_bits, e.step);
 }
@@ -288,13 +290,15 @@ __global__ void walk_act_kernel(WState *states, double *act, int batch, int set)
 // ================================================================================================ host side
 // Bare physics (reset, step, forced episodes and the timers are refused) or, created with FFE_WALK_EPISODES, the walk_imitation
 // environment with the floor off or, with FFE_WALK_FLOOR too, on the floor (step 4c: the third of the five
-// launches is then `imitation_floor_step` of walk_floor_env.hip).
+// launches is then `imitation_floor_step` of walk_floor_env.hip; step 4d, with FFE_WALK_SELF on top: `imitation_self_step` of
+// walk_imit_self_env.hip).
 struct WalkEnv final : ffe::EnvBackend {
   int flags = 0;
   bool limits = false;    // FFE_WALK_JOINT_LIMITS: walk_limits_kernel steps this handle
   bool episodes = false;  // FFE_WALK_EPISODES: ffe_step / ffe_reset / ... work, imitation_step_kernel steps them
   bool floor = false;     // FFE_WALK_FLOOR: floor_step steps this handle (with `episodes`: imitation_floor_step)
-  bool self = false;      // FFE_WALK_SELF (with `floor`, without `episodes`): floor_self_step of walk_self_env.hip steps this handle
+  bool self = false;      // FFE_WALK_SELF (with `floor`): floor_self_step of walk_self_env.hip steps this handle (with `episodes`:
+                          // imitation_self_step of walk_imit_self_env.hip)
   FloorRec *rec = nullptr;  // floor handle only: contacts, normal-force sum and smallest distance of the last substep
   WalkHost host;
   ffe::DeviceBuffers mem{"ffe_create_walk_physics"};  // everything below lives here
@@ -362,7 +366,8 @@ struct WalkEnv final : ffe::EnvBackend {
     task_ok(ffe_walktask_reference_pose(task, clip, zero, batch, const_cast<double *>(args.pose), nullptr, stream), "walk_imitation");
     const ImitArgs &a = args;
     tm.start(s);
-    if (floor) launch_imitation_floor_step(model_dev, flags, states, args_dev, act, obs, batch, s);
+    if (self) launch_imitation_self_step(model_dev, flags, states, args_dev, act, obs, batch, s);
+    else if (floor) launch_imitation_floor_step(model_dev, flags, states, args_dev, act, obs, batch, s);
     else hipLaunchKernelGGL(imitation_step_kernel, dim3(batch), dim3(64), 0, s, model_dev, flags, states, args_dev, act, obs, batch);
     HIP_OK(hipGetLastError());
     tm.stop(s);
@@ -488,17 +493,25 @@ std::unique_ptr<ffe::EnvBackend> walk_create(const void *blob, size_t blob_size,
   if (!blob || batch <= 0) throw std::runtime_error("ffe_create_walk_physics: bad arguments");
   const bool limits = (physics_flags & BF_WALK_JOINT_LIMITS) != 0, no_limit = (physics_flags & BF_NO_LIMIT) != 0;
   const bool episodes = (physics_flags & BF_WALK_EPISODES) != 0, floor = (physics_flags & BF_WALK_FLOOR) != 0;
-  const bool self = (physics_flags & BF_WALK_SELF) != 0;
-  if (self) {
+  const bool self = (physics_flags & BF_WALK_SELF) != 0, self_env = (physics_flags & BF_WALK_SELF_EPISODES) != 0;
+  if (self || self_env) {
     const int switches = BF_NO_FLUID | BF_NO_DAMPER | BF_NO_SPRING | BF_NO_GRAVITY | BF_NO_ACTUATION | BF_NO_NOSLIP | BF_NO_ADHESION;
-    if (episodes)
-      throw std::runtime_error("ffe_create_walk_physics: FFE_WALK_SELF (the fly's own contacts) with FFE_WALK_EPISODES: the walk_imitation environment "
-                               "(FFE_WALK_EPISODES, with or without FFE_WALK_FLOOR) does not carry the fly's own contacts yet; the bit is accepted on "
-                               "the bare-physics floor handle only");
-    if ((physics_flags & ~switches) != (BF_NO_CONTACT | BF_WALK_JOINT_LIMITS | BF_WALK_FLOOR | BF_WALK_SELF))
+    if (episodes && !floor)
+      throw std::runtime_error("ffe_create_walk_physics: FFE_WALK_SELF (the fly's own contacts) with FFE_WALK_EPISODES needs FFE_WALK_FLOOR: the "
+                               "walk_imitation environment with the floor off does not carry the fly's own contacts");
+    if (episodes && !task.task)
+      throw std::runtime_error("ffe_create_walk_physics: FFE_WALK_SELF (the fly's own contacts) with FFE_WALK_EPISODES needs the task (a null "
+                               "ffe_walk_task pointer): a handle without one does not carry the episode protocol; without FFE_WALK_EPISODES the bit "
+                               "makes the bare-physics floor handle");
+    if ((physics_flags & ~(switches | BF_WALK_EPISODES | BF_WALK_SELF_EPISODES)) != (BF_NO_CONTACT | BF_WALK_JOINT_LIMITS | BF_WALK_FLOOR | BF_WALK_SELF))
       throw std::runtime_error("ffe_create_walk_physics: FFE_WALK_SELF (the fly's own contacts on the bare-physics floor handle) is accepted only as "
                                "FFE_NO_CONTACT | FFE_WALK_JOINT_LIMITS | FFE_WALK_FLOOR | FFE_WALK_SELF plus the force switches, FFE_NO_NOSLIP and "
-                               "FFE_NO_ADHESION");
+                               "FFE_NO_ADHESION, and with FFE_WALK_EPISODES | FFE_WALK_SELF_EPISODES and the task on top of exactly that");
+    // FFE_WALK_EPISODES | FFE_WALK_FLOOR | FFE_WALK_SELF alone is a refusal the C ABI contract pins: the environment takes its own bit too
+    if (episodes != self_env)
+      throw std::runtime_error("ffe_create_walk_physics: FFE_WALK_SELF under the environment (FFE_WALK_EPISODES | FFE_WALK_FLOOR and the task) is asked "
+                               "for with FFE_WALK_SELF_EPISODES on top: the three bits without it are refused, and so is FFE_WALK_SELF_EPISODES "
+                               "without FFE_WALK_EPISODES | FFE_WALK_FLOOR | FFE_WALK_SELF");
   } else if (floor && episodes) {
     const int switches = BF_NO_FLUID | BF_NO_DAMPER | BF_NO_SPRING | BF_NO_GRAVITY | BF_NO_ACTUATION | BF_NO_NOSLIP | BF_NO_ADHESION;
     if ((physics_flags & ~switches) != (BF_NO_CONTACT | BF_WALK_JOINT_LIMITS | BF_WALK_EPISODES | BF_WALK_FLOOR))
@@ -529,7 +542,7 @@ std::unique_ptr<ffe::EnvBackend> walk_create(const void *blob, size_t blob_size,
   std::unique_ptr<WalkEnv> e(new WalkEnv());  // frees the device allocations made so far if a later step throws
   Blob b(blob, blob_size);
   e->host = build_walk_model(b);
-  e->device = device; e->batch = batch; e->flags = physics_flags & ~BF_WALK_EPISODES; e->limits = limits; e->episodes = episodes; e->floor = floor; e->self = self;
+  e->device = device; e->batch = batch; e->flags = physics_flags & ~(BF_WALK_EPISODES | BF_WALK_SELF_EPISODES); e->limits = limits; e->episodes = episodes; e->floor = floor; e->self = self;
   if (self) build_walk_self(b, e->host);  // (before the model goes to the device)
   if (floor && !e->host.m.x.f_ok)
     throw std::runtime_error("ffe_create_walk_physics: FFE_WALK_FLOOR: the floor's contacts are expected to be condim 3 with one solimp");

@@ -1,8 +1,8 @@
 // walk_substeps.hpp - the device code of the free-root substep that more than one translation unit compiles: the state record, the LDS
 // tiles, the wave's context, stage 1 / stage 2 with the limit and floor constraint blocks, the substep loop and the state export.
-// walk_env.hip (the four kernels of bare physics and of the floor-off environment), walk_floor_env.hip (the environment on the floor) and
-// walk_self_env.hip (bare physics with the fly's own contacts) include it; what the code does is described at the head of walk_env.hip
-// and where each part starts.
+// walk_env.hip (the four kernels of bare physics and of the floor-off environment), walk_floor_env.hip (the environment on the floor),
+// walk_self_env.hip (bare physics with the fly's own contacts) and walk_imit_self_env.hip (the environment on the floor with the fly's
+// own contacts) include it; what the code does is described at the head of walk_env.hip and where each part starts.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -17,6 +17,7 @@
 #include "walk_imu.hpp"
 #include "walk_floor.hpp"
 #include "walk_sense.hpp"
+#include "walk_self_sense.hpp"
 #include "walk_self.hpp"
 
 
@@ -41,6 +42,7 @@ constexpr int BF_WALK_JOINT_LIMITS = 512;  // FFE_WALK_JOINT_LIMITS: host side o
 constexpr int BF_WALK_EPISODES = 1024;     // FFE_WALK_EPISODES: host side only
 constexpr int BF_WALK_FLOOR = 2048;        // FFE_WALK_FLOOR: host side only (it selects the floor kernel)
 constexpr int BF_WALK_SELF = 4096;         // FFE_WALK_SELF: host side only (it selects the kernel with the fly's own contacts)
+constexpr int BF_WALK_SELF_EPISODES = 8192;  // FFE_WALK_SELF_EPISODES: host side only (FFE_WALK_SELF under the environment is asked for by it)
 constexpr int LCOL = 16;                  // solve columns per block of M: a block has at most NSTEP = 14 hinges, each with one limit row
 static_assert(NSTEP <= LCOL, "a block's limit rows must fit its columns");
 
@@ -196,6 +198,46 @@ struct is_self_tile<T, std::enable_if_t<T::kSelf>> : std::true_type {};
 struct SelfCtx : FloorCtx {
   int ns;          // fly-fly contacts kept in this substep: slots nc .. nc + ns - 1
 };
+
+// Tile of the episode kernel on the floor with the fly's own contacts (walk_imit_self_env.hip `imitation_self_step`; DESIGN.md section
+// 12 step 4d): a sense tile and a self tile at once.  WTileF + the sensor part of WTileS (432 B) + the self part of WTileX (304 B) would
+// be 20 608 B, 128 B over what 8 waves per CU leave, so the fly-fly normal has no array of its own here (`kPackedNormal`): a fly-fly slot
+// k uses c_vel[k][0] alone of its three c_vel floats (-aref of its one row) and never c_mu[k] (the solver reads c_mu of the floor's cone
+// blocks k < nc only), and a floor slot never had a stored normal (its normal is the plane's), so the normal of slot k lies in
+// c_vel[k][1], c_vel[k][2], c_mu[k] behind `self_nrm` / `self_put`.  That saves c_nrm's 192 B: 20 416 B.
+// Overlays, as in the two parents (asserted below where the tile cannot show it by itself):
+//   between stage 1 and stage 2   the link poses `lp` over the head of G; the primitive slots over X4[0 .. 2 NPG) and their radii over
+//                                 G[NL 14 .. NL 14 + NPG); the convex pass's geom centres and pair lists over X4.  All of it is dead when
+//                                 the collision passes have returned: stage 2 starts by staging Q / V over X4 and builds G afresh.
+//   after the solver's return     G is dead.  The hinges' right-hand side is parked at G[kSensePark .. kSensePark + 192) - the floats the
+//                                 radii used during the collision - while the qacc solve runs; the hinges' qacc stays in X4[.].x for the
+//                                 sensor pass, which exchanges its link values through `lp` (the head of G, below kSensePark).
+struct alignas(16) WTileSX : WTileF {
+  static constexpr bool kSense = true;
+  static constexpr bool kSelf = true;
+  static constexpr bool kPackedNormal = true;
+  float sens[36];
+  float fsq[6][4];
+  float sp[6][8];
+  unsigned short c_amask1[NC];
+  unsigned char c_link1[NC], c_blk1[NC], c_col1[NC];
+  float sv0[8];
+};
+static_assert(sizeof(WTileSX) == sizeof(WTileF) + 432 + 304 - sizeof(float[NC][3]), "the sensor part and the self part without c_nrm");
+static_assert(sizeof(WTileSX) <= 20480, "the tile must leave room for 8 waves per CU");
+static_assert(NL * 14 <= kSensePark && kSensePark + 3 * 64 <= RMAX * (RMAX + 1) / 2,
+              "the parked right-hand side lies behind the sensor pass's link exchange, inside G");
+static_assert(NPG <= 3 * 64, "the slot radii of the collision pass and the parked right-hand side share the same floats of G, one after the other");
+template <class T, class = void>
+struct is_packed_normal : std::false_type {};
+template <class T>
+struct is_packed_normal<T, std::enable_if_t<T::kPackedNormal>> : std::true_type {};
+// the normal (from geom1's link to geom2's) of fly-fly slot k
+template <class TileX>
+__device__ __forceinline__ void self_nrm(const TileX &T, const int k, float (&n)[3]) {
+  if constexpr (is_packed_normal<TileX>::value) { n[0] = T.c_vel[k][1]; n[1] = T.c_vel[k][2]; n[2] = T.c_mu[k]; }
+  else { n[0] = T.c_nrm[k][0]; n[1] = T.c_nrm[k][1]; n[2] = T.c_nrm[k][2]; }
+}
 
 // What the episode kernel reads besides the model and the state: fixed at create, in device memory, fetched by scalar loads where it
 // is used (as kernel arguments its thirty dwords stayed in SGPRs over the whole substep loop and spilled into VGPR lanes).
@@ -860,11 +902,13 @@ __device__ __forceinline__ void self_put(TileX &T, const BallModel FFE_GLOBAL &M
   const float imp = impedance(si_, fabsf(dist - incl));
   const bool excl = dist >= incl;  // inside the margin but not inside margin - gap: kept (an adhesion actuator counts it), exerts nothing
   T.c_pos[at][0] = p.x; T.c_pos[at][1] = p.y; T.c_pos[at][2] = p.z;
-  T.c_nrm[at][0] = n.x; T.c_nrm[at][1] = n.y; T.c_nrm[at][2] = n.z;
+  if constexpr (!is_packed_normal<TileX>::value) { T.c_nrm[at][0] = n.x; T.c_nrm[at][1] = n.y; T.c_nrm[at][2] = n.z; }
   T.c_dist[at] = dist; T.c_excl[at] = excl ? 1 : 0;
   T.c_D[at] = excl ? 0.f : wsf::row_D<float>(imp, invw);
-  T.c_vel[at][0] = wsf::row_neg_aref<float>(M.sc_K, M.sc_B, imp, dist, incl, vel); T.c_vel[at][1] = 0.f; T.c_vel[at][2] = 0.f;
-  T.c_mu[at] = 0.f; T.c_geom[at] = 0;
+  T.c_vel[at][0] = wsf::row_neg_aref<float>(M.sc_K, M.sc_B, imp, dist, incl, vel);
+  if constexpr (is_packed_normal<TileX>::value) { T.c_vel[at][1] = n.x; T.c_vel[at][2] = n.y; T.c_mu[at] = n.z; }  // (the floats such a slot leaves unused)
+  else { T.c_vel[at][1] = 0.f; T.c_vel[at][2] = 0.f; T.c_mu[at] = 0.f; }
+  T.c_geom[at] = 0;
   const int fp = M.l_chain[M.l_nchain[lpos] - 1][lpos];
   T.c_link[at] = (unsigned char)lpos; T.c_blk[at] = (unsigned char)M.d_blk[fp]; T.c_amask[at] = (unsigned short)M.d_amask[fp];
   if (lneg >= 0) {
@@ -1107,7 +1151,10 @@ __device__ __forceinline__ float self_gather(const TileX &T, const BallModel FFE
     const int k = nc + j;
     const bool on_pos = (int)T.c_blk[k] == blk && (((unsigned)T.c_amask[k] >> li) & 1u);
     const bool on_neg = (int)T.c_blk1[k] == blk && (((unsigned)T.c_amask1[k] >> li) & 1u);
-    if (on_pos != on_neg) acc += wsf::row_hinge<float>(T.C[f], T.c_pos[k], T.c_nrm[k], on_pos, on_neg) * w[j];
+    if (on_pos != on_neg) {
+      if constexpr (is_packed_normal<TileX>::value) { float n[3]; self_nrm(T, k, n); acc += wsf::row_hinge<float>(T.C[f], T.c_pos[k], n, on_pos, on_neg) * w[j]; }
+      else acc += wsf::row_hinge<float>(T.C[f], T.c_pos[k], T.c_nrm[k], on_pos, on_neg) * w[j];
+    }
   }
   return acc;
 }
@@ -1121,7 +1168,8 @@ __device__ __forceinline__ float self_gather(const TileX &T, const BallModel FFE
 // contacts, fly-fly ones included (mjTRN_BODY).  Returns the solver's iterations.
 template <class C>
 __device__ __forceinline__ int self_forces(C &c, const int R, const int (&lrow)[3], const float (&lsgn)[3], float (&qs)[3]) {
-  WTileX &T = *c.T;
+  auto &T = *c.T;  // (WTileX, or the environment's WTileSX)
+  using TileX = std::remove_reference_t<decltype(T)>;
   const BallModel FFE_GLOBAL &M = model(c);
   const WalkExtra FFE_GLOBAL &X = *c.X;
   const int lane = c.lane, nc = c.fl.nc, ns = c.fl.ns, nrc = 3 * nc, nrs = nrc + ns, ncs = nc + ns;
@@ -1133,7 +1181,10 @@ __device__ __forceinline__ int self_forces(C &c, const int R, const int (&lrow)[
   float fr[9];
   floor_frame(c, fr);
   if (crow) { const int r3 = 3 * (lane - 3 * (lane / 3)); er[0] = fr[r3]; er[1] = fr[r3 + 1]; er[2] = fr[r3 + 2]; }
-  if (srow) { const float *n = T.c_nrm[nc + lane - nrc]; er[0] = n[0]; er[1] = n[1]; er[2] = n[2]; }
+  if (srow) {
+    if constexpr (is_packed_normal<TileX>::value) self_nrm(T, nc + lane - nrc, er);
+    else { const float *n = T.c_nrm[nc + lane - nrc]; er[0] = n[0]; er[1] = n[1]; er[2] = n[2]; }
+  }
   if (lane < nc) {  // a floor contact: as floor_forces, the adhesion pull shared with the body's fly-fly contacts
     const int g = T.c_geom[lane];
     const float dist = T.c_dist[lane], incl = X.f_margin[g] - X.f_gap[g];
@@ -1469,6 +1520,91 @@ __device__ __noinline__ void floor_sense(WTileS *Tp, const BallModel FFE_GLOBAL 
   DM_SYNC();
 }
 
+// `floor_sense` on the tile that also holds the fly's own contacts (slots nc .. nc + ns - 1, their forces in T.r_f[3 nc + j]): a fly-fly
+// contact pushes the link of geom2 along its normal and the link of geom1 against it (walk_self_sense.hpp); a slot inside the gap has a
+// row with D = 0 and a zero force.  Everything behind the contact loop is floor_sense's.  Out of line and a leaf.
+template <class TileSX>
+__device__ __noinline__ void self_sense(TileSX *Tp, const BallModel FFE_GLOBAL *Mp, const WalkExtra FFE_GLOBAL *Xp, const int lane, const int nc, const int ns,
+                                        const float xr0, const float xr1, const float xr2, const float xr3,
+                                        const float xr4, const float xr5, const float qw, const float qx, const float qy, const float qz) {
+  TileSX &T = *Tp;
+  const BallModel FFE_GLOBAL &M = *Mp;
+  const WalkExtra FFE_GLOBAL &X = *Xp;
+  const unsigned lpack = M.l_pack[lane], tree = M.l_tree[lane];
+  const int parent = (int)(lpack & 0xffu) - 1, ndof = (int)((lpack >> 12) & 0x3u);
+  const int sub = (int)(tree & 0xffu), anc2 = (int)((tree >> 8) & 0xffu) - 1, anc4 = (int)((tree >> 16) & 0xffu) - 1;
+  float fext[3] = {0.f, 0.f, 0.f}, touch = 0.f;
+  if (nc > 0) {
+    const M3 Rr = q2m(Q4{qw, qx, qy, qz});
+    const float Rm[9] = {Rr.m0, Rr.m1, Rr.m2, Rr.m3, Rr.m4, Rr.m5, Rr.m6, Rr.m7, Rr.m8};
+    float fw[9], fr[9];
+#pragma unroll
+    for (int k = 0; k < 9; k++) fw[k] = X.f_frame[k];
+    wf::frame_in_root<float>(Rm, fw, fr);
+    for (int k = 0; k < nc; k++) {
+      if ((int)T.c_link[k] == lane && !T.c_excl[k]) {  // (a contact inside the gap, or one switched off for want of a column, has no row)
+        const float f[3] = {T.r_f[3 * k], T.r_f[3 * k + 1], T.r_f[3 * k + 2]};
+        ws::add_contact_force<float>(fr, f, fext);
+        touch += ws::touch_share<float>(f[0]);
+      }
+    }
+  }
+  for (int j = 0; j < ns; j++) {
+    const int k = nc + j;
+    const bool on_pos = (int)T.c_link[k] == lane, on_neg = (int)T.c_link1[k] == lane;  // (255, the thorax, is no lane's link)
+    if ((on_pos || on_neg) && !T.c_excl[k]) {
+      float n[3];
+      self_nrm(T, k, n);
+      const float f = T.r_f[3 * nc + j];
+      wss::add_pair_force<float>(n, f, on_pos, on_neg, fext);
+      touch += wss::pair_touch_share<float>(f, on_pos, on_neg);
+    }
+  }
+  // sum over the ancestor path of cdof * qacc by pointer jumping, as stage 1 sums the velocities
+  S6 dacc = zero6();
+  float g[3] = {0.f, 0.f, 0.f};
+#pragma unroll
+  for (int s = 0; s < 3; s++) {
+    if (s < ndof) {
+      const int f = M.s_dof[s][lane];
+      const float a = T.X4[f].x;
+      dacc = dacc + a * ld6(T.C[f]);
+      g[0] += a * T.F[f][3]; g[1] += a * T.F[f][4]; g[2] += a * T.F[f][5];
+    }
+  }
+#pragma unroll
+  for (int r = 0; r < 3; r++) {
+    const int an = r == 0 ? parent : (r == 1 ? anc2 : anc4);
+    st6(T.lp[lane], dacc);
+    DM_SYNC();
+    if (an >= 0) dacc = dacc + ld6(T.lp[an]);
+    DM_SYNC();
+  }
+  {
+    float *o = T.lp[lane];
+    o[0] = g[0]; o[1] = g[1]; o[2] = g[2]; o[3] = fext[0]; o[4] = fext[1]; o[5] = fext[2];
+  }
+  DM_SYNC();
+  const int fi = M.l_force[lane], ti = M.l_touch[lane];
+  if (fi >= 0) {
+    float gs[3] = {0.f, 0.f, 0.f};
+#pragma unroll 1
+    for (int t = 1; t < sub; t++) {
+      const float *p = T.lp[lane + t];
+      gs[0] += p[0]; gs[1] += p[1]; gs[2] += p[2]; fext[0] += p[3]; fext[1] += p[4]; fext[2] += p[5];
+    }
+    const float A[6] = {xr0 + dacc.a0, xr1 + dacc.a1, xr2 + dacc.a2, xr3 + dacc.l0, xr4 + dacc.l1, xr5 + dacc.l2};
+    const float *sp = T.sp[fi];
+    float fint[3], o[3];
+    ws::accel_term<float>(sp[3], sp + 4, A, fint);
+    fint[0] += gs[0] + sp[0] - fext[0]; fint[1] += gs[1] + sp[1] - fext[1]; fint[2] += gs[2] + sp[2] - fext[2];
+    ws::to_site<float>(T.fsq[fi], fint, o);
+    T.sens[9 + 3 * fi] += o[0]; T.sens[9 + 3 * fi + 1] += o[1]; T.sens[9 + 3 * fi + 2] += o[2];
+  }
+  if (ti >= 0) T.sens[27 + ti] += touch;
+  DM_SYNC();
+}
+
 // ------------------------------------------------------------------------------------------------ stage 2
 // EP (the episode kernel): also mj's qacc = M^-1 (qfrc_smooth + qfrc_constraint) through M's own factor - the Euler solve below is
 // implicit in the joint damping, so its solution is not qacc - for the accelerometer of this substep (`acc`, from the state before the
@@ -1638,7 +1774,8 @@ __device__ __forceinline__ void stage2(C &c, float act_reg, float ctrl_reg, floa
     const float qr[4] = {c.rq.w, c.rq.x, c.rq.y, c.rq.z}, wb[3] = {c.wb.x, c.wb.y, c.wb.z}, al[3] = {aw.x, aw.y, aw.z}, wd[3] = {xr[0], xr[1], xr[2]};
     wi::imu_acceleration<float>(qr, wb, al, wd, grav ? M.gz : 0.f, ep->site_pos, ep->site_quat, acc);
     if constexpr (SENSE) {  // (last: only the accelerometer and sum qacc^2 are live across the call)
-      floor_sense(c.T, (ModelPtr)c.M, c.X, lane, c.fl.nc, xr[0], xr[1], xr[2], xr[3], xr[4], xr[5], c.rq.w, c.rq.x, c.rq.y, c.rq.z);
+      if constexpr (SELF) self_sense(c.T, (ModelPtr)c.M, c.X, lane, c.fl.nc, c.fl.ns, xr[0], xr[1], xr[2], xr[3], xr[4], xr[5], c.rq.w, c.rq.x, c.rq.y, c.rq.z);
+      else floor_sense(c.T, (ModelPtr)c.M, c.X, lane, c.fl.nc, xr[0], xr[1], xr[2], xr[3], xr[4], xr[5], c.rq.w, c.rq.x, c.rq.y, c.rq.z);
     }
     if (!integrate) { act_out = act_reg; return; }
 #pragma unroll
@@ -1879,7 +2016,8 @@ __device__ __forceinline__ void walk_substeps(Tile &T, const WalkModel *__restri
     S.wb[0] = c.wb.x; S.wb[1] = c.wb.y; S.wb[2] = c.wb.z;
     S.pos[0] = c.pos[0]; S.pos[1] = c.pos[1]; S.pos[2] = c.pos[2];
     if constexpr (LIMITS) { S.nlim = nlim; S.iters = iters; S.step_bits = c.overflow; }
-    if constexpr (FLOOR && EP) ep.a->rec[env] = FloorRec{c.fl.nc, T.rootf[6], c.fl.mind, 0};
+    if constexpr (FLOOR && EP && is_self_tile<Tile>::value) ep.a->rec[env] = FloorRec{c.fl.nc + c.fl.ns, T.rootf[6], c.fl.mind, c.fl.ns};
+    else if constexpr (FLOOR && EP) ep.a->rec[env] = FloorRec{c.fl.nc, T.rootf[6], c.fl.mind, 0};
     else if constexpr (is_self_tile<Tile>::value) ep.rec[env] = FloorRec{c.fl.nc + c.fl.ns, T.rootf[6], c.fl.mind, c.fl.ns};
     else if constexpr (FLOOR) ep.rec[env] = FloorRec{c.fl.nc, T.rootf[6], c.fl.mind, 0};
   }
@@ -1914,6 +2052,10 @@ __device__ __forceinline__ void walk_substeps(Tile &T, const WalkModel *__restri
 // hipGetLastError.
 void launch_imitation_floor_step(const WalkModel *model, int flags, WState *states, const ImitArgs *args, const float *action, float *obs, int batch,
                                  hipStream_t stream);
+// One control step of walk_imitation on the floor with the fly's own contacts (walk_imit_self_env.hip): launches `imitation_self_step`
+// on `stream`; the caller checks hipGetLastError.
+void launch_imitation_self_step(const WalkModel *model, int flags, WState *states, const ImitArgs *args, const float *action, float *obs, int batch,
+                                hipStream_t stream);
 // `nphys` substeps of bare physics with the floor and the fly's own contacts (walk_self_env.hip): launches `floor_self_step` on `stream`;
 // the caller checks hipGetLastError.
 void launch_floor_self_step(const WalkModel *model, int flags, WState *states, const float *ctrl, FloorRec *rec, int batch, int nphys, hipStream_t stream);

@@ -2,7 +2,8 @@
 batched MI355X environments instead of single-instance `composer.Environment`s.
 
 Built so far: `flight_imitation` (`fly_envs.py:29-72`), `walk_on_ball` (`fly_envs.py:125-157`) and `walk_imitation` without its
-floor (`floor_contacts=False`; the default call raises until floor contacts exist).  `vision_guided_flight` and `template_task` are
+floor (`floor_contacts=False`), on the floor plane (`floor_contacts="primitives"`) and there with the fly's own contacts
+(`self_contacts=True`); the default call raises until the plane collides the fly's ellipsoids and cylinders too.  `vision_guided_flight` and `template_task` are
 later rows of SURVEY.md section 8 and raise `NotImplementedError`.
 """
 
@@ -61,8 +62,8 @@ def walk_on_ball(random_state=None, *, batch_size: int = 1, device: int = 0, **e
     return BatchedBallEnv(batch_size=batch_size, device=device, time_limit=2.0, **env_kwargs)
 
 
-def walk_imitation(ref_path=None, random_state=None, terminal_com_dist: float = 0.3, *, floor_contacts=True, batch_size: int = 1,
-                   device: int = 0, **env_kwargs):
+def walk_imitation(ref_path=None, random_state=None, terminal_com_dist: float = 0.3, *, floor_contacts=True, self_contacts: bool = False,
+                   batch_size: int = 1, device: int = 0, **env_kwargs):
     """Requires a fruitfly to track a reference walking fly (`fly_envs.py:75-122`).
 
     Built: the compiled model (`assets/fly_walk.ffmb`: free root, floor plane, Walking
@@ -70,15 +71,15 @@ def walk_imitation(ref_path=None, random_state=None, terminal_com_dist: float = 
     task layer on the device (`tasks/walk_tracker.py`: features, reward, termination, observation columns), the free-root smooth
     dynamics with the joint limits of the 102 hinges (`batched_env.BatchedWalkPhysics`), and around them the sensors and the episode
     protocol of the step kernel (`batched_env.BatchedWalkEnv`), with the floor plane under the fly's 48 sphere / capsule geoms and the
-    force and touch sensors on it; the float64 CPU restatement of the whole task that the tests check against is test
-    infrastructure, outside this package.  Missing among the floor contacts and the others of the reference's task: the fly's own
-    contacts (leg against leg, leg against body) and the plane against the fly's ellipsoid and cylinder geoms.
+    force and touch sensors on it and, opt-in, the fly's own contacts (leg against leg, leg against body); the float64 CPU restatement
+    of the whole task that the tests check against is test infrastructure, outside this package.  Missing among the floor contacts
+    of the reference's task: the plane against the fly's ellipsoid and cylinder geoms.
 
     So the default call (`floor_contacts=True`, the reference's task with every contact) raises `NotImplementedError`: this package
     has no CPU path and the factory fails instead of returning a slow or a different environment.  The explicit opt-ins to what exists:
     `floor_contacts="primitives"` returns a `BatchedWalkEnv` that stands and walks on the floor (plane against spheres and capsules; the
-    fly's own contacts off), and `floor_contacts=False` one whose fly falls freely under gravity (or floats with
-    `physics_flags=FFE_NO_GRAVITY`), with force and touch reading zero.
+    fly's own contacts off unless `self_contacts=True` switches them on), and `floor_contacts=False` one whose fly falls freely under
+    gravity (or floats with `physics_flags=FFE_NO_GRAVITY`), with force and touch reading zero.
 
     Args:
         ref_path: `.npz` written by `tasks.walking.save_npz` (clips of individual lengths with their tracked features).  None = the
@@ -87,16 +88,18 @@ def walk_imitation(ref_path=None, random_state=None, terminal_com_dist: float = 
         terminal_com_dist: an episode terminates when the root is further than this from the reference root (cm).
         floor_contacts: True (the default) raises; "primitives" returns the environment on the floor plane (sphere / capsule geoms only);
             False returns the environment without the floor.
+        self_contacts: with `floor_contacts="primitives"`, True adds the fly's own contacts (`BatchedWalkEnv(self_contacts=True)`).
         batch_size, device: batching.  `env_kwargs` go to `BatchedWalkEnv` (`inference_mode`, `env_id_base`, `pad_first_obs`,
             `physics_flags`, `canonical_actions`, `clip_actions`, `double_buffer`)."""
     if isinstance(floor_contacts, str) and floor_contacts != "primitives":
         raise ValueError(f"walk_imitation: floor_contacts must be True, False or \"primitives\", not {floor_contacts!r}")
     if floor_contacts and floor_contacts != "primitives":
         raise NotImplementedError("walk_imitation: the floor contacts of the HIP step kernel are built for the floor plane against the fly's sphere "
-                                  "and capsule geoms only (DESIGN.md section 12); the fly's own contacts and the plane against its ellipsoid and "
-                                  "cylinder geoms are missing.  The model, the device task layer (WalkTracker), the free-root smooth dynamics "
-                                  "with their joint limits (BatchedWalkPhysics), the sensors and the episode protocol (BatchedWalkEnv) exist: "
-                                  "walk_imitation(floor_contacts=\"primitives\") returns the environment on that floor, "
+                                  "and capsule geoms only (DESIGN.md section 12): the plane against its ellipsoid and cylinder geoms is missing, "
+                                  "and the fly's own contacts are the opt-in self_contacts=True.  The model, the device task layer "
+                                  "(WalkTracker), the free-root smooth dynamics with their joint limits (BatchedWalkPhysics), the sensors and "
+                                  "the episode protocol (BatchedWalkEnv) exist: walk_imitation(floor_contacts=\"primitives\") returns the "
+                                  "environment on that floor, with self_contacts=True also with the fly's own contacts, "
                                   "walk_imitation(floor_contacts=False) the one without a floor")
     from .batched_env import BatchedWalkEnv
     from .tasks import walking
@@ -116,7 +119,8 @@ def walk_imitation(ref_path=None, random_state=None, terminal_com_dist: float = 
         seed = 0 if random_state is None else int(random_state)
     # fly_envs.py:100-118: time_limit 10 s, future_steps 64, joint_filter / adhesion_filter compiled into the model
     return BatchedWalkEnv(refs, view, batch_size=batch_size, device=device, seed=seed, future_steps=64, time_limit=10.0,
-                          terminal_com_dist=terminal_com_dist, floor_contacts=floor_contacts == "primitives", **env_kwargs)
+                          terminal_com_dist=terminal_com_dist, floor_contacts=floor_contacts == "primitives", self_contacts=bool(self_contacts),
+                          **env_kwargs)
 
 
 def vision_guided_flight(*args, **kwargs):

@@ -64,8 +64,9 @@ enum {
   FFE_WALK_JOINT_LIMITS = 512,
   /* ffe_create_walk_physics only: the handle is the walk_imitation environment (sensors, episode protocol, task layer): with the floor
    * off as FFE_NO_CONTACT | FFE_WALK_JOINT_LIMITS | FFE_WALK_EPISODES plus force switches (the third step kernel of csrc/walk_env.hip),
-   * on the floor plane with FFE_WALK_FLOOR on top of that (csrc/walk_floor_env.hip).  An opt-in bit and provisional for the same
-   * reason: it goes when every contact of the reference's task is built. */
+   * on the floor plane with FFE_WALK_FLOOR on top of that (csrc/walk_floor_env.hip), and there with the fly's own contacts with
+   * FFE_WALK_SELF | FFE_WALK_SELF_EPISODES on top of both (csrc/walk_imit_self_env.hip).  An opt-in bit and provisional for the same reason: it goes when every
+   * contact of the reference's task is built. */
   FFE_WALK_EPISODES = 1024,
   /* ffe_create_walk_physics only: the floor plane against the fly's sphere and capsule geoms, on the bare-physics handle (the fourth
    * step kernel of csrc/walk_env.hip) or, with FFE_WALK_EPISODES and the task, under the environment (csrc/walk_floor_env.hip).  Accepted
@@ -74,12 +75,19 @@ enum {
    * on.  An opt-in bit and provisional as the two above. */
   FFE_WALK_FLOOR = 2048,
   /* ffe_create_walk_physics only: the fly's own contacts (its 48 sphere / capsule geoms against each other, and every candidate pair
-   * with an ellipsoid or a cylinder on one side) on the bare-physics floor handle (csrc/walk_self_env.hip).  Accepted only as
-   * FFE_NO_CONTACT | FFE_WALK_JOINT_LIMITS | FFE_WALK_FLOOR | FFE_WALK_SELF plus force switches, FFE_NO_NOSLIP and FFE_NO_ADHESION;
+   * with an ellipsoid or a cylinder on one side) on the bare-physics floor handle (csrc/walk_self_env.hip) or, with FFE_WALK_EPISODES and
+   * the task (and FFE_WALK_SELF_EPISODES, below), under the environment on the floor (csrc/walk_imit_self_env.hip).  Accepted only as
+   * FFE_NO_CONTACT | FFE_WALK_JOINT_LIMITS | FFE_WALK_FLOOR | FFE_WALK_SELF [| FFE_WALK_EPISODES | FFE_WALK_SELF_EPISODES] plus force switches, FFE_NO_NOSLIP and
+   * FFE_NO_ADHESION;
    * FFE_NO_CONTACT is then only the marker every accepted set of that create call carries (plain "contacts on" stays a pinned refusal
-   * while the floor against ellipsoids and cylinders is missing): the contacts that are built are all on.  Not yet carried by the
-   * environment: with FFE_WALK_EPISODES the bit is refused.  An opt-in bit and provisional as the three above. */
-  FFE_WALK_SELF = 4096
+   * while the floor against ellipsoids and cylinders is missing): the contacts that are built are all on.  With FFE_WALK_EPISODES the
+   * bit needs FFE_WALK_FLOOR, the task and FFE_WALK_SELF_EPISODES: a handle without a task does not carry the episode protocol and is
+   * refused.  An opt-in bit and provisional as the three above. */
+  FFE_WALK_SELF = 4096,
+  /* ffe_create_walk_physics only: asks for FFE_WALK_SELF under the environment.  It exists because FFE_WALK_EPISODES | FFE_WALK_FLOOR |
+   * FFE_WALK_SELF by themselves are a pinned refusal of that create call, as plain FFE_NO_CONTACT is (see FFE_WALK_JOINT_LIMITS):
+   * accepted only together with exactly those three and the task, refused in every other set.  Provisional as the four above. */
+  FFE_WALK_SELF_EPISODES = 8192
 };
 
 typedef struct ffe_walk_task_s ffe_walk_task; /* the walk_imitation task layer's inputs, defined with ffe_walktask_create below */
@@ -163,7 +171,8 @@ int ffe_create_walk_on_ball(const void *model_blob, size_t blob_size, const ffe_
  * protocol on the device, a fly that falls freely (or floats with FFE_NO_GRAVITY).  FFE_WALK_FLOOR adds the floor plane against the
  * fly's 48 sphere / capsule geoms (elliptic cones, noslip, adhesion) to the bare-physics handle or, together with FFE_WALK_EPISODES,
  * to the environment, whose force and touch columns are then live; FFE_WALK_SELF adds the fly's own contacts to the bare-physics floor
- * handle.  The fly's own contacts under the environment and the floor against ellipsoids and cylinders are not built yet. */
+ * handle or, together with FFE_WALK_EPISODES | FFE_WALK_FLOOR | FFE_WALK_SELF_EPISODES, to the environment on the floor.  The floor against ellipsoids and
+ * cylinders is not built yet. */
 typedef struct {
   /* FFE_NO_CONTACT and exactly one of FFE_NO_LIMIT (smooth dynamics alone) or FFE_WALK_JOINT_LIMITS (joint limits on: up to 48 limit
    * rows per env and substep), plus any of the force switches FFE_NO_FLUID / _DAMPER / _SPRING / _GRAVITY / _ACTUATION; every other
@@ -173,15 +182,18 @@ typedef struct {
    * FFE_NO_ADHESION (meaningful only with this bit), with or without FFE_WALK_EPISODES; every other set with it - with FFE_NO_LIMIT,
    * without FFE_WALK_JOINT_LIMITS, with FFE_WALK_EPISODES and a null `task` - is refused with a text naming FFE_WALK_FLOOR (and
    * FFE_WALK_EPISODES when that bit was passed too).  FFE_WALK_SELF is accepted only as FFE_NO_CONTACT | FFE_WALK_JOINT_LIMITS |
-   * FFE_WALK_FLOOR | FFE_WALK_SELF plus the same switches; every other set with it - without FFE_WALK_FLOOR, with FFE_NO_LIMIT, with
-   * FFE_WALK_EPISODES (the environment does not carry the fly's own contacts yet) - is refused with a text naming FFE_WALK_SELF.  The
-   * accepted sets:
+   * FFE_WALK_FLOOR | FFE_WALK_SELF plus the same switches, bare physics, or with FFE_WALK_EPISODES | FFE_WALK_SELF_EPISODES and the
+   * task on top of exactly that; every other set with it - without FFE_WALK_FLOOR, with FFE_NO_LIMIT, with FFE_WALK_EPISODES and a null
+   * `task` (a handle without the task does not carry the episode protocol), with only one of FFE_WALK_EPISODES and
+   * FFE_WALK_SELF_EPISODES - is refused with a text naming FFE_WALK_SELF.  The accepted sets:
    *   FFE_NO_CONTACT | FFE_NO_LIMIT                                                   smooth dynamics
    *   FFE_NO_CONTACT | FFE_WALK_JOINT_LIMITS                                          + joint limits
    *   FFE_NO_CONTACT | FFE_WALK_JOINT_LIMITS | FFE_WALK_FLOOR                         + the floor plane (bare physics)
    *   FFE_NO_CONTACT | FFE_WALK_JOINT_LIMITS | FFE_WALK_FLOOR | FFE_WALK_SELF         + the fly's own contacts (bare physics)
    *   FFE_NO_CONTACT | FFE_WALK_JOINT_LIMITS | FFE_WALK_EPISODES                      walk_imitation, floor off
-   *   FFE_NO_CONTACT | FFE_WALK_JOINT_LIMITS | FFE_WALK_EPISODES | FFE_WALK_FLOOR     walk_imitation on the floor plane */
+   *   FFE_NO_CONTACT | FFE_WALK_JOINT_LIMITS | FFE_WALK_EPISODES | FFE_WALK_FLOOR     walk_imitation on the floor plane
+   *   FFE_NO_CONTACT | FFE_WALK_JOINT_LIMITS | FFE_WALK_EPISODES | FFE_WALK_FLOOR | FFE_WALK_SELF | FFE_WALK_SELF_EPISODES
+   *                                                                                   + the fly's own contacts */
   int32_t physics_flags;
   /* read only when physics_flags has FFE_WALK_EPISODES (a caller without the bit may pass the one int above alone) */
   const ffe_walk_task *task;  /* clips, tracked joints / sites, reward and termination constants: a float32 task layer of the env's
@@ -236,6 +248,11 @@ typedef struct {
  *   ffe_get_task_state  int 0 = clip, int 1 = step counter, int 2 = episodes started (low 32 bits), int 3 = needs_reset (the next
  *                       ffe_step resets this env), ints 4, 6, 7 as on a limits handle, int 5 and every real zero; with FFE_WALK_FLOOR
  *                       int 5, real 0 and real 1 as on a floor handle, and the floor's bits 1 / 4 in step_bits and episode_bits too
+ *                       with FFE_WALK_SELF on top of that (the force and touch columns then carry the fly-fly contacts' forces on both
+ *                       of their links) every column keeps its meaning and: int 5 = all contacts kept in the last substep, floor
+ *                       and fly-fly, real 2 = the fly-fly contacts among them (int 3 is needs_reset here; real 2 is zero on every other
+ *                       handle), real 1 = the smallest distance over both kinds, and bit value 8 (a convex candidate pair left out)
+ *                       joins bits 1 / 2 / 4 in step_bits, sticky per episode in episode_bits
  * A failure of the env's task layer is the env handle's error text. */
 int ffe_create_walk_physics(const void *model_blob, size_t blob_size, const ffe_walk_physics_task *task, int batch, int device,
                             ffe_handle *out);

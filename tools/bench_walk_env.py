@@ -1,9 +1,11 @@
 """Control steps/s of the walk_imitation environment (`BatchedWalkEnv`) at B = 4 096, and the share of each launch in a step: with the
 floor off (csrc/walk_env.hip `imitation_step_kernel` and the four launches around it) or, with `--floor`, on the floor plane
 (csrc/walk_floor_env.hip `imitation_floor_step` in its place; `walk_imitation(floor_contacts="primitives")`).  Nothing is asserted and
-there is no target.
+there is no target.  `--self` compares the environment on the floor with the fly's own contacts (csrc/walk_imit_self_env.hip
+`imitation_self_step`; `walk_imitation(floor_contacts="primitives", self_contacts=True)`) with the one without them in one session:
+the two envs and the two action cases alternate window by window, and the summary holds the medians, their ratio and the flagged steps.
 
-    python tools/bench_walk_env.py [--floor] [--batch 4096] [--windows 5] [--iters 50] [--log profiles/bench_walk_env.log] [--no-trace]
+    python tools/bench_walk_env.py [--floor | --self] [--batch 4096] [--windows 5] [--iters 50] [--log profiles/bench_walk_env.log] [--no-trace]
 
 Timing: `ffe_time_steps` (device events around `iters` step launches on the env's stream) per window; the cases - zero actions and
 uniform +-0.5 actions - alternate window by window so that clock and neighbours act on both alike; window 0 of each case warms up and
@@ -30,10 +32,44 @@ def launches(floor):
             "episode_close_kernel")
 
 
-def make_env(batch, floor=False):
+def make_env(batch, floor=False, self_contacts=False):
     from flybody_amd import fly_envs
 
-    return fly_envs.walk_imitation(floor_contacts="primitives" if floor else False, batch_size=batch)
+    return fly_envs.walk_imitation(floor_contacts="primitives" if floor else False, self_contacts=self_contacts, batch_size=batch)
+
+
+def compare_self(args, say):
+    """`--self`: windows alternate between the env with the fly's own contacts and the floor env without them, case by case."""
+    import numpy as np
+    import torch
+
+    B = args.batch
+    envs = {"floor_self": make_env(B, True, True), "floor": make_env(B, True, False)}
+    cases = action_cases(torch, B)
+    ms = {(e, c): [] for e in envs for c in cases}
+    flagged = {e: 0 for e in envs}
+    for w in range(args.windows + 1):  # window 0 warms up
+        for case, act in cases.items():
+            for name, env in envs.items():
+                env.reset()
+                t = env.time_steps(act, args.iters)
+                v = env.validity()
+                nflag = int(v.episode_flagged_steps.sum())  # (flagged control steps of the episodes the window's steps belong to)
+                say({"env": name, "case": case, "window": w, "warmup": w == 0, "ms_per_step": t, "env_steps_per_s": B / t * 1e3,
+                     "finite": bool(torch.isfinite(env.flat_observation).all()), "episode_flagged_steps": nflag,
+                     "episode_bits": int(np.bitwise_or.reduce(v.episode_bits.cpu().numpy(), initial=0))})
+                if w > 0:
+                    ms[(name, case)].append(t)
+                    flagged[name] += nflag
+    out = {"batch": B, "iters_per_window": args.iters, "windows": args.windows, "flagged_steps": flagged}
+    for case in cases:
+        a, b = statistics.median(ms[("floor_self", case)]), statistics.median(ms[("floor", case)])
+        out[case] = {"floor_self_median_ms_per_step": a, "floor_median_ms_per_step": b, "ratio": a / b,
+                     "floor_self_step_kernel_alone_ms": envs["floor_self"].time_kernel(cases[case], args.iters),
+                     "floor_step_kernel_alone_ms": envs["floor"].time_kernel(cases[case], args.iters)}
+    say(out)
+    for env in envs.values():
+        env.close()
 
 
 def action_cases(torch, batch):
@@ -85,6 +121,8 @@ def main():
     ap.add_argument("--iters", type=int, default=50)
     ap.add_argument("--trace-steps", type=int, default=200)
     ap.add_argument("--floor", action="store_true", help="the environment on the floor plane instead of the one with the floor off")
+    ap.add_argument("--self", dest="self_contacts", action="store_true",
+                    help="compare the environment on the floor with the fly's own contacts with the one without them (no trace)")
     ap.add_argument("--no-trace", action="store_true", help="skip the rocprofv3 run")
     ap.add_argument("--trace-child", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--log", default=None, help="append the printed lines to this file")
@@ -99,6 +137,13 @@ def main():
         print(line, flush=True)
         lines.append(line)
 
+    if args.self_contacts:
+        compare_self(args, say)
+        if args.log:
+            os.makedirs(os.path.dirname(os.path.abspath(args.log)), exist_ok=True)
+            with open(args.log, "a") as f:
+                f.write("\n".join(lines) + "\n")
+        return
     if not args.no_trace:  # first, while this process has not touched the device
         say({"batch": args.batch, "floor": args.floor, "trace_steps": args.trace_steps,
              "launch_shares": launch_shares(args.batch, args.trace_steps, args.floor)})
