@@ -14,7 +14,9 @@
 // solve: free fall is exact, and no gravity torque about the root origin is rounded in float32 and divided by the small rotational
 // inertias of S (which cost 2e-3 rad/s^2 of root angular acceleration when gravity went through the solve).
 // The device code of the substep lives in walk_substeps.hpp (stage 1 is the text fragment `#include "leg_stage1.inc"` inside its `stage1`),
-// shared with walk_floor_env.hip, which holds the fifth kernel: the environment on the floor.
+// shared with walk_floor_env.hip, walk_self_env.hip and walk_imit_self_env.hip, one kernel each: there the constraint block of every floor
+// tile is the one `contact_forces` and the sensor pass the one `contact_sense`, what the fly's own contacts add under `Tile::kSelf`.
+// On the host one table names the handle kinds `walk_create` accepts, and one kernel (`walk_report_kernel`) reports for all of them.
 // Four kernels of this file share that code: three of bare physics (`ffe_physics_step`; the third, `floor_step`, collides the floor plane with
 // the fly's sphere / capsule geoms and is described where its code starts: "floor contacts") and
 // the walk_imitation environment with the floor off (`imitation_step_kernel`, at the end of the kernel section).  `walk_step_kernel` is the smooth dynamics alone (a handle created with FFE_NO_CONTACT |
@@ -200,22 +202,30 @@ __global__ void episode_init_kernel(EpState *eps, int batch) {
   z.needs_reset = 1; z.forced = -1;
   eps[i] = z;
 }
-// episode handle: task state {clip, step counter, episode (low 32 bits), needs_reset, limit rows of the last substep, 0, solver
-// iterations of the last substep, overflow bits of the last launch}, reals zero; validity {step_bits, episode_flagged_steps,
-// episode_bits, episode_steps}.  On the floor (`rec` not null) int 5 and reals 0 / 1 are the floor handle's.  With FFE_WALK_SELF int 5
-// counts the floor and the fly-fly contacts kept, real 1 is taken over both kinds, and real 2 is the fly-fly count (int 3, where the
-// bare-physics handle reports it, is needs_reset here; real 2 is zero on every other handle).
-__global__ void episode_report_kernel(const EpState *eps, const WState *states, const FloorRec *rec, int *ints, double *reals, int *info, int batch) {
+// Task state and validity of every handle with limit rows; `eps` is null without FFE_WALK_EPISODES, `rec` without FFE_WALK_FLOOR.
+//   ints      {clip, step counter, episode (low 32 bits), needs_reset} of the episode record, zeros without one - but int 3 of a
+//             bare-physics floor handle is the fly-fly contacts among int 5 (0 without FFE_WALK_SELF); limit rows of the last substep;
+//             contacts kept in the last substep (floor and, with FFE_WALK_SELF, fly-fly), 0 off the floor; solver iterations of the last
+//             substep; overflow bits of the last launch
+//   reals     on the floor the sum of the contacts' normal forces and the smallest contact distance (0 without a contact; with
+//             FFE_WALK_SELF over both kinds), and on an episode handle, where int 3 is taken, the fly-fly count in real 2; zeros otherwise
+//   validity  {overflow bits of the last launch (1 more contacts than slots, 2 more rows than RMAX, 4 more rows in a block than columns,
+//             8 a convex candidate pair left out because a pair list of the substep was full), episode_flagged_steps, episode_bits,
+//             episode_steps}, the last three zero without an episode record
+__global__ void walk_report_kernel(const EpState *eps, const WState *states, const FloorRec *rec, int *ints, double *reals, int *info, int batch) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= batch) return;
   const WState &S = states[i];
-  const EpState &e = eps[i];
   if (ints) {
     int *o = ints + (size_t)i * 8;
-    o[0] = e.clip; o[1] = e.step; o[2] = (int)(unsigned)e.episode; o[3] = e.needs_reset; o[4] = S.nlim; o[5] = rec ? rec[i].ncon : 0; o[6] = S.iters; o[7] = S.step_bits;
-    for (int k = 0; k < 8; k++) reals[(size_t)i * 8 + k] = !rec ? 0.0 : (k == 0 ? (double)rec[i].fsum : (k == 1 ? (double)rec[i].mind : (k == 2 ? (double)rec[i].nself : 0.0)));
+    o[0] = eps ? eps[i].clip : 0; o[1] = eps ? eps[i].step : 0; o[2] = eps ? (int)(unsigned)eps[i].episode : 0;
+    o[3] = eps ? eps[i].needs_reset : (rec ? rec[i].nself : 0);
+    o[4] = S.nlim; o[5] = rec ? rec[i].ncon : 0; o[6] = S.iters; o[7] = S.step_bits;
+    double *r = reals + (size_t)i * 8;
+    for (int k = 0; k < 8; k++) r[k] = 0.0;
+    if (rec) { r[0] = (double)rec[i].fsum; r[1] = (double)rec[i].mind; if (eps) r[2] = (double)rec[i].nself; }
   }
-  if (info) *reinterpret_cast<int4 *>(info + (size_t)i * 4) = make_int4(S.step_bits, e.ep_flagged, e.ep_bits, e.step);
+  if (info) *reinterpret_cast<int4 *>(info + (size_t)i * 4) = eps ? make_int4(S.step_bits, eps[i].ep_flagged, eps[i].ep_bits, eps[i].step) : make_int4(S.step_bits, 0, 0, 0);
 }
 
 // mj: mj_normalizeQuat as the position stage applies it (float32, a null quaternion becomes the identity)
@@ -250,35 +260,6 @@ __global__ void walk_set_state_kernel(WState *states, const double *qpos, const 
   for (int k = t; k < ND; k += blockDim.x) { S.q[k] = (float)qp[7 + k]; S.v[k] = (float)qv[6 + k]; }
   if (t < 3) { S.pos[t] = qp[t]; S.vlin[t] = (float)qv[t]; S.wb[t] = (float)qv[3 + t]; }
   if (t == 0) store_quat(S, qp[3], qp[4], qp[5], qp[6]);
-}
-// limits handle: task state {0, 0, 0, 0, limit rows of the last substep, 0, solver iterations of the last substep, overflow bits of the
-// last launch}, reals zero; validity {overflow bits of the last launch, 0, 0, 0}
-__global__ void walk_limits_report_kernel(const WState *states, int *ints, double *reals, int *info, int batch) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= batch) return;
-  const WState &S = states[i];
-  if (ints) {
-    int *o = ints + (size_t)i * 8;
-    o[0] = o[1] = o[2] = o[3] = o[5] = 0; o[4] = S.nlim; o[6] = S.iters; o[7] = S.step_bits;
-    for (int k = 0; k < 8; k++) reals[(size_t)i * 8 + k] = 0.0;
-  }
-  if (info) *reinterpret_cast<int4 *>(info + (size_t)i * 4) = make_int4(S.step_bits, 0, 0, 0);
-}
-// floor handle: the limits handle's report with int 5 = floor contacts kept in the last substep, real 0 = the sum of their normal
-// forces, real 1 = the smallest contact distance (0 without a contact); validity {overflow bits of the last launch (1 more contacts
-// than slots, 2 more rows than RMAX, 4 more rows in a block than columns), 0, 0, 0}.  With FFE_WALK_SELF int 5 counts the floor and the
-// fly-fly contacts kept, int 3 the fly-fly ones among them (0 otherwise), real 1 is taken over both kinds, and bit value 8 says that a
-// convex candidate pair was left out because a pair list of the substep was full
-__global__ void floor_report_kernel(const WState *states, const FloorRec *rec, int *ints, double *reals, int *info, int batch) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= batch) return;
-  const WState &S = states[i];
-  if (ints) {
-    int *o = ints + (size_t)i * 8;
-    o[0] = o[1] = o[2] = 0; o[3] = rec[i].nself; o[4] = S.nlim; o[5] = rec[i].ncon; o[6] = S.iters; o[7] = S.step_bits;
-    for (int k = 0; k < 8; k++) reals[(size_t)i * 8 + k] = k == 0 ? (double)rec[i].fsum : (k == 1 ? (double)rec[i].mind : 0.0);
-  }
-  if (info) *reinterpret_cast<int4 *>(info + (size_t)i * 4) = make_int4(S.step_bits, 0, 0, 0);
 }
 __global__ void walk_act_kernel(WState *states, double *act, int batch, int set) {
   const int env = blockIdx.x, t = threadIdx.x;
@@ -404,36 +385,17 @@ struct WalkEnv final : ffe::EnvBackend {
     hipLaunchKernelGGL(walk_act_kernel, dim3(batch), dim3(64), 0, (hipStream_t)stream, states, const_cast<double *>(act), batch, 1);
     HIP_OK(hipGetLastError());
   }
+  void report(int *ints, double *reals, int *info, void *stream) {
+    hipLaunchKernelGGL(walk_report_kernel, dim3((batch + 63) / 64), dim3(64), 0, (hipStream_t)stream, eps, states, rec, ints, reals, info, batch);
+    HIP_OK(hipGetLastError());
+  }
   void get_task_state(int32_t *ints, double *reals, void *stream) override {  // int32[B][8] and float64[B][8]: zeros on a plain handle
-    if (episodes) {
-      hipLaunchKernelGGL(episode_report_kernel, dim3((batch + 63) / 64), dim3(64), 0, (hipStream_t)stream, eps, states, rec, ints, reals, (int *)nullptr, batch);
-      HIP_OK(hipGetLastError());
-      return;
-    }
-    if (floor) {
-      hipLaunchKernelGGL(floor_report_kernel, dim3((batch + 63) / 64), dim3(64), 0, (hipStream_t)stream, states, rec, ints, reals, (int *)nullptr, batch);
-      HIP_OK(hipGetLastError());
-      return;
-    }
-    if (limits) {
-      hipLaunchKernelGGL(walk_limits_report_kernel, dim3((batch + 63) / 64), dim3(64), 0, (hipStream_t)stream, states, ints, reals, (int *)nullptr, batch);
-      HIP_OK(hipGetLastError());
-      return;
-    }
+    if (limits) return report(ints, reals, nullptr, stream);
     HIP_OK(hipMemsetAsync(ints, 0, sizeof(int32_t) * 8 * (size_t)batch, (hipStream_t)stream));
     HIP_OK(hipMemsetAsync(reals, 0, sizeof(double) * 8 * (size_t)batch, (hipStream_t)stream));
   }
   void get_validity(int32_t *info, void *stream) override {  // int32[B][4]: zeros on a plain handle
-    if (episodes) {
-      hipLaunchKernelGGL(episode_report_kernel, dim3((batch + 63) / 64), dim3(64), 0, (hipStream_t)stream, eps, states, rec, (int *)nullptr, (double *)nullptr, info, batch);
-      HIP_OK(hipGetLastError());
-      return;
-    }
-    if (limits) {
-      hipLaunchKernelGGL(walk_limits_report_kernel, dim3((batch + 63) / 64), dim3(64), 0, (hipStream_t)stream, states, (int *)nullptr, (double *)nullptr, info, batch);
-      HIP_OK(hipGetLastError());
-      return;
-    }
+    if (limits) return report(nullptr, nullptr, info, stream);
     HIP_OK(hipMemsetAsync(info, 0, sizeof(int32_t) * 4 * (size_t)batch, (hipStream_t)stream));
   }
 };
@@ -488,14 +450,44 @@ static void make_episodes(WalkEnv &e, const Blob &b, const void *blob, size_t bl
   e.tm.create();
 }
 
+// The handle kinds without the fly's own contacts.  A set of flags belongs to the first kind whose `key` it shows under `key_mask`; it is
+// accepted when, the kind's `switches` aside, it is exactly `bits`, and when the task is there where `task` asks for it.
+constexpr int kForceSwitches = BF_NO_FLUID | BF_NO_DAMPER | BF_NO_SPRING | BF_NO_GRAVITY | BF_NO_ACTUATION;
+constexpr int kSwitches = kForceSwitches | BF_NO_NOSLIP | BF_NO_ADHESION;
+constexpr int kLimitBits = BF_NO_CONTACT | BF_NO_LIMIT | BF_WALK_JOINT_LIMITS;  // all a handle off the floor and without episodes is judged by
+struct WalkKind { int key_mask, key, bits, switches; bool task; const char *bad_flags, *no_task; };
+static const WalkKind kWalkKinds[] = {
+  {BF_WALK_FLOOR | BF_WALK_EPISODES, BF_WALK_FLOOR | BF_WALK_EPISODES, BF_NO_CONTACT | BF_WALK_JOINT_LIMITS | BF_WALK_EPISODES | BF_WALK_FLOOR, kSwitches, true,
+   "ffe_create_walk_physics: FFE_WALK_EPISODES | FFE_WALK_FLOOR (the walk_imitation environment on the floor plane) needs "
+   "FFE_NO_CONTACT | FFE_WALK_JOINT_LIMITS and takes the force switches, FFE_NO_NOSLIP and FFE_NO_ADHESION only: it excludes "
+   "FFE_NO_LIMIT",
+   "ffe_create_walk_physics: FFE_WALK_EPISODES | FFE_WALK_FLOOR needs the task (a null ffe_walk_task pointer); FFE_WALK_FLOOR "
+   "without FFE_WALK_EPISODES is the bare-physics floor handle"},
+  {BF_WALK_FLOOR | BF_WALK_EPISODES, BF_WALK_FLOOR, BF_NO_CONTACT | BF_WALK_JOINT_LIMITS | BF_WALK_FLOOR, kSwitches, false,
+   "ffe_create_walk_physics: FFE_WALK_FLOOR (the floor plane against the fly's sphere and capsule geoms, bare physics) needs "
+   "FFE_NO_CONTACT | FFE_WALK_JOINT_LIMITS and takes the force switches, FFE_NO_NOSLIP and FFE_NO_ADHESION only: it excludes "
+   "FFE_NO_LIMIT and FFE_WALK_EPISODES",
+   nullptr},
+  {BF_WALK_FLOOR | BF_WALK_EPISODES, BF_WALK_EPISODES, BF_NO_CONTACT | BF_WALK_JOINT_LIMITS | BF_WALK_EPISODES, kForceSwitches, true,
+   "ffe_create_walk_physics: FFE_WALK_EPISODES (the walk_imitation environment with the floor off) needs FFE_NO_CONTACT | "
+   "FFE_WALK_JOINT_LIMITS and takes the force switches only: floor contacts are not built yet",
+   "ffe_create_walk_physics: FFE_WALK_EPISODES needs the task (a null ffe_walk_task pointer)"},
+  // without the bit the text is the one the C ABI contract pins; with it the text names the bit
+  {BF_WALK_JOINT_LIMITS, BF_WALK_JOINT_LIMITS, BF_NO_CONTACT | BF_WALK_JOINT_LIMITS, ~kLimitBits, false,
+   "ffe_create_walk_physics: floor contacts and joint limits are not built yet as a step kernel: FFE_WALK_JOINT_LIMITS needs "
+   "FFE_NO_CONTACT and excludes FFE_NO_LIMIT",
+   nullptr},
+  {0, 0, BF_NO_CONTACT | BF_NO_LIMIT, ~kLimitBits, false,
+   "ffe_create_walk_physics: floor contacts and joint limits are not built yet: physics_flags must contain FFE_NO_CONTACT | FFE_NO_LIMIT", nullptr},
+};
+
 std::unique_ptr<ffe::EnvBackend> walk_create(const void *blob, size_t blob_size, const ffe_walk_physics_task &task, int batch, int device) {
   const int physics_flags = task.physics_flags;
   if (!blob || batch <= 0) throw std::runtime_error("ffe_create_walk_physics: bad arguments");
-  const bool limits = (physics_flags & BF_WALK_JOINT_LIMITS) != 0, no_limit = (physics_flags & BF_NO_LIMIT) != 0;
+  const bool limits = (physics_flags & BF_WALK_JOINT_LIMITS) != 0;
   const bool episodes = (physics_flags & BF_WALK_EPISODES) != 0, floor = (physics_flags & BF_WALK_FLOOR) != 0;
   const bool self = (physics_flags & BF_WALK_SELF) != 0, self_env = (physics_flags & BF_WALK_SELF_EPISODES) != 0;
-  if (self || self_env) {
-    const int switches = BF_NO_FLUID | BF_NO_DAMPER | BF_NO_SPRING | BF_NO_GRAVITY | BF_NO_ACTUATION | BF_NO_NOSLIP | BF_NO_ADHESION;
+  if (self || self_env) {  // the fly's own contacts: refusals of their own, which the table does not express
     if (episodes && !floor)
       throw std::runtime_error("ffe_create_walk_physics: FFE_WALK_SELF (the fly's own contacts) with FFE_WALK_EPISODES needs FFE_WALK_FLOOR: the "
                                "walk_imitation environment with the floor off does not carry the fly's own contacts");
@@ -503,7 +495,7 @@ std::unique_ptr<ffe::EnvBackend> walk_create(const void *blob, size_t blob_size,
       throw std::runtime_error("ffe_create_walk_physics: FFE_WALK_SELF (the fly's own contacts) with FFE_WALK_EPISODES needs the task (a null "
                                "ffe_walk_task pointer): a handle without one does not carry the episode protocol; without FFE_WALK_EPISODES the bit "
                                "makes the bare-physics floor handle");
-    if ((physics_flags & ~(switches | BF_WALK_EPISODES | BF_WALK_SELF_EPISODES)) != (BF_NO_CONTACT | BF_WALK_JOINT_LIMITS | BF_WALK_FLOOR | BF_WALK_SELF))
+    if ((physics_flags & ~(kSwitches | BF_WALK_EPISODES | BF_WALK_SELF_EPISODES)) != (BF_NO_CONTACT | BF_WALK_JOINT_LIMITS | BF_WALK_FLOOR | BF_WALK_SELF))
       throw std::runtime_error("ffe_create_walk_physics: FFE_WALK_SELF (the fly's own contacts on the bare-physics floor handle) is accepted only as "
                                "FFE_NO_CONTACT | FFE_WALK_JOINT_LIMITS | FFE_WALK_FLOOR | FFE_WALK_SELF plus the force switches, FFE_NO_NOSLIP and "
                                "FFE_NO_ADHESION, and with FFE_WALK_EPISODES | FFE_WALK_SELF_EPISODES and the task on top of exactly that");
@@ -512,32 +504,11 @@ std::unique_ptr<ffe::EnvBackend> walk_create(const void *blob, size_t blob_size,
       throw std::runtime_error("ffe_create_walk_physics: FFE_WALK_SELF under the environment (FFE_WALK_EPISODES | FFE_WALK_FLOOR and the task) is asked "
                                "for with FFE_WALK_SELF_EPISODES on top: the three bits without it are refused, and so is FFE_WALK_SELF_EPISODES "
                                "without FFE_WALK_EPISODES | FFE_WALK_FLOOR | FFE_WALK_SELF");
-  } else if (floor && episodes) {
-    const int switches = BF_NO_FLUID | BF_NO_DAMPER | BF_NO_SPRING | BF_NO_GRAVITY | BF_NO_ACTUATION | BF_NO_NOSLIP | BF_NO_ADHESION;
-    if ((physics_flags & ~switches) != (BF_NO_CONTACT | BF_WALK_JOINT_LIMITS | BF_WALK_EPISODES | BF_WALK_FLOOR))
-      throw std::runtime_error("ffe_create_walk_physics: FFE_WALK_EPISODES | FFE_WALK_FLOOR (the walk_imitation environment on the floor plane) needs "
-                               "FFE_NO_CONTACT | FFE_WALK_JOINT_LIMITS and takes the force switches, FFE_NO_NOSLIP and FFE_NO_ADHESION only: it excludes "
-                               "FFE_NO_LIMIT");
-    if (!task.task)
-      throw std::runtime_error("ffe_create_walk_physics: FFE_WALK_EPISODES | FFE_WALK_FLOOR needs the task (a null ffe_walk_task pointer); FFE_WALK_FLOOR "
-                               "without FFE_WALK_EPISODES is the bare-physics floor handle");
-  } else if (floor) {
-    const int switches = BF_NO_FLUID | BF_NO_DAMPER | BF_NO_SPRING | BF_NO_GRAVITY | BF_NO_ACTUATION | BF_NO_NOSLIP | BF_NO_ADHESION;
-    if ((physics_flags & ~switches) != (BF_NO_CONTACT | BF_WALK_JOINT_LIMITS | BF_WALK_FLOOR))
-      throw std::runtime_error("ffe_create_walk_physics: FFE_WALK_FLOOR (the floor plane against the fly's sphere and capsule geoms, bare physics) needs "
-                               "FFE_NO_CONTACT | FFE_WALK_JOINT_LIMITS and takes the force switches, FFE_NO_NOSLIP and FFE_NO_ADHESION only: it excludes "
-                               "FFE_NO_LIMIT and FFE_WALK_EPISODES");
-  } else if (episodes) {
-    const int force_switches = BF_NO_FLUID | BF_NO_DAMPER | BF_NO_SPRING | BF_NO_GRAVITY | BF_NO_ACTUATION;
-    if ((physics_flags & ~force_switches) != (BF_NO_CONTACT | BF_WALK_JOINT_LIMITS | BF_WALK_EPISODES))
-      throw std::runtime_error("ffe_create_walk_physics: FFE_WALK_EPISODES (the walk_imitation environment with the floor off) needs FFE_NO_CONTACT | "
-                               "FFE_WALK_JOINT_LIMITS and takes the force switches only: floor contacts are not built yet");
-    if (!task.task) throw std::runtime_error("ffe_create_walk_physics: FFE_WALK_EPISODES needs the task (a null ffe_walk_task pointer)");
-  } else if (!(physics_flags & BF_NO_CONTACT) || limits == no_limit) {
-    // without the new bit the text is the one the C ABI contract pins; with it the text names the bit
-    if (!limits) throw std::runtime_error("ffe_create_walk_physics: floor contacts and joint limits are not built yet: physics_flags must contain FFE_NO_CONTACT | FFE_NO_LIMIT");
-    throw std::runtime_error("ffe_create_walk_physics: floor contacts and joint limits are not built yet as a step kernel: FFE_WALK_JOINT_LIMITS needs "
-                             "FFE_NO_CONTACT and excludes FFE_NO_LIMIT");
+  } else {
+    const WalkKind *kind = kWalkKinds;
+    while ((physics_flags & kind->key_mask) != kind->key) kind++;  // (the last kind's mask is empty: it takes what is left)
+    if ((physics_flags & ~kind->switches) != kind->bits) throw std::runtime_error(kind->bad_flags);
+    if (kind->task && !task.task) throw std::runtime_error(kind->no_task);
   }
   std::unique_ptr<WalkEnv> e(new WalkEnv());  // frees the device allocations made so far if a later step throws
   Blob b(blob, blob_size);

@@ -6,11 +6,11 @@
 // `WTileS`:
 //   front    the action row (NaN -> 0, act_action, canonical / clipped actions) or the reset row (the reference pose, at rest, actuation
 //            disabled);
-//   substep  stage 1, the collision pass (`floor_collide`), stage 2 with `floor_forces` (contact rows first, limit rows after, noslip,
+//   substep  stage 1, the collision pass (`floor_collide`), stage 2 with `contact_forces` (contact rows first, limit rows after, noslip,
 //            adhesion, always from lambda = 0), ten times in registers; a reset row runs stage 1, the collision pass and the
 //            acceleration half of stage 2 once and integrates nothing (mj_forward with contacts on);
 //   qacc     each substep's second arrowhead solve through M's own factor, its root right-hand side carrying the contacts' force on the
-//            root as the Euler solve's does; the accelerometer, and force and touch (`floor_sense`, walk_sense.hpp), are sampled there:
+//            root as the Euler solve's does; the accelerometer, and force and touch (`contact_sense`, walk_sense.hpp), are sampled there:
 //            the state before the integration, this substep's qacc and contact forces;
 //   tail     the 92 physics columns, qpos / qvel for the task layer, the three termination reads, and per env the contacts kept, the
 //            sum of their normal forces and the smallest distance of the last substep.

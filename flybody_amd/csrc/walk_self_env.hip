@@ -7,7 +7,7 @@
 //   collision  `floor_collide`, then `self_prim_collide` (the 48 sphere / capsule geoms against each other) and `self_convex_collide`
 //              (the pairs with an ellipsoid or a cylinder on one side, cvx:: of convex.hpp), both restated from ball_env.hip in the root
 //              frame; the floor's contacts keep the first slots, NC = 16 in all, the deepest are kept beyond that;
-//   rows       `self_forces`: floor cone blocks, one normal row per fly-fly contact over the hinges of two chains (no entry on the
+//   rows       `contact_forces`: floor cone blocks, one normal row per fly-fly contact over the hinges of two chains (no entry on the
 //              root: walk_self.hpp), joint limits; from lambda = 0, the model's noslip sweeps, adhesion shared over all contacts of a body.
 // There is no "no floor in reach" shortcut (the mouth parts touch in every pose) and no state besides WState: a launch's result is a
 // function of (state, act, ctrl) alone; in particular no separating direction is kept from substep to substep.

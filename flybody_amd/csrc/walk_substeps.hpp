@@ -1,5 +1,6 @@
 // walk_substeps.hpp - the device code of the free-root substep that more than one translation unit compiles: the state record, the LDS
-// tiles, the wave's context, stage 1 / stage 2 with the limit and floor constraint blocks, the substep loop and the state export.
+// tiles, the wave's context, stage 1 / stage 2 with the limit block and the one contact block (`contact_forces`: the floor's rows and, on
+// a self tile, the fly's own) and sensor pass (`contact_sense`), the substep loop and the state export.
 // walk_env.hip (the four kernels of bare physics and of the floor-off environment), walk_floor_env.hip (the environment on the floor),
 // walk_self_env.hip (bare physics with the fly's own contacts) and walk_imit_self_env.hip (the environment on the floor with the fly's
 // own contacts) include it; what the code does is described at the head of walk_env.hip and where each part starts.
@@ -19,7 +20,6 @@
 #include "walk_sense.hpp"
 #include "walk_self_sense.hpp"
 #include "walk_self.hpp"
-
 
 namespace ffw {
 using namespace dm;
@@ -46,7 +46,16 @@ constexpr int BF_WALK_SELF_EPISODES = 8192;  // FFE_WALK_SELF_EPISODES: host sid
 constexpr int LCOL = 16;                  // solve columns per block of M: a block has at most NSTEP = 14 hinges, each with one limit row
 static_assert(NSTEP <= LCOL, "a block's limit rows must fit its columns");
 
-struct alignas(16) WTile {
+// What a tile adds to the smooth substep: a tile that derives from another sets its own switches to true, and the shared code reads
+// `Tile::kFloor` ... under `if constexpr`.
+struct TileKind {
+  static constexpr bool kFloor = false;         // the floor's contact tables: the collision pass and the contact block
+  static constexpr bool kSense = false;         // the sensor sums of the environment on the floor
+  static constexpr bool kSelf = false;          // the second chain of a fly-fly contact
+  static constexpr bool kPackedNormal = false;  // a fly-fly slot keeps its normal in floats it leaves unused (WTileSX)
+};
+
+struct alignas(16) WTile : TileKind {
   union {
     struct { float Q[NDP], V[NDP]; };  // joint state staged for the actuators (start of stage 2)
     float4 X4[NDP];                     // right-hand sides / solutions of the block solves
@@ -67,7 +76,7 @@ static_assert(sizeof(WTile) <= 20480, "the tile must leave room for 8 waves per 
 
 // Tile of the limits kernel: WTile without Y (a row lane reads its hinge's Y_m straight from the solve), with the packed G over the
 // two arrays that are dead once stage 1 has factorised (G dies with the substep), and the row tables.
-struct alignas(16) WTileL {
+struct alignas(16) WTileL : TileKind {
   union {
     struct { float Q[NDP], V[NDP]; };
     float4 X4[NDP];
@@ -94,7 +103,7 @@ static_assert(sizeof(WTileL) <= 20480, "the tile must leave room for 8 waves per
 // contacts, KCOL columns per block), the contact tables, and the link poses of the collision pass over the floats of G, which are dead
 // between the factorisation of stage 1 and the G build of stage 2.  What a contact row needs of its geom is read from the model tables
 // through c_geom; the rows' Jacobian entries are evaluated where they are used, as in the tethered kernel.
-struct alignas(16) WTileF {
+struct alignas(16) WTileF : TileKind {
   static constexpr bool kFloor = true;
   union {
     struct { float Q[NDP], V[NDP]; };
@@ -131,10 +140,6 @@ static_assert(sizeof(float[NL][14]) <= sizeof(float[RMAX * (RMAX + 1) / 2]), "th
 // as an instantiation apart (sharing the limits kernel's own instantiation changed that kernel's register allocation).
 struct alignas(16) WTileFar : WTileL {};
 static_assert(sizeof(WTileFar) <= sizeof(WTileF), "the far substep runs inside the floor tile");
-template <class T, class = void>
-struct is_floor_tile : std::false_type {};
-template <class T>
-struct is_floor_tile<T, std::enable_if_t<T::kFloor>> : std::true_type {};
 // what a floor wave carries from stage to stage and reports (per env, in a buffer of the handle)
 struct FloorCtx {
   int nc;          // contacts kept in this substep
@@ -165,10 +170,6 @@ struct alignas(16) WTileS : WTileF {
 constexpr int kSensePark = NL * 14;  // floats into G: behind the link exchange
 static_assert(kSensePark + 3 * 64 <= RMAX * (RMAX + 1) / 2, "the parked right-hand side must fit behind the link exchange");
 static_assert(sizeof(WTileS) <= 20480, "the tile must leave room for 8 waves per CU");
-template <class T, class = void>
-struct is_sense_tile : std::false_type {};
-template <class T>
-struct is_sense_tile<T, std::enable_if_t<T::kSense>> : std::true_type {};
 
 // Tile of the kernel with the fly's own contacts (walk_self_env.hip `floor_self_step`, FFE_WALK_SELF): the
 // floor kernel's, whose contact tables now hold the floor contacts in the first slots and the fly-fly contacts behind them (NC in all).
@@ -191,13 +192,12 @@ struct alignas(16) WTileX : WTileF {
 static_assert(sizeof(WTileX) <= 20480, "the tile must leave room for 8 waves per CU");
 static_assert(2 * NPG <= NDP && NL * 14 + NPG <= RMAX * (RMAX + 1) / 2, "the primitive slots must fit over X4 and the tail of G");
 static_assert((NG + (CL1 * 2 + 15) / 16 + (CL2 * 2 + 15) / 16) <= NDP, "the geom centres and the pair lists must fit over X4");
-template <class T, class = void>
-struct is_self_tile : std::false_type {};
-template <class T>
-struct is_self_tile<T, std::enable_if_t<T::kSelf>> : std::true_type {};
 struct SelfCtx : FloorCtx {
   int ns;          // fly-fly contacts kept in this substep: slots nc .. nc + ns - 1
 };
+struct NoSelf { constexpr operator int() const { return 0; } };  // the fly-fly count of a tile without them: an argument that takes no register
+__device__ __forceinline__ NoSelf self_count(const FloorCtx &) { return {}; }
+__device__ __forceinline__ int self_count(const SelfCtx &fl) { return fl.ns; }
 
 // Tile of the episode kernel on the floor with the fly's own contacts (walk_imit_self_env.hip `imitation_self_step`; DESIGN.md section
 // 12 step 4d): a sense tile and a self tile at once.  WTileF + the sensor part of WTileS (432 B) + the self part of WTileX (304 B) would
@@ -228,14 +228,10 @@ static_assert(sizeof(WTileSX) <= 20480, "the tile must leave room for 8 waves pe
 static_assert(NL * 14 <= kSensePark && kSensePark + 3 * 64 <= RMAX * (RMAX + 1) / 2,
               "the parked right-hand side lies behind the sensor pass's link exchange, inside G");
 static_assert(NPG <= 3 * 64, "the slot radii of the collision pass and the parked right-hand side share the same floats of G, one after the other");
-template <class T, class = void>
-struct is_packed_normal : std::false_type {};
-template <class T>
-struct is_packed_normal<T, std::enable_if_t<T::kPackedNormal>> : std::true_type {};
 // the normal (from geom1's link to geom2's) of fly-fly slot k
 template <class TileX>
 __device__ __forceinline__ void self_nrm(const TileX &T, const int k, float (&n)[3]) {
-  if constexpr (is_packed_normal<TileX>::value) { n[0] = T.c_vel[k][1]; n[1] = T.c_vel[k][2]; n[2] = T.c_mu[k]; }
+  if constexpr (TileX::kPackedNormal) { n[0] = T.c_vel[k][1]; n[1] = T.c_vel[k][2]; n[2] = T.c_mu[k]; }
   else { n[0] = T.c_nrm[k][0]; n[1] = T.c_nrm[k][1]; n[2] = T.c_nrm[k][2]; }
 }
 
@@ -259,6 +255,9 @@ struct ImitCall {
 };
 struct NoEpisode {};  // the bare-physics kernels: no episode code is compiled
 struct FloorCall { FloorRec *rec; };  // the floor kernel (bare physics too): where a wave reports its contacts
+// where a floor wave reports its contacts: the bare-physics call's buffer or the environment's
+__device__ __forceinline__ FloorRec *contact_record(const FloorCall &ep) { return ep.rec; }
+__device__ __forceinline__ FloorRec *contact_record(const ImitCall &ep) { return ep.a->rec; }
 
 template <class Tile>
 struct CtxT {
@@ -282,7 +281,7 @@ struct CtxT {
   I10 Itree;    // spatial inertia of the whole tree about the root origin = M_rr
   S6 Ftot;      // bias force of the whole tree without gravity = -(root rows of the smooth force)
   int overflow; // limits kernel: overflow bits of this launch
-  std::conditional_t<is_self_tile<Tile>::value, SelfCtx, std::conditional_t<is_floor_tile<Tile>::value, FloorCtx, NoEpisode>> fl;
+  std::conditional_t<Tile::kSelf, SelfCtx, std::conditional_t<Tile::kFloor, FloorCtx, NoEpisode>> fl;
 };
 
 // ------------------------------------------------------------------------------------------------ stage 1
@@ -382,6 +381,44 @@ __device__ __forceinline__ void chol6_backward(const float (&Sm)[6][6], const fl
   }
 }
 
+// z = A^-1 f and Y = A^-1 M_jr through the factor (L, dinv) of A - M_jj (Lm, dinv_m) or M_jj + h B (Lh, dinv_h): seven right-hand sides
+// in two four-wide block solves.  `cols`: M_jr's columns of the lane's three slots in registers, or T.F, from which they are read where
+// they are used.  `rows(half)` runs after each solve while X4 holds its solution (half 0: z and Y's angular columns, half 1: Y's linear).
+struct NoRows { __device__ __forceinline__ void operator()(int) const {} };
+__device__ __forceinline__ S6 col6(const S6 (&mrj)[3], int s, int) { return mrj[s]; }
+__device__ __forceinline__ S6 col6(const float (&F)[NDP][6], int, int f) { return ld6(F[f]); }
+template <class C, class Cols, class Rows = NoRows>
+__device__ __forceinline__ void solve_zy(C &c, const float *L, const float *dinv, const float (&f)[3], const Cols &cols, float (&z)[3], S6 (&y)[3],
+                                         Rows &&rows = Rows()) {
+  auto &T = *c.T;
+#pragma unroll
+  for (int s = 0; s < 3; s++) {
+    if (slot_on(c, s)) { const S6 m = col6(cols, s, opq(c.sdof[s])); T.X4[opq(c.sdof[s])] = make_float4(f[s], m.a0, m.a1, m.a2); }
+  }
+  DM_SYNC();
+  solve4(c, L, dinv);
+#pragma unroll
+  for (int s = 0; s < 3; s++) {
+    const float4 x = slot_on(c, s) ? T.X4[opq(c.sdof[s])] : make_float4(0.f, 0.f, 0.f, 0.f);
+    z[s] = x.x; y[s].a0 = x.y; y[s].a1 = x.z; y[s].a2 = x.w;
+  }
+  rows(0);
+  DM_SYNC();
+#pragma unroll
+  for (int s = 0; s < 3; s++) {
+    if (slot_on(c, s)) { const S6 m = col6(cols, s, opq(c.sdof[s])); T.X4[opq(c.sdof[s])] = make_float4(m.l0, m.l1, m.l2, 0.f); }
+  }
+  DM_SYNC();
+  solve4(c, L, dinv);
+#pragma unroll
+  for (int s = 0; s < 3; s++) {
+    const float4 x = slot_on(c, s) ? T.X4[opq(c.sdof[s])] : make_float4(0.f, 0.f, 0.f, 0.f);
+    y[s].l0 = x.x; y[s].l1 = x.y; y[s].l2 = x.z;
+  }
+  rows(1);
+  DM_SYNC();
+}
+
 // ------------------------------------------------------------------------------------------------ joint-limit rows
 // The constraint block of a substep with R > 0 limit rows (rows already in T.r_sgn / r_D / r_dof / r_blk, -aref in T.r_y0): adds the
 // hinges' constraint forces to `qs`.  Returns the solver's iterations.
@@ -393,29 +430,13 @@ __device__ __forceinline__ int limit_forces(C &c, const int R, const int (&lrow)
   // ---- z_m = M_jj^-1 f_j and Y_m = M_jj^-1 M_jr through M's own factor; a row lane keeps its hinge's Y_m
   S6 ym[3], yr = zero6();
   float zm[3];
-#pragma unroll
-  for (int s = 0; s < 3; s++) if (slot_on(c, s)) T.X4[opq(c.sdof[s])] = make_float4(qs[s], mrj[s].a0, mrj[s].a1, mrj[s].a2);
-  DM_SYNC();
-  solve4(c, T.Lm, T.dinv_m);
-#pragma unroll
-  for (int s = 0; s < 3; s++) {
-    const float4 x = slot_on(c, s) ? T.X4[opq(c.sdof[s])] : make_float4(0.f, 0.f, 0.f, 0.f);
-    zm[s] = x.x; ym[s].a0 = x.y; ym[s].a1 = x.z; ym[s].a2 = x.w;
-  }
-  const int rdof = row ? (int)T.r_dof[lane] : 0;
-  if (row) { const float4 x = T.X4[rdof]; yr.a0 = x.y; yr.a1 = x.z; yr.a2 = x.w; }
-  DM_SYNC();
-#pragma unroll
-  for (int s = 0; s < 3; s++) if (slot_on(c, s)) T.X4[opq(c.sdof[s])] = make_float4(mrj[s].l0, mrj[s].l1, mrj[s].l2, 0.f);
-  DM_SYNC();
-  solve4(c, T.Lm, T.dinv_m);
-#pragma unroll
-  for (int s = 0; s < 3; s++) {
-    const float4 x = slot_on(c, s) ? T.X4[opq(c.sdof[s])] : make_float4(0.f, 0.f, 0.f, 0.f);
-    ym[s].l0 = x.x; ym[s].l1 = x.y; ym[s].l2 = x.z;
-  }
-  if (row) { const float4 x = T.X4[rdof]; yr.l0 = x.x; yr.l1 = x.y; yr.l2 = x.z; }
-  DM_SYNC();
+  int rdof = 0;
+  solve_zy(c, T.Lm, T.dinv_m, qs, mrj, zm, ym, [&](int half) {
+    if (half == 0) {
+      rdof = row ? (int)T.r_dof[lane] : 0;
+      if (row) { const float4 x = T.X4[rdof]; yr.a0 = x.y; yr.a1 = x.z; yr.a2 = x.w; }
+    } else if (row) { const float4 x = T.X4[rdof]; yr.l0 = x.x; yr.l1 = x.y; yr.l2 = x.z; }
+  });
   // ---- S_m = L L', x_r = S_m^-1 (b_r - M_rj z_m), the hinges' smooth acceleration a_s = z_m - Y_m x_r (gravity: zero on the hinges)
   float Sm[6][6], br[6], id[6], xr[6];
   schur(c, mrj, ym, zm, Sm, br);
@@ -614,272 +635,6 @@ __device__ __forceinline__ void floor_frame(const C &c, float (&fr)[9]) {
 // times closer (with FFE_NO_NOSLIP, where no sweep polishes the tangential forces, the one-substep error of root_ang was 3.6e-4 at 1).
 constexpr float kFloorScale = 1e-2f;
 
-// The constraint block of a floor substep with R > 0 rows: 3 per contact (rows 0 .. 3 nc - 1: the cone blocks come first), then the
-// instantiated joint limits (already in T.r_sgn / r_D / r_dof / r_blk, -aref in T.r_y0).  ball_env.hip's stage 2 with the ball's
-// rank-3 term replaced by the root's rank-6 term:
-//   G = J_j M_jj^-1 J_j' + w S_m^-1 w',  w = J_r - J_j Y_m  (J_r = (p x e, e) on a contact row, 0 on a limit row)
-// and the three root terms a limit row never needed: the adhesion pull enters the smooth force of hinges and root before y0 is formed;
-// y0 carries the root's share of J qacc_smooth with w_b x v_b and gravity added by hand (they are outside the arrowhead solve);
-// J_r' f joins the root's right-hand side of the Euler solve (c.fl.rootf) and J_j' f the hinges' (qs).  Returns the solver's iterations.
-template <class C>
-__device__ __forceinline__ int floor_forces(C &c, const int R, const int (&lrow)[3], const float (&lsgn)[3], float (&qs)[3]) {
-  WTileF &T = *c.T;
-  const BallModel FFE_GLOBAL &M = model(c);
-  const WalkExtra FFE_GLOBAL &X = *c.X;
-  const int lane = c.lane, nc = c.fl.nc, nrc = 3 * nc;
-  const bool row = lane < R, crow = lane < nrc;
-  float er[3] = {0.f, 0.f, 0.f};  // this row's direction (a contact row's normal or tangent)
-  {
-  float fr[9];
-  floor_frame(c, fr);
-  if (crow) { const int r3 = 3 * (lane - 3 * (lane / 3)); er[0] = fr[r3]; er[1] = fr[r3 + 1]; er[2] = fr[r3 + 2]; }
-  // ---- per contact: impedance, D, friction, -aref on its three rows, and the adhesion pull (mj: mj_transmission mjTRN_BODY: -force
-  //      along the normal row, the mean over the body's contacts, the ones inside the gap included)
-  if (lane < nc) {
-    const int g = T.c_geom[lane];
-    const float dist = T.c_dist[lane], incl = X.f_margin[g] - X.f_gap[g];
-    float si_[5];
-#pragma unroll
-    for (int q2 = 0; q2 < 5; q2++) si_[q2] = X.f_solimp[q2];
-    const float imp = impedance(si_, fabsf(dist - incl));
-    const float R0 = fmaxf(1e-15f, (1.f - imp) * X.f_invw[g] * frcp(imp));
-    T.c_D[lane] = T.c_excl[lane] ? 0.f : frcp(R0);
-    T.c_mu[lane] = X.f_fric[g];
-    const float B = X.f_B[g], K = X.f_K[g];
-    T.r_y0[3 * lane] = B * wf::dot3<float>(&fr[0], T.c_vel[lane]) + K * imp * (dist - incl);
-    T.r_y0[3 * lane + 1] = B * wf::dot3<float>(&fr[3], T.c_vel[lane]);
-    T.r_y0[3 * lane + 2] = B * wf::dot3<float>(&fr[6], T.c_vel[lane]);
-    const int adh = X.f_adh[g];
-    int cnt = 0;
-    for (int j = 0; j < nc; j++) cnt += T.c_link[j] == T.c_link[lane] ? 1 : 0;
-    T.c_w[lane] = adh >= 0 ? -T.frc[adh] / (float)cnt : 0.f;
-  }
-  if (lane < RMAX) T.r_lam[lane] = 0.f;  // no warm start: a substep's result depends on its state alone
-  if (crow) T.r_blk[lane] = T.c_blk[lane / 3];
-  for (int k = lane; k < NBLK * KCOL; k += 64) (&T.rowof[0][0])[k] = 255;
-  DM_SYNC();
-  // ---- adhesion into the smooth forces of the hinges and of the root
-  {
-    float fa[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    for (int k = 0; k < nc; k++) {
-      float jr[6];
-      wf::row_root<float>(T.c_pos[k], &fr[0], jr);
-#pragma unroll
-      for (int a = 0; a < 6; a++) fa[a] += jr[a] * T.c_w[k];
-    }
-    if (lane == 0) {
-#pragma unroll
-      for (int a = 0; a < 6; a++) T.rootf[a] = fa[a];
-    }
-  }
-#pragma unroll
-  for (int s = 0; s < 3; s++) if (slot_on(c, s)) qs[s] += floor_gather<true>(T, M, fr, nc, opq(c.sdof[s]), T.c_w);
-  }
-  // ---- columns: a row's column is its rank among the rows of its block (ball_env.hip); more than KCOL rows in a block: flagged, and
-  //      the rows without a column are switched off for this substep
-  const int myb = row ? (int)T.r_blk[lane] : -1;
-  int ncol;
-  {
-    int mycol = 0;
-    for (int b = 0; b < NBLK; b++) {
-      const unsigned long long mb = __ballot(myb == b);
-      if (myb == b) mycol = __popcll(mb & ((1ull << lane) - 1ull));
-    }
-    if (row) {
-      T.r_col[lane] = (unsigned char)mycol;
-      if (mycol < KCOL) T.rowof[myb][mycol] = (unsigned char)lane;
-      mycol += 1;
-    }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) mycol = max(mycol, __shfl_xor(mycol, off));
-    ncol = min(mycol, KCOL);
-    if (mycol > KCOL) {
-      c.overflow |= 4;
-      DM_SYNC();
-      if (row && (int)T.r_col[lane] >= KCOL) { if (crow) T.c_excl[lane / 3] = 1; else T.r_D[lane] = 0.f; }
-      DM_SYNC();
-      if (lane < nc && T.c_excl[lane]) T.c_D[lane] = 0.f;
-    }
-  }
-  DM_SYNC();
-  const int mycol = row ? (int)T.r_col[lane] : 0;
-  // this row: its point, its direction, its root Jacobian; a limit row's hinge
-  const int ck = crow ? lane / 3 : 0, cr = crow ? lane - 3 * (lane / 3) : 0;
-  const int clink = crow ? (int)T.c_link[ck] : 0, cnch = crow ? M.l_nchain[clink] : 0;
-  const int rdof = (row && !crow) ? (int)T.r_dof[lane] : 0;
-  const float sg = (row && !crow) ? T.r_sgn[lane] : 0.f;
-  // ---- z_m = M_jj^-1 f_j and Y_m = M_jj^-1 M_jr through M's own factor; a row lane keeps J_j z_m and J_j Y_m of its row
-  S6 ym[3];
-  float zm[3], jz = 0.f, jy[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-  for (int s = 0; s < 3; s++) if (slot_on(c, s)) { const float *m6 = T.F[opq(c.sdof[s])]; T.X4[opq(c.sdof[s])] = make_float4(qs[s], m6[0], m6[1], m6[2]); }
-  DM_SYNC();
-  solve4(c, T.Lm, T.dinv_m);
-#pragma unroll
-  for (int s = 0; s < 3; s++) {
-    const float4 x = slot_on(c, s) ? T.X4[opq(c.sdof[s])] : make_float4(0.f, 0.f, 0.f, 0.f);
-    zm[s] = x.x; ym[s].a0 = x.y; ym[s].a1 = x.z; ym[s].a2 = x.w;
-  }
-  if (crow) {
-    for (int p = 0; p < cnch; p++) {
-      const int f = M.l_chain[p][clink];
-      const float jv = fj_row(T, er, ck, f);
-      const float4 x = T.X4[f];
-      jz += jv * x.x; jy[0] += jv * x.y; jy[1] += jv * x.z; jy[2] += jv * x.w;
-    }
-  } else if (row) { const float4 x = T.X4[rdof]; jz = sg * x.x; jy[0] = sg * x.y; jy[1] = sg * x.z; jy[2] = sg * x.w; }
-  DM_SYNC();
-#pragma unroll
-  for (int s = 0; s < 3; s++) if (slot_on(c, s)) { const float *m6 = T.F[opq(c.sdof[s])]; T.X4[opq(c.sdof[s])] = make_float4(m6[3], m6[4], m6[5], 0.f); }
-  DM_SYNC();
-  solve4(c, T.Lm, T.dinv_m);
-#pragma unroll
-  for (int s = 0; s < 3; s++) {
-    const float4 x = slot_on(c, s) ? T.X4[opq(c.sdof[s])] : make_float4(0.f, 0.f, 0.f, 0.f);
-    ym[s].l0 = x.x; ym[s].l1 = x.y; ym[s].l2 = x.z;
-  }
-  if (crow) {
-    for (int p = 0; p < cnch; p++) {
-      const int f = M.l_chain[p][clink];
-      const float jv = fj_row(T, er, ck, f);
-      const float4 x = T.X4[f];
-      jy[3] += jv * x.x; jy[4] += jv * x.y; jy[5] += jv * x.z;
-    }
-  } else if (row) { const float4 x = T.X4[rdof]; jy[3] = sg * x.x; jy[4] = sg * x.y; jy[5] = sg * x.z; }
-  DM_SYNC();
-  // ---- S_m = L L', x_r = S_m^-1 (b_r + adhesion - M_rj z_m); qfrc_smooth . qacc_smooth for the solver's stopping test
-  float Sm[6][6], br[6], id[6], xr[6];
-  {
-    S6 m6[3];
-#pragma unroll
-    for (int s = 0; s < 3; s++) m6[s] = slot_on(c, s) ? ld6(T.F[opq(c.sdof[s])]) : zero6();
-    schur(c, m6, ym, zm, Sm, br);
-  }
-#pragma unroll
-  for (int k = 0; k < 6; k++) br[k] += T.rootf[k];
-  chol6(Sm, id);
-  chol6_forward(Sm, id, br, xr);
-  chol6_backward(Sm, id, xr);
-  float sq = 0.f;
-#pragma unroll
-  for (int s = 0; s < 3; s++) {
-    if (slot_on(c, s)) {
-      float a = zm[s];
-#pragma unroll
-      for (int k = 0; k < 6; k++) a -= comp(ym[s], k) * xr[k];
-      sq += qs[s] * a;
-    }
-  }
-  float scale2 = wave_sum(sq);
-#pragma unroll
-  for (int k = 0; k < 6; k++) scale2 += br[k] * xr[k];
-  scale2 *= kFloorScale;
-  // ---- y0 = J qacc_smooth - aref: the hinges' share J_j (z_m - Y_m x_r), the root's share with w_b x v_b and gravity by hand
-  if (row) {
-    float y = jz;
-#pragma unroll
-    for (int k = 0; k < 6; k++) y -= jy[k] * xr[k];
-    if (crow) {
-      const M3 Rr = q2m(c.rq);
-      const V3 g3 = (c.flags & BF_NO_GRAVITY) ? V3{0.f, 0.f, 0.f} : mtv(Rr, V3{0.f, 0.f, M.gz});
-      const float wb[3] = {c.V0.a0, c.V0.a1, c.V0.a2}, vb[3] = {c.V0.l0, c.V0.l1, c.V0.l2}, gb[3] = {g3.x, g3.y, g3.z};
-      float jr[6];
-      wf::row_root<float>(T.c_pos[ck], er, jr);
-      y += wf::root_y0<float>(jr, xr, wb, vb, gb);
-    }
-    T.r_y0[lane] += y;
-  }
-  // ---- the rank-6 part of G: u = L^-1 (J_r - J_j Y_m), G_ik = u_i . u_k
-  const int gtri = lane * (lane + 1) / 2;  // G is symmetric: row `lane` keeps its columns r2 <= lane
-  {
-    float u[6], jr[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    if (crow) wf::row_root<float>(T.c_pos[ck], er, jr);
-    wf::rank6_factor<float>(Sm, id, jr, jy, u);
-    for (int r2 = 0; r2 < R; r2++) {
-      float gv = 0.f;
-#pragma unroll
-      for (int k = 0; k < 6; k++) gv += u[k] * rl_f(u[k], r2);
-      if (row && r2 <= lane) T.G[gtri + r2] = gv;
-    }
-  }
-  // ---- the block part J_j M_jj^-1 J_j': four columns per block solve, rows of different blocks sharing a column
-#pragma unroll 1
-  for (int cb = 0; cb < ncol; cb += 4) {
-    for (int f = lane; f < ND; f += 64) T.X4[f] = make_float4(0.f, 0.f, 0.f, 0.f);
-    DM_SYNC();
-    {
-      const int col = mycol - cb;
-      if (row && col >= 0 && col < 4) {
-        if (crow) { for (int p = 0; p < cnch; p++) { const int f = M.l_chain[p][clink]; (&T.X4[f].x)[col] = fj_row(T, er, ck, f); } }
-        else (&T.X4[rdof].x)[col] = sg;
-      }
-    }
-    DM_SYNC();
-    solve4(c, T.Lm, T.dinv_m);
-    if (row) {
-      float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
-      if (crow) {
-        for (int p = 0; p < cnch; p++) {
-          const int f = M.l_chain[p][clink];
-          const float jv = fj_row(T, er, ck, f);
-          const float4 y = T.X4[f];
-          acc.x += jv * y.x; acc.y += jv * y.y; acc.z += jv * y.z; acc.w += jv * y.w;
-        }
-      } else { const float4 y = T.X4[rdof]; acc = make_float4(sg * y.x, sg * y.y, sg * y.z, sg * y.w); }
-#pragma unroll
-      for (int q2 = 0; q2 < 4; q2++) {
-        const float av = q2 == 0 ? acc.x : (q2 == 1 ? acc.y : (q2 == 2 ? acc.z : acc.w));
-        const int r2 = cb + q2 < KCOL ? (int)T.rowof[myb][cb + q2] : 255;
-        if (r2 <= lane) T.G[gtri + r2] += av;  // (255 = no such row)
-      }
-    }
-    DM_SYNC();
-  }
-  // ---- solve: contact blocks first, limit rows after them, the model's noslip sweeps
-  int nact = 0;
-  for (int k = 0; k < nc; k++) nact += T.c_excl[k] ? 0 : 1;
-  const int nslip = (nact > 0 && !(c.flags & BF_NO_NOSLIP)) ? M.noslip_iterations : 0;
-  ModelPtr mp_ = (ModelPtr)c.M;
-  int iters;
-  if (R <= 12) iters = row_newton<12, ConeRows>(c.T, mp_, lane, R, nrc, scale2, nslip, 0);
-  else if (R <= 18) iters = row_newton<18, ConeRows>(c.T, mp_, lane, R, nrc, scale2, nslip, 0);
-  else if (R <= 24) iters = row_newton<24, ConeRows>(c.T, mp_, lane, R, nrc, scale2, nslip, 0);
-  else if (R <= 32) iters = row_newton<32, ConeRows>(c.T, mp_, lane, R, nrc, scale2, nslip, 0);
-  else iters = row_newton<RMAX, ConeRows>(c.T, mp_, lane, R, nrc, scale2, nslip, 0);
-  // ---- qfrc_constraint: J_j' f on the hinges, J_r' f (and the adhesion pull) on the root
-  float fr[9];
-  floor_frame(c, fr);
-  {
-    float fsum = 0.f, fa[6];
-#pragma unroll
-    for (int a = 0; a < 6; a++) fa[a] = T.rootf[a];
-    for (int k = 0; k < nc; k++) {
-      fsum += T.r_f[3 * k];
-#pragma unroll
-      for (int r = 0; r < 3; r++) {
-        float j6[6];
-        wf::row_root<float>(T.c_pos[k], &fr[3 * r], j6);
-        const float f = T.r_f[3 * k + r];
-#pragma unroll
-        for (int a = 0; a < 6; a++) fa[a] += j6[a] * f;
-      }
-    }
-    DM_SYNC();
-    if (lane == 0) {
-#pragma unroll
-      for (int a = 0; a < 6; a++) T.rootf[a] = fa[a];
-      T.rootf[6] = fsum;
-    }
-  }
-#pragma unroll
-  for (int s = 0; s < 3; s++) {
-    if (slot_on(c, s)) qs[s] += floor_gather<false>(T, M, fr, nc, opq(c.sdof[s]), T.r_f);
-    if (lrow[s] >= 0) qs[s] += lsgn[s] * T.r_f[lrow[s]];
-  }
-  DM_SYNC();
-  return iters;
-}
-
 // ------------------------------------------------------------------------------------------------ the fly's own contacts
 // (FFE_WALK_SELF)  ball_env.hip's `self_collide` and `convex_collide` restated on the walker's tile, in
 // the root frame: the geoms' frames come from the link poses `floor_collide` has published (T.lp), the narrow phase of the convex pairs
@@ -902,11 +657,11 @@ __device__ __forceinline__ void self_put(TileX &T, const BallModel FFE_GLOBAL &M
   const float imp = impedance(si_, fabsf(dist - incl));
   const bool excl = dist >= incl;  // inside the margin but not inside margin - gap: kept (an adhesion actuator counts it), exerts nothing
   T.c_pos[at][0] = p.x; T.c_pos[at][1] = p.y; T.c_pos[at][2] = p.z;
-  if constexpr (!is_packed_normal<TileX>::value) { T.c_nrm[at][0] = n.x; T.c_nrm[at][1] = n.y; T.c_nrm[at][2] = n.z; }
+  if constexpr (!TileX::kPackedNormal) { T.c_nrm[at][0] = n.x; T.c_nrm[at][1] = n.y; T.c_nrm[at][2] = n.z; }
   T.c_dist[at] = dist; T.c_excl[at] = excl ? 1 : 0;
   T.c_D[at] = excl ? 0.f : wsf::row_D<float>(imp, invw);
   T.c_vel[at][0] = wsf::row_neg_aref<float>(M.sc_K, M.sc_B, imp, dist, incl, vel);
-  if constexpr (is_packed_normal<TileX>::value) { T.c_vel[at][1] = n.x; T.c_vel[at][2] = n.y; T.c_mu[at] = n.z; }  // (the floats such a slot leaves unused)
+  if constexpr (TileX::kPackedNormal) { T.c_vel[at][1] = n.x; T.c_vel[at][2] = n.y; T.c_mu[at] = n.z; }  // (the floats such a slot leaves unused)
   else { T.c_vel[at][1] = 0.f; T.c_vel[at][2] = 0.f; T.c_mu[at] = 0.f; }
   T.c_geom[at] = 0;
   const int fp = M.l_chain[M.l_nchain[lpos] - 1][lpos];
@@ -1152,40 +907,54 @@ __device__ __forceinline__ float self_gather(const TileX &T, const BallModel FFE
     const bool on_pos = (int)T.c_blk[k] == blk && (((unsigned)T.c_amask[k] >> li) & 1u);
     const bool on_neg = (int)T.c_blk1[k] == blk && (((unsigned)T.c_amask1[k] >> li) & 1u);
     if (on_pos != on_neg) {
-      if constexpr (is_packed_normal<TileX>::value) { float n[3]; self_nrm(T, k, n); acc += wsf::row_hinge<float>(T.C[f], T.c_pos[k], n, on_pos, on_neg) * w[j]; }
+      if constexpr (TileX::kPackedNormal) { float n[3]; self_nrm(T, k, n); acc += wsf::row_hinge<float>(T.C[f], T.c_pos[k], n, on_pos, on_neg) * w[j]; }
       else acc += wsf::row_hinge<float>(T.C[f], T.c_pos[k], T.c_nrm[k], on_pos, on_neg) * w[j];
     }
   }
   return acc;
 }
 
-// The constraint block of a substep with the fly's own contacts: `floor_forces` with one more kind of row between the floor's cone blocks
-// and the joint limits - rows 0 .. 3 nc - 1 the floor contacts, then one normal row per fly-fly contact, then the limits (the oracle
-// lists limits first and the contacts in pair order; the solution of the convex problem does not depend on the order of its rows).  A
-// fly-fly row is a scalar row of the solver, like a limit row, over the hinges of two chains (walk_self.hpp): no entry on the root, so
-//   w = -J_j Y_m in the rank-6 term, no w_b x v_b / gravity term in y0, nothing on the root's right-hand side.
-// Its two chains may lie in two blocks of M: it then owns a column in each.  The adhesion pull of a body is the mean over all of its
-// contacts, fly-fly ones included (mjTRN_BODY).  Returns the solver's iterations.
+// ------------------------------------------------------------------------------------------------ the contact block
+// The constraint block of a floor substep with R > 0 rows: 3 per floor contact (rows 0 .. 3 nc - 1: the cone blocks come first), on a
+// self tile one normal row per fly-fly contact, then the instantiated joint limits (already in T.r_sgn / r_D / r_dof / r_blk, -aref in
+// T.r_y0; the oracle lists limits first and the contacts in pair order: the solution of the convex problem does not depend on the order
+// of its rows).  ball_env.hip's stage 2 with the ball's rank-3 term replaced by the root's rank-6 term:
+//   G = J_j M_jj^-1 J_j' + w S_m^-1 w',  w = J_r - J_j Y_m  (J_r = (p x e, e) on a floor row, 0 on a fly-fly or a limit row)
+// and the three root terms a limit row never needed: the adhesion pull enters the smooth force of hinges and root before y0 is formed;
+// y0 carries the root's share of J qacc_smooth with w_b x v_b and gravity added by hand (they are outside the arrowhead solve);
+// J_r' f joins the root's right-hand side of the Euler solve (T.rootf) and J_j' f the hinges' (qs).
+// Everything a fly-fly row adds sits under SELF.  It is a scalar row of the solver, like a limit row, over the hinges of two chains
+// (walk_self.hpp) with no entry on the root: w = -J_j Y_m in the rank-6 term, no w_b x v_b / gravity term in y0, nothing on the root's
+// right-hand side.  Its two chains may lie in two blocks of M: it then owns a column in each.  The adhesion pull of a body is the mean
+// over all of its contacts, fly-fly ones included (mjTRN_BODY).  Where the two kinds of tile form the same number in two ways (seeding a
+// column of G, y0, the hinges' gather), each keeps its own: the ways differ in the sign of a zero, and the floor tiles' single chain loop
+// with a single accumulator is what holds the floor kernels' register figures.  Returns the solver's iterations.
 template <class C>
-__device__ __forceinline__ int self_forces(C &c, const int R, const int (&lrow)[3], const float (&lsgn)[3], float (&qs)[3]) {
-  auto &T = *c.T;  // (WTileX, or the environment's WTileSX)
-  using TileX = std::remove_reference_t<decltype(T)>;
+__device__ __forceinline__ int contact_forces(C &c, const int R, const int (&lrow)[3], const float (&lsgn)[3], float (&qs)[3]) {
+  using Tile = std::remove_pointer_t<decltype(c.T)>;
+  constexpr bool SELF = Tile::kSelf;
+  std::conditional_t<SELF, Tile, WTileF> &T = *c.T;  // (WTileX, or the environment's WTileSX; the floor tiles through their base)
   const BallModel FFE_GLOBAL &M = model(c);
   const WalkExtra FFE_GLOBAL &X = *c.X;
-  const int lane = c.lane, nc = c.fl.nc, ns = c.fl.ns, nrc = 3 * nc, nrs = nrc + ns, ncs = nc + ns;
-  const bool row = lane < R, crow = lane < nrc, srow = lane >= nrc && lane < nrs, jrow = lane < nrs;
+  const int lane = c.lane, nc = c.fl.nc, nrc = 3 * nc;
+  const int ns = self_count(c.fl), nrs = nrc + ns, ncs = nc + ns;
+  const bool row = lane < R, crow = lane < nrc, srow = SELF && lane >= nrc && lane < nrs, jrow = SELF ? lane < nrs : crow;
   float er[3] = {0.f, 0.f, 0.f};  // this row's direction: a floor row's normal or tangent, a fly-fly row's normal
-  // contacts of link `l`, on either side
-  auto contacts_of = [&](int l) { int n = 0; for (int j = 0; j < ncs; j++) n += ((int)T.c_link[j] == l || (int)T.c_link1[j] == l) ? 1 : 0; return n; };
+  // contacts of link `l`: of a fly-fly contact on either side
+  auto contacts_of = [&](int l) {
+    int n = 0;
+    if constexpr (SELF) { for (int j = 0; j < ncs; j++) n += ((int)T.c_link[j] == l || (int)T.c_link1[j] == l) ? 1 : 0; }
+    else { for (int j = 0; j < nc; j++) n += T.c_link[j] == l ? 1 : 0; }
+    return n;
+  };
   {
   float fr[9];
   floor_frame(c, fr);
   if (crow) { const int r3 = 3 * (lane - 3 * (lane / 3)); er[0] = fr[r3]; er[1] = fr[r3 + 1]; er[2] = fr[r3 + 2]; }
-  if (srow) {
-    if constexpr (is_packed_normal<TileX>::value) self_nrm(T, nc + lane - nrc, er);
-    else { const float *n = T.c_nrm[nc + lane - nrc]; er[0] = n[0]; er[1] = n[1]; er[2] = n[2]; }
-  }
-  if (lane < nc) {  // a floor contact: as floor_forces, the adhesion pull shared with the body's fly-fly contacts
+  if constexpr (SELF) { if (srow) self_nrm(T, nc + lane - nrc, er); }
+  // ---- per floor contact: impedance, D, friction, -aref on its three rows, and the adhesion pull (mj: mj_transmission mjTRN_BODY: -force
+  //      along the normal row, the mean over the body's contacts, the ones inside the gap included)
+  if (lane < nc) {
     const int g = T.c_geom[lane];
     const float dist = T.c_dist[lane], incl = X.f_margin[g] - X.f_gap[g];
     float si_[5];
@@ -1200,15 +969,19 @@ __device__ __forceinline__ int self_forces(C &c, const int R, const int (&lrow)[
     T.r_y0[3 * lane + 1] = B * wf::dot3<float>(&fr[3], T.c_vel[lane]);
     T.r_y0[3 * lane + 2] = B * wf::dot3<float>(&fr[6], T.c_vel[lane]);
     const int adh = X.f_adh[g];
-    T.c_w[lane] = adh >= 0 ? -T.frc[adh] / (float)contacts_of(T.c_link[lane]) : 0.f;
-  } else if (lane < ncs) {  // a fly-fly contact: D and -aref are the collision pass's; the pull of both bodies' adhesion actuators
-    const int ri = nrc + lane - nc, lp_ = T.c_link[lane], ln_ = T.c_link1[lane];
-    T.r_y0[ri] = T.c_vel[lane][0]; T.r_D[ri] = T.c_D[lane]; T.r_sgn[ri] = 0.f; T.r_dof[ri] = 0;
-    float w = 0.f;
-    const int ap = M.l_adh[lp_], an = ln_ != 255 ? M.l_adh[ln_] : -1;
-    if (ap >= 0) w -= T.frc[ap] / (float)contacts_of(lp_);
-    if (an >= 0) w -= T.frc[an] / (float)contacts_of(ln_);
-    T.c_w[lane] = w;
+    const int cnt = contacts_of(T.c_link[lane]);
+    T.c_w[lane] = adh >= 0 ? -T.frc[adh] / (float)cnt : 0.f;
+  }
+  if constexpr (SELF) {
+    if (lane >= nc && lane < ncs) {  // a fly-fly contact: D and -aref are the collision pass's; the pull of both bodies' adhesion actuators
+      const int ri = nrc + lane - nc, lp_ = T.c_link[lane], ln_ = T.c_link1[lane];
+      T.r_y0[ri] = T.c_vel[lane][0]; T.r_D[ri] = T.c_D[lane]; T.r_sgn[ri] = 0.f; T.r_dof[ri] = 0;
+      float w = 0.f;
+      const int ap = M.l_adh[lp_], an = ln_ != 255 ? M.l_adh[ln_] : -1;
+      if (ap >= 0) w -= T.frc[ap] / (float)contacts_of(lp_);
+      if (an >= 0) w -= T.frc[an] / (float)contacts_of(ln_);
+      T.c_w[lane] = w;
+    }
   }
   if (lane < RMAX) T.r_lam[lane] = 0.f;  // no warm start: a substep's result depends on its state alone
   if (crow) T.r_blk[lane] = T.c_blk[lane / 3];
@@ -1230,29 +1003,37 @@ __device__ __forceinline__ int self_forces(C &c, const int R, const int (&lrow)[
     }
   }
 #pragma unroll
-  for (int s = 0; s < 3; s++)
-    if (slot_on(c, s)) qs[s] += floor_gather<true>(T, M, fr, nc, opq(c.sdof[s]), T.c_w) + self_gather(T, M, nc, ns, opq(c.sdof[s]), &T.c_w[nc]);
+  for (int s = 0; s < 3; s++) {
+    if (slot_on(c, s)) {
+      if constexpr (SELF) qs[s] += floor_gather<true>(T, M, fr, nc, opq(c.sdof[s]), T.c_w) + self_gather(T, M, nc, ns, opq(c.sdof[s]), &T.c_w[nc]);
+      else qs[s] += floor_gather<true>(T, M, fr, nc, opq(c.sdof[s]), T.c_w);
+    }
+  }
   }
   // ---- columns: a row's column is its rank among the rows of its block; a fly-fly row whose chains sit in two blocks takes a column
   //      in each (ball_env.hip).  More than KCOL rows in a block: flagged, the rows without a column are switched off for this substep
   const int myb = row ? (int)T.r_blk[lane] : -1;
   int myb2 = -1;
-  if (srow) { const int b1 = T.c_blk1[nc + lane - nrc]; if (b1 != 255 && b1 != myb) myb2 = b1; }
+  if constexpr (SELF) { if (srow) { const int b1 = T.c_blk1[nc + lane - nrc]; if (b1 != 255 && b1 != myb) myb2 = b1; } }
   int ncol, mycol2 = 0;
   {
     int mycol = 0;
     for (int b = 0; b < NBLK; b++) {
-      const unsigned long long mb = __ballot(myb == b || myb2 == b);
+      const unsigned long long mb = __ballot(myb == b || (SELF && myb2 == b));
       if (myb == b) mycol = __popcll(mb & ((1ull << lane) - 1ull));
-      if (myb2 == b) mycol2 = __popcll(mb & ((1ull << lane) - 1ull));
+      if constexpr (SELF) { if (myb2 == b) mycol2 = __popcll(mb & ((1ull << lane) - 1ull)); }
     }
     if (row) {
       T.r_col[lane] = (unsigned char)mycol;
       if (mycol < KCOL) T.rowof[myb][mycol] = (unsigned char)lane;
-      if (myb2 >= 0 && mycol2 < KCOL) T.rowof[myb2][mycol2] = (unsigned char)lane;
-      if (myb2 < 0) mycol2 = mycol;
-      if (srow) T.c_col1[nc + lane - nrc] = (unsigned char)mycol2;
-      mycol = max(mycol, mycol2) + 1;
+      if constexpr (SELF) {
+        if (myb2 >= 0 && mycol2 < KCOL) T.rowof[myb2][mycol2] = (unsigned char)lane;
+        if (myb2 < 0) mycol2 = mycol;
+        if (srow) T.c_col1[nc + lane - nrc] = (unsigned char)mycol2;
+        mycol = max(mycol, mycol2) + 1;
+      } else {
+        mycol += 1;
+      }
     }
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) mycol = max(mycol, __shfl_xor(mycol, off));
@@ -1260,51 +1041,37 @@ __device__ __forceinline__ int self_forces(C &c, const int R, const int (&lrow)[
     if (mycol > KCOL) {
       c.overflow |= 4;
       DM_SYNC();
-      if (row && ((int)T.r_col[lane] >= KCOL || mycol2 >= KCOL)) { if (crow) T.c_excl[lane / 3] = 1; else T.r_D[lane] = 0.f; }
+      if (row && ((int)T.r_col[lane] >= KCOL || (SELF && mycol2 >= KCOL))) { if (crow) T.c_excl[lane / 3] = 1; else T.r_D[lane] = 0.f; }
       DM_SYNC();
       if (lane < nc && T.c_excl[lane]) T.c_D[lane] = 0.f;
     }
   }
   DM_SYNC();
   const int mycol = row ? (int)T.r_col[lane] : 0;
-  // this row: its contact, the two links whose chains it spans (a floor row: one), a limit row's hinge
+  // this row: its contact, the link whose chain it spans (a fly-fly row: the links of geom2 and geom1), a limit row's hinge
   const int ck = crow ? lane / 3 : (srow ? nc + lane - nrc : 0);
-  const int lpos = jrow ? (int)T.c_link[ck] : 0, lneg = jrow ? (int)T.c_link1[ck] : 255;
-  const int npos = jrow ? M.l_nchain[lpos] : 0, nneg = lneg != 255 ? M.l_nchain[lneg] : 0;
+  const int lpos = jrow ? (int)T.c_link[ck] : 0, npos = jrow ? M.l_nchain[lpos] : 0;
+  int lneg = 255, nneg = 0;
+  if constexpr (SELF) { lneg = jrow ? (int)T.c_link1[ck] : 255; nneg = lneg != 255 ? M.l_nchain[lneg] : 0; }
   const int rdof = (row && !jrow) ? (int)T.r_dof[lane] : 0;
   const float sg = (row && !jrow) ? T.r_sgn[lane] : 0.f;
   // fn(hinge, J entry, 0 = geom2's chain / 1 = geom1's): a hinge on both chains is visited twice and the entries cancel
   auto each = [&](auto &&fn) {
     for (int p = 0; p < npos; p++) { const int f = M.l_chain[p][lpos]; fn(f, fj_row(T, er, ck, f), 0); }
-    for (int p = 0; p < nneg; p++) { const int f = M.l_chain[p][lneg]; fn(f, -fj_row(T, er, ck, f), 1); }
+    if constexpr (SELF) { for (int p = 0; p < nneg; p++) { const int f = M.l_chain[p][lneg]; fn(f, -fj_row(T, er, ck, f), 1); } }
   };
   // ---- z_m = M_jj^-1 f_j and Y_m = M_jj^-1 M_jr through M's own factor; a row lane keeps J_j z_m and J_j Y_m of its row
   S6 ym[3];
   float zm[3], jz = 0.f, jy[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-  for (int s = 0; s < 3; s++) if (slot_on(c, s)) { const float *m6 = T.F[opq(c.sdof[s])]; T.X4[opq(c.sdof[s])] = make_float4(qs[s], m6[0], m6[1], m6[2]); }
-  DM_SYNC();
-  solve4(c, T.Lm, T.dinv_m);
-#pragma unroll
-  for (int s = 0; s < 3; s++) {
-    const float4 x = slot_on(c, s) ? T.X4[opq(c.sdof[s])] : make_float4(0.f, 0.f, 0.f, 0.f);
-    zm[s] = x.x; ym[s].a0 = x.y; ym[s].a1 = x.z; ym[s].a2 = x.w;
-  }
-  if (jrow) each([&](int f, float jv, int) { const float4 x = T.X4[f]; jz += jv * x.x; jy[0] += jv * x.y; jy[1] += jv * x.z; jy[2] += jv * x.w; });
-  else if (row) { const float4 x = T.X4[rdof]; jz = sg * x.x; jy[0] = sg * x.y; jy[1] = sg * x.z; jy[2] = sg * x.w; }
-  DM_SYNC();
-#pragma unroll
-  for (int s = 0; s < 3; s++) if (slot_on(c, s)) { const float *m6 = T.F[opq(c.sdof[s])]; T.X4[opq(c.sdof[s])] = make_float4(m6[3], m6[4], m6[5], 0.f); }
-  DM_SYNC();
-  solve4(c, T.Lm, T.dinv_m);
-#pragma unroll
-  for (int s = 0; s < 3; s++) {
-    const float4 x = slot_on(c, s) ? T.X4[opq(c.sdof[s])] : make_float4(0.f, 0.f, 0.f, 0.f);
-    ym[s].l0 = x.x; ym[s].l1 = x.y; ym[s].l2 = x.z;
-  }
-  if (jrow) each([&](int f, float jv, int) { const float4 x = T.X4[f]; jy[3] += jv * x.x; jy[4] += jv * x.y; jy[5] += jv * x.z; });
-  else if (row) { const float4 x = T.X4[rdof]; jy[3] = sg * x.x; jy[4] = sg * x.y; jy[5] = sg * x.z; }
-  DM_SYNC();
+  solve_zy(c, T.Lm, T.dinv_m, qs, T.F, zm, ym, [&](int half) {
+    if (half == 0) {
+      if (jrow) each([&](int f, float jv, int) { const float4 x = T.X4[f]; jz += jv * x.x; jy[0] += jv * x.y; jy[1] += jv * x.z; jy[2] += jv * x.w; });
+      else if (row) { const float4 x = T.X4[rdof]; jz = sg * x.x; jy[0] = sg * x.y; jy[1] = sg * x.z; jy[2] = sg * x.w; }
+    } else {
+      if (jrow) each([&](int f, float jv, int) { const float4 x = T.X4[f]; jy[3] += jv * x.x; jy[4] += jv * x.y; jy[5] += jv * x.z; });
+      else if (row) { const float4 x = T.X4[rdof]; jy[3] = sg * x.x; jy[4] = sg * x.y; jy[5] = sg * x.z; }
+    }
+  });
   // ---- S_m = L L', x_r = S_m^-1 (b_r + adhesion - M_rj z_m); qfrc_smooth . qacc_smooth for the solver's stopping test
   float Sm[6][6], br[6], id[6], xr[6];
   {
@@ -1332,9 +1099,16 @@ __device__ __forceinline__ int self_forces(C &c, const int R, const int (&lrow)[
 #pragma unroll
   for (int k = 0; k < 6; k++) scale2 += br[k] * xr[k];
   scale2 *= kFloorScale;
-  // ---- y0 = J qacc_smooth - aref: the hinges' share J_j (z_m - Y_m x_r); a floor row adds the root's share, a fly-fly row has none
+  // ---- y0 = J qacc_smooth - aref: the hinges' share J_j (z_m - Y_m x_r); a floor row adds the root's share with w_b x v_b and gravity by
+  //      hand, a fly-fly row has none
   if (row) {
-    float y = wsf::row_y0<float>(jz, jy, xr, 0.f);
+    float y;
+    if constexpr (SELF) y = wsf::row_y0<float>(jz, jy, xr, 0.f);
+    else {
+      y = jz;
+#pragma unroll
+      for (int k = 0; k < 6; k++) y -= jy[k] * xr[k];
+    }
     if (crow) {
       const M3 Rr = q2m(c.rq);
       const V3 g3 = (c.flags & BF_NO_GRAVITY) ? V3{0.f, 0.f, 0.f} : mtv(Rr, V3{0.f, 0.f, M.gz});
@@ -1371,44 +1145,74 @@ __device__ __forceinline__ int self_forces(C &c, const int R, const int (&lrow)[
   for (int cb = 0; cb < ncol; cb += 4) {
     for (int f = lane; f < ND; f += 64) T.X4[f] = make_float4(0.f, 0.f, 0.f, 0.f);
     DM_SYNC();
-    if (jrow) {
-      each([&](int f, float jv, int half) {
-        const int col = (half == 0 ? mycol : mycol2) - cb;
-        if (col >= 0 && col < 4) (&T.X4[f].x)[col] += jv;  // (its own lane alone writes this column of this block)
-      });
-    } else if (row) {
-      const int col = mycol - cb;
-      if (col >= 0 && col < 4) (&T.X4[rdof].x)[col] = sg;
-    }
-    DM_SYNC();
-    solve4(c, T.Lm, T.dinv_m);
-    if (jrow) {
-      float4 a0 = make_float4(0.f, 0.f, 0.f, 0.f), a1 = make_float4(0.f, 0.f, 0.f, 0.f);
-      each([&](int f, float jv, int half) {
-        const float4 y = T.X4[f];
-        if (half == 0) { a0.x += jv * y.x; a0.y += jv * y.y; a0.z += jv * y.z; a0.w += jv * y.w; }
-        else { a1.x += jv * y.x; a1.y += jv * y.y; a1.z += jv * y.z; a1.w += jv * y.w; }
-      });
-      g_add(a0, myb, cb);
-      if (nneg) g_add(a1, myb2 >= 0 ? myb2 : myb, cb);
-    } else if (row) {
-      const float4 y = T.X4[rdof];
-      g_add(make_float4(sg * y.x, sg * y.y, sg * y.z, sg * y.w), myb, cb);
+    if constexpr (SELF) {  // two chains, two columns and two accumulators: one of each per block the row has entries in
+      if (jrow) {
+        each([&](int f, float jv, int half) {
+          const int col = (half == 0 ? mycol : mycol2) - cb;
+          if (col >= 0 && col < 4) (&T.X4[f].x)[col] += jv;  // (its own lane alone writes this column of this block)
+        });
+      } else if (row) {
+        const int col = mycol - cb;
+        if (col >= 0 && col < 4) (&T.X4[rdof].x)[col] = sg;
+      }
+      DM_SYNC();
+      solve4(c, T.Lm, T.dinv_m);
+      if (jrow) {
+        float4 a0 = make_float4(0.f, 0.f, 0.f, 0.f), a1 = make_float4(0.f, 0.f, 0.f, 0.f);
+        each([&](int f, float jv, int half) {
+          const float4 y = T.X4[f];
+          if (half == 0) { a0.x += jv * y.x; a0.y += jv * y.y; a0.z += jv * y.z; a0.w += jv * y.w; }
+          else { a1.x += jv * y.x; a1.y += jv * y.y; a1.z += jv * y.z; a1.w += jv * y.w; }
+        });
+        g_add(a0, myb, cb);
+        if (nneg) g_add(a1, myb2 >= 0 ? myb2 : myb, cb);
+      } else if (row) {
+        const float4 y = T.X4[rdof];
+        g_add(make_float4(sg * y.x, sg * y.y, sg * y.z, sg * y.w), myb, cb);
+      }
+    } else {  // one chain: the column is stored, not added, and one accumulator takes it back
+      {
+        const int col = mycol - cb;
+        if (row && col >= 0 && col < 4) {
+          if (crow) { for (int p = 0; p < npos; p++) { const int f = M.l_chain[p][lpos]; (&T.X4[f].x)[col] = fj_row(T, er, ck, f); } }
+          else (&T.X4[rdof].x)[col] = sg;
+        }
+      }
+      DM_SYNC();
+      solve4(c, T.Lm, T.dinv_m);
+      if (row) {
+        float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (crow) {
+          for (int p = 0; p < npos; p++) {
+            const int f = M.l_chain[p][lpos];
+            const float jv = fj_row(T, er, ck, f);
+            const float4 y = T.X4[f];
+            acc.x += jv * y.x; acc.y += jv * y.y; acc.z += jv * y.z; acc.w += jv * y.w;
+          }
+        } else { const float4 y = T.X4[rdof]; acc = make_float4(sg * y.x, sg * y.y, sg * y.z, sg * y.w); }
+#pragma unroll
+        for (int q2 = 0; q2 < 4; q2++) {
+          const float av = q2 == 0 ? acc.x : (q2 == 1 ? acc.y : (q2 == 2 ? acc.z : acc.w));
+          const int r2 = cb + q2 < KCOL ? (int)T.rowof[myb][cb + q2] : 255;
+          if (r2 <= lane) T.G[gtri + r2] += av;  // (255 = no such row)
+        }
+      }
     }
     DM_SYNC();
   }
-  // ---- solve: floor cone blocks first, the scalar rows (fly-fly, limits) after them, the model's noslip sweeps (with the revert
-  //      test of ConeRowsResidual: on the fly's own contacts ConeRows' test flipped by rounding, row_newton.hpp)
+  // ---- solve: floor cone blocks first, the scalar rows (fly-fly, limits) after them, the model's noslip sweeps (with the fly's own
+  //      contacts under the revert test of ConeRowsResidual: on them ConeRows' test flipped by rounding, row_newton.hpp)
+  using Rows = std::conditional_t<SELF, ConeRowsResidual, ConeRows>;
   int nact = 0;
   for (int k = 0; k < nc; k++) nact += T.c_excl[k] ? 0 : 1;
   const int nslip = (nact > 0 && !(c.flags & BF_NO_NOSLIP)) ? M.noslip_iterations : 0;
   ModelPtr mp_ = (ModelPtr)c.M;
   int iters;
-  if (R <= 12) iters = row_newton<12, ConeRowsResidual>(c.T, mp_, lane, R, nrc, scale2, nslip, 0);
-  else if (R <= 18) iters = row_newton<18, ConeRowsResidual>(c.T, mp_, lane, R, nrc, scale2, nslip, 0);
-  else if (R <= 24) iters = row_newton<24, ConeRowsResidual>(c.T, mp_, lane, R, nrc, scale2, nslip, 0);
-  else if (R <= 32) iters = row_newton<32, ConeRowsResidual>(c.T, mp_, lane, R, nrc, scale2, nslip, 0);
-  else iters = row_newton<RMAX, ConeRowsResidual>(c.T, mp_, lane, R, nrc, scale2, nslip, 0);
+  if (R <= 12) iters = row_newton<12, Rows>(c.T, mp_, lane, R, nrc, scale2, nslip, 0);
+  else if (R <= 18) iters = row_newton<18, Rows>(c.T, mp_, lane, R, nrc, scale2, nslip, 0);
+  else if (R <= 24) iters = row_newton<24, Rows>(c.T, mp_, lane, R, nrc, scale2, nslip, 0);
+  else if (R <= 32) iters = row_newton<32, Rows>(c.T, mp_, lane, R, nrc, scale2, nslip, 0);
+  else iters = row_newton<RMAX, Rows>(c.T, mp_, lane, R, nrc, scale2, nslip, 0);
   // ---- qfrc_constraint: J_j' f on the hinges, J_r' f (floor rows alone, and the adhesion pull) on the root
   float fr[9];
   floor_frame(c, fr);
@@ -1436,7 +1240,10 @@ __device__ __forceinline__ int self_forces(C &c, const int R, const int (&lrow)[
   }
 #pragma unroll
   for (int s = 0; s < 3; s++) {
-    if (slot_on(c, s)) qs[s] += floor_gather<false>(T, M, fr, nc, opq(c.sdof[s]), T.r_f) + self_gather(T, M, nc, ns, opq(c.sdof[s]), &T.r_f[nrc]);
+    if (slot_on(c, s)) {
+      if constexpr (SELF) qs[s] += floor_gather<false>(T, M, fr, nc, opq(c.sdof[s]), T.r_f) + self_gather(T, M, nc, ns, opq(c.sdof[s]), &T.r_f[nrc]);
+      else qs[s] += floor_gather<false>(T, M, fr, nc, opq(c.sdof[s]), T.r_f);
+    }
     if (lrow[s] >= 0) qs[s] += lsgn[s] * T.r_f[lrow[s]];
   }
   DM_SYNC();
@@ -1447,11 +1254,15 @@ __device__ __forceinline__ int self_forces(C &c, const int R, const int (&lrow)[
 // mj: mj_rnePostConstraint + mj_sensorAcc for the force and touch sensors, on the free root (walk_sense.hpp): called from the
 // acceleration stage with this substep's qacc (the hinges' in T.X4[.].x; `xr`: the root rows of the arrowhead solve, gravity not yet
 // added) and contact forces (T.r_f), the state still the one before the integration.  Adds into T.sens[9 .. 32].  The link values go
-// through T.lp, which is dead once the solver has returned.  Out of line and a leaf.
-__device__ __noinline__ void floor_sense(WTileS *Tp, const BallModel FFE_GLOBAL *Mp, const WalkExtra FFE_GLOBAL *Xp, const int lane, const int nc,
-                                         const float xr0, const float xr1, const float xr2, const float xr3,
-                                         const float xr4, const float xr5, const float qw, const float qx, const float qy, const float qz) {
-  WTileS &T = *Tp;
+// through T.lp, which is dead once the solver has returned.  On a tile that also holds the fly's own contacts (slots nc .. nc + ns - 1,
+// their forces in T.r_f[3 nc + j]; `ns` is an int there and takes no register otherwise) a fly-fly contact pushes the link of geom2 along
+// its normal and the link of geom1 against it (walk_self_sense.hpp); a slot inside the gap has a row with D = 0 and a zero force.  Out of
+// line and a leaf.
+template <class Tile>
+__device__ __noinline__ void contact_sense(Tile *Tp, const BallModel FFE_GLOBAL *Mp, const WalkExtra FFE_GLOBAL *Xp, const int lane, const int nc,
+                                           const std::conditional_t<Tile::kSelf, int, NoSelf> ns, const float xr0, const float xr1, const float xr2,
+                                           const float xr3, const float xr4, const float xr5, const float qw, const float qx, const float qy, const float qz) {
+  Tile &T = *Tp;
   const BallModel FFE_GLOBAL &M = *Mp;
   const WalkExtra FFE_GLOBAL &X = *Xp;
   const unsigned lpack = M.l_pack[lane], tree = M.l_tree[lane];
@@ -1470,6 +1281,19 @@ __device__ __noinline__ void floor_sense(WTileS *Tp, const BallModel FFE_GLOBAL 
         const float f[3] = {T.r_f[3 * k], T.r_f[3 * k + 1], T.r_f[3 * k + 2]};
         ws::add_contact_force<float>(fr, f, fext);
         touch += ws::touch_share<float>(f[0]);
+      }
+    }
+  }
+  if constexpr (Tile::kSelf) {
+    for (int j = 0; j < ns; j++) {
+      const int k = nc + j;
+      const bool on_pos = (int)T.c_link[k] == lane, on_neg = (int)T.c_link1[k] == lane;  // (255, the thorax, is no lane's link)
+      if ((on_pos || on_neg) && !T.c_excl[k]) {
+        float n[3];
+        self_nrm(T, k, n);
+        const float f = T.r_f[3 * nc + j];
+        wss::add_pair_force<float>(n, f, on_pos, on_neg, fext);
+        touch += wss::pair_touch_share<float>(f, on_pos, on_neg);
       }
     }
   }
@@ -1520,91 +1344,6 @@ __device__ __noinline__ void floor_sense(WTileS *Tp, const BallModel FFE_GLOBAL 
   DM_SYNC();
 }
 
-// `floor_sense` on the tile that also holds the fly's own contacts (slots nc .. nc + ns - 1, their forces in T.r_f[3 nc + j]): a fly-fly
-// contact pushes the link of geom2 along its normal and the link of geom1 against it (walk_self_sense.hpp); a slot inside the gap has a
-// row with D = 0 and a zero force.  Everything behind the contact loop is floor_sense's.  Out of line and a leaf.
-template <class TileSX>
-__device__ __noinline__ void self_sense(TileSX *Tp, const BallModel FFE_GLOBAL *Mp, const WalkExtra FFE_GLOBAL *Xp, const int lane, const int nc, const int ns,
-                                        const float xr0, const float xr1, const float xr2, const float xr3,
-                                        const float xr4, const float xr5, const float qw, const float qx, const float qy, const float qz) {
-  TileSX &T = *Tp;
-  const BallModel FFE_GLOBAL &M = *Mp;
-  const WalkExtra FFE_GLOBAL &X = *Xp;
-  const unsigned lpack = M.l_pack[lane], tree = M.l_tree[lane];
-  const int parent = (int)(lpack & 0xffu) - 1, ndof = (int)((lpack >> 12) & 0x3u);
-  const int sub = (int)(tree & 0xffu), anc2 = (int)((tree >> 8) & 0xffu) - 1, anc4 = (int)((tree >> 16) & 0xffu) - 1;
-  float fext[3] = {0.f, 0.f, 0.f}, touch = 0.f;
-  if (nc > 0) {
-    const M3 Rr = q2m(Q4{qw, qx, qy, qz});
-    const float Rm[9] = {Rr.m0, Rr.m1, Rr.m2, Rr.m3, Rr.m4, Rr.m5, Rr.m6, Rr.m7, Rr.m8};
-    float fw[9], fr[9];
-#pragma unroll
-    for (int k = 0; k < 9; k++) fw[k] = X.f_frame[k];
-    wf::frame_in_root<float>(Rm, fw, fr);
-    for (int k = 0; k < nc; k++) {
-      if ((int)T.c_link[k] == lane && !T.c_excl[k]) {  // (a contact inside the gap, or one switched off for want of a column, has no row)
-        const float f[3] = {T.r_f[3 * k], T.r_f[3 * k + 1], T.r_f[3 * k + 2]};
-        ws::add_contact_force<float>(fr, f, fext);
-        touch += ws::touch_share<float>(f[0]);
-      }
-    }
-  }
-  for (int j = 0; j < ns; j++) {
-    const int k = nc + j;
-    const bool on_pos = (int)T.c_link[k] == lane, on_neg = (int)T.c_link1[k] == lane;  // (255, the thorax, is no lane's link)
-    if ((on_pos || on_neg) && !T.c_excl[k]) {
-      float n[3];
-      self_nrm(T, k, n);
-      const float f = T.r_f[3 * nc + j];
-      wss::add_pair_force<float>(n, f, on_pos, on_neg, fext);
-      touch += wss::pair_touch_share<float>(f, on_pos, on_neg);
-    }
-  }
-  // sum over the ancestor path of cdof * qacc by pointer jumping, as stage 1 sums the velocities
-  S6 dacc = zero6();
-  float g[3] = {0.f, 0.f, 0.f};
-#pragma unroll
-  for (int s = 0; s < 3; s++) {
-    if (s < ndof) {
-      const int f = M.s_dof[s][lane];
-      const float a = T.X4[f].x;
-      dacc = dacc + a * ld6(T.C[f]);
-      g[0] += a * T.F[f][3]; g[1] += a * T.F[f][4]; g[2] += a * T.F[f][5];
-    }
-  }
-#pragma unroll
-  for (int r = 0; r < 3; r++) {
-    const int an = r == 0 ? parent : (r == 1 ? anc2 : anc4);
-    st6(T.lp[lane], dacc);
-    DM_SYNC();
-    if (an >= 0) dacc = dacc + ld6(T.lp[an]);
-    DM_SYNC();
-  }
-  {
-    float *o = T.lp[lane];
-    o[0] = g[0]; o[1] = g[1]; o[2] = g[2]; o[3] = fext[0]; o[4] = fext[1]; o[5] = fext[2];
-  }
-  DM_SYNC();
-  const int fi = M.l_force[lane], ti = M.l_touch[lane];
-  if (fi >= 0) {
-    float gs[3] = {0.f, 0.f, 0.f};
-#pragma unroll 1
-    for (int t = 1; t < sub; t++) {
-      const float *p = T.lp[lane + t];
-      gs[0] += p[0]; gs[1] += p[1]; gs[2] += p[2]; fext[0] += p[3]; fext[1] += p[4]; fext[2] += p[5];
-    }
-    const float A[6] = {xr0 + dacc.a0, xr1 + dacc.a1, xr2 + dacc.a2, xr3 + dacc.l0, xr4 + dacc.l1, xr5 + dacc.l2};
-    const float *sp = T.sp[fi];
-    float fint[3], o[3];
-    ws::accel_term<float>(sp[3], sp + 4, A, fint);
-    fint[0] += gs[0] + sp[0] - fext[0]; fint[1] += gs[1] + sp[1] - fext[1]; fint[2] += gs[2] + sp[2] - fext[2];
-    ws::to_site<float>(T.fsq[fi], fint, o);
-    T.sens[9 + 3 * fi] += o[0]; T.sens[9 + 3 * fi + 1] += o[1]; T.sens[9 + 3 * fi + 2] += o[2];
-  }
-  if (ti >= 0) T.sens[27 + ti] += touch;
-  DM_SYNC();
-}
-
 // ------------------------------------------------------------------------------------------------ stage 2
 // EP (the episode kernel): also mj's qacc = M^-1 (qfrc_smooth + qfrc_constraint) through M's own factor - the Euler solve below is
 // implicit in the joint damping, so its solution is not qacc - for the accelerometer of this substep (`acc`, from the state before the
@@ -1613,9 +1352,10 @@ template <bool LIMITS, bool EP = false, class C>
 __device__ __forceinline__ void stage2(C &c, float act_reg, float ctrl_reg, float &act_out, int &nlim_out, int &iters_out,
                                        const ImitArgs *ep = nullptr, bool integrate = true, float *acc = nullptr, float *qn2 = nullptr) {
   auto &T = *c.T;
-  constexpr bool FLOOR = is_floor_tile<std::remove_reference_t<decltype(T)>>::value;  // the floor kernel: everything it adds is under this switch
-  constexpr bool SENSE = is_sense_tile<std::remove_reference_t<decltype(T)>>::value;  // the episode kernel on the floor: likewise
-  constexpr bool SELF = is_self_tile<std::remove_reference_t<decltype(T)>>::value;    // the kernel with the fly's own contacts: likewise
+  using Tile = std::remove_reference_t<decltype(T)>;
+  constexpr bool FLOOR = Tile::kFloor;  // the floor kernel: everything it adds is under this switch
+  constexpr bool SENSE = Tile::kSense;  // the episode kernel on the floor: likewise
+  constexpr bool SELF = Tile::kSelf;    // the kernel with the fly's own contacts: likewise
   const BallModel FFE_GLOBAL &M = model(c);
   const int lane = c.lane;
   const float h = M.h;
@@ -1708,8 +1448,7 @@ __device__ __forceinline__ void stage2(C &c, float act_reg, float ctrl_reg, floa
     iters_out = 0;
     if (R > 0) {  // wave-uniform: a substep without a row pays the ballots only
       DM_SYNC();
-      if constexpr (SELF) iters_out = self_forces(c, R, lrow, lsgn, qs);
-      else if constexpr (FLOOR) iters_out = floor_forces(c, R, lrow, lsgn, qs);  // (limit rows alone too: the cone solver with no cone block)
+      if constexpr (FLOOR) iters_out = contact_forces(c, R, lrow, lsgn, qs);  // (limit rows alone too: the cone solver with no cone block)
       else iters_out = limit_forces(c, R, lrow, lsgn, mrj, qs);
       // (read again rather than kept in registers across the solver's call: 18 fewer live values there)
 #pragma unroll
@@ -1726,26 +1465,7 @@ __device__ __forceinline__ void stage2(C &c, float act_reg, float ctrl_reg, floa
 #pragma unroll
     for (int s = 0; s < 3; s++) T.qsave[s][lane] = qs[s];
     }
-#pragma unroll
-    for (int s = 0; s < 3; s++) if (slot_on(c, s)) T.X4[opq(c.sdof[s])] = make_float4(qs[s], mrj[s].a0, mrj[s].a1, mrj[s].a2);
-    DM_SYNC();
-    solve4(c, T.Lm, T.dinv_m);
-#pragma unroll
-    for (int s = 0; s < 3; s++) {
-      const float4 x = slot_on(c, s) ? T.X4[opq(c.sdof[s])] : make_float4(0.f, 0.f, 0.f, 0.f);
-      zm[s] = x.x; ym[s].a0 = x.y; ym[s].a1 = x.z; ym[s].a2 = x.w;
-    }
-    DM_SYNC();
-#pragma unroll
-    for (int s = 0; s < 3; s++) if (slot_on(c, s)) T.X4[opq(c.sdof[s])] = make_float4(mrj[s].l0, mrj[s].l1, mrj[s].l2, 0.f);
-    DM_SYNC();
-    solve4(c, T.Lm, T.dinv_m);
-#pragma unroll
-    for (int s = 0; s < 3; s++) {
-      const float4 x = slot_on(c, s) ? T.X4[opq(c.sdof[s])] : make_float4(0.f, 0.f, 0.f, 0.f);
-      ym[s].l0 = x.x; ym[s].l1 = x.y; ym[s].l2 = x.z;
-    }
-    DM_SYNC();
+    solve_zy(c, T.Lm, T.dinv_m, qs, mrj, zm, ym);
     float Sm[6][6], br[6], id[6], xr[6];
     schur(c, mrj, ym, zm, Sm, br);
     if constexpr (FLOOR) {  // the contacts' force on the root (and the adhesion pull), as in the Euler solve below
@@ -1763,7 +1483,7 @@ __device__ __forceinline__ void stage2(C &c, float act_reg, float ctrl_reg, floa
 #pragma unroll
         for (int k = 0; k < 6; k++) a -= comp(ym[s], k) * xr[k];
         sq += a * a;
-        if constexpr (SENSE) T.X4[opq(c.sdof[s])].x = a;  // (its own lane reads it back in floor_sense: three fewer live values)
+        if constexpr (SENSE) T.X4[opq(c.sdof[s])].x = a;  // (its own lane reads it back in contact_sense: three fewer live values)
       }
     }
     const M3 R = q2m(c.rq);
@@ -1774,8 +1494,7 @@ __device__ __forceinline__ void stage2(C &c, float act_reg, float ctrl_reg, floa
     const float qr[4] = {c.rq.w, c.rq.x, c.rq.y, c.rq.z}, wb[3] = {c.wb.x, c.wb.y, c.wb.z}, al[3] = {aw.x, aw.y, aw.z}, wd[3] = {xr[0], xr[1], xr[2]};
     wi::imu_acceleration<float>(qr, wb, al, wd, grav ? M.gz : 0.f, ep->site_pos, ep->site_quat, acc);
     if constexpr (SENSE) {  // (last: only the accelerometer and sum qacc^2 are live across the call)
-      if constexpr (SELF) self_sense(c.T, (ModelPtr)c.M, c.X, lane, c.fl.nc, c.fl.ns, xr[0], xr[1], xr[2], xr[3], xr[4], xr[5], c.rq.w, c.rq.x, c.rq.y, c.rq.z);
-      else floor_sense(c.T, (ModelPtr)c.M, c.X, lane, c.fl.nc, xr[0], xr[1], xr[2], xr[3], xr[4], xr[5], c.rq.w, c.rq.x, c.rq.y, c.rq.z);
+      contact_sense(c.T, (ModelPtr)c.M, c.X, lane, c.fl.nc, self_count(c.fl), xr[0], xr[1], xr[2], xr[3], xr[4], xr[5], c.rq.w, c.rq.x, c.rq.y, c.rq.z);
     }
     if (!integrate) { act_out = act_reg; return; }
 #pragma unroll
@@ -1785,26 +1504,7 @@ __device__ __forceinline__ void stage2(C &c, float act_reg, float ctrl_reg, floa
       mrj[s] = slot_on(c, s) ? ld6(T.F[opq(c.sdof[s])]) : zero6();
     }
   }
-#pragma unroll
-  for (int s = 0; s < 3; s++) if (slot_on(c, s)) T.X4[opq(c.sdof[s])] = make_float4(qs[s], mrj[s].a0, mrj[s].a1, mrj[s].a2);
-  DM_SYNC();
-  solve4(c, T.Lh, T.dinv_h);
-#pragma unroll
-  for (int s = 0; s < 3; s++) {
-    const float4 x = slot_on(c, s) ? T.X4[opq(c.sdof[s])] : make_float4(0.f, 0.f, 0.f, 0.f);
-    z[s] = x.x; y[s].a0 = x.y; y[s].a1 = x.z; y[s].a2 = x.w;
-  }
-  DM_SYNC();
-#pragma unroll
-  for (int s = 0; s < 3; s++) if (slot_on(c, s)) T.X4[opq(c.sdof[s])] = make_float4(mrj[s].l0, mrj[s].l1, mrj[s].l2, 0.f);
-  DM_SYNC();
-  solve4(c, T.Lh, T.dinv_h);
-#pragma unroll
-  for (int s = 0; s < 3; s++) {
-    const float4 x = slot_on(c, s) ? T.X4[opq(c.sdof[s])] : make_float4(0.f, 0.f, 0.f, 0.f);
-    y[s].l0 = x.x; y[s].l1 = x.y; y[s].l2 = x.z;
-  }
-  DM_SYNC();
+  solve_zy(c, T.Lh, T.dinv_h, qs, mrj, z, y);
   if constexpr (!LIMITS) {
 #pragma unroll
     for (int s = 0; s < 3; s++) if (slot_on(c, s)) st6(T.Y[opq(c.sdof[s])], y[s]);  // (the limits kernel reads its rows' Y_m from the solve instead)
@@ -1911,7 +1611,7 @@ __device__ __forceinline__ void walk_substeps(Tile &T, const WalkModel *__restri
       ctrl_reg = av;
     }
     nphys = row == 1 ? 1 : M.nsub;
-    if constexpr (is_sense_tile<Tile>::value) nphys = __builtin_amdgcn_readfirstlane(nphys);  // (the loop bound in an SGPR: it was this kernel's last spilled VGPR)
+    if constexpr (Tile::kSense) nphys = __builtin_amdgcn_readfirstlane(nphys);  // (the loop bound in an SGPR: it was this kernel's last spilled VGPR)
     if (lane < 36) T.sens[lane] = 0.f;  // (the sums are cleared at substep 0)
     DM_SYNC();
   } else {
@@ -1919,16 +1619,16 @@ __device__ __forceinline__ void walk_substeps(Tile &T, const WalkModel *__restri
   }
   int nlim = 0, iters = 0;
   float qn2 = 0.f;
-  constexpr bool FLOOR = is_floor_tile<Tile>::value;
+  constexpr bool FLOOR = Tile::kFloor;
 #pragma unroll 1
   for (int s = 0; s < nphys; s++) {
-    if constexpr (is_sense_tile<Tile>::value) {
+    if constexpr (Tile::kSense) {
       // (opaque per substep: the LDS addresses stage 1 forms from the lane and its parent are then formed again in every substep, a
       //  few VALU operations, and not kept in registers over the loop, where they were the two VGPRs this kernel spilled)
       c.lpack = opq(c.lpack); c.lane = opq(c.lane);
     }
     stage1(c);
-    if constexpr (is_sense_tile<Tile>::value) {
+    if constexpr (Tile::kSense) {
       // ---- what the sensor pass of stage 2 needs of this link, while stage 1's values are at hand (walk_sense.hpp)
       //      every link publishes its velocity term, its mass and m r through T.lp (free between the factorisation and the collision
       //      pass); a sensor's link sums them over its depth-first lane range
@@ -1974,7 +1674,7 @@ __device__ __forceinline__ void walk_substeps(Tile &T, const WalkModel *__restri
       float md = 0.f;
       for (int k = 0; k < c.fl.nc; k++) md = k == 0 ? T.c_dist[0] : fminf(md, T.c_dist[k]);
       c.fl.mind = md;
-      if constexpr (is_self_tile<Tile>::value) {
+      if constexpr (Tile::kSelf) {
         // ---- the fly's own contacts behind the floor's: sphere / capsule pairs, then the pairs with an ellipsoid or a cylinder.
         //      Every substep runs both passes (the mouth parts touch in every pose: there is no "nothing in reach" shortcut).
         if (lane < 6) T.sv0[lane] = comp(c.V0, lane);  // (visible after the first pass's own barrier, as the three stores below)
@@ -1992,7 +1692,7 @@ __device__ __forceinline__ void walk_substeps(Tile &T, const WalkModel *__restri
     if constexpr (EP) {
       // dm_control runs mj_step2 ; mj_step1 and samples: the accelerometer is the acceleration stage's (the state before the
       // integration, this substep's qacc), gyro and velocimeter belong to the state after it.  Force and touch stay zero: no contacts.
-      // (On the floor they are the acceleration stage's too: stage 2 calls floor_sense.)
+      // (On the floor they are the acceleration stage's too: stage 2 calls contact_sense.)
       float acc[3], gy[3], ve[3];
       stage2<LIMITS, true>(c, act_reg, ctrl_reg, act_new, nlim, iters, ep.a, row == 0, acc, &qn2);
       const float qr[4] = {c.rq.w, c.rq.x, c.rq.y, c.rq.z}, vl[3] = {c.vw.x, c.vw.y, c.vw.z}, wb[3] = {c.wb.x, c.wb.y, c.wb.z};
@@ -2016,10 +1716,10 @@ __device__ __forceinline__ void walk_substeps(Tile &T, const WalkModel *__restri
     S.wb[0] = c.wb.x; S.wb[1] = c.wb.y; S.wb[2] = c.wb.z;
     S.pos[0] = c.pos[0]; S.pos[1] = c.pos[1]; S.pos[2] = c.pos[2];
     if constexpr (LIMITS) { S.nlim = nlim; S.iters = iters; S.step_bits = c.overflow; }
-    if constexpr (FLOOR && EP && is_self_tile<Tile>::value) ep.a->rec[env] = FloorRec{c.fl.nc + c.fl.ns, T.rootf[6], c.fl.mind, c.fl.ns};
-    else if constexpr (FLOOR && EP) ep.a->rec[env] = FloorRec{c.fl.nc, T.rootf[6], c.fl.mind, 0};
-    else if constexpr (is_self_tile<Tile>::value) ep.rec[env] = FloorRec{c.fl.nc + c.fl.ns, T.rootf[6], c.fl.mind, c.fl.ns};
-    else if constexpr (FLOOR) ep.rec[env] = FloorRec{c.fl.nc, T.rootf[6], c.fl.mind, 0};
+    if constexpr (FLOOR) {
+      const int ns = self_count(c.fl);
+      contact_record(ep)[env] = FloorRec{c.fl.nc + ns, T.rootf[6], c.fl.mind, ns};
+    }
   }
   if constexpr (EP) {
     // ---- the 92 physics columns of the observation row (the task layer writes the kinematic ones), the state for the task layer, and
