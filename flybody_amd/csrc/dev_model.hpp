@@ -6,11 +6,13 @@
 #pragma once
 
 #include <cmath>
+#include <cstddef>
 #include <cstdint>
 #include <cstring>
 #include <map>
 #include <stdexcept>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "convex.hpp"  // cvx::ushape: the broad phase's per-geom constants
@@ -87,11 +89,83 @@ class Blob {
   std::map<std::string, Tensor> tensors_;
 };
 
+// ------------------------------------------------------------------------------------------------ arena layout
+// Every model table sits at a compile-time byte offset of the arena, so that a kernel stage forms a table's address as
+// (arena base + constant) from one base pair instead of fetching the table's pointer from the struct below ahead of every read.
+// The arena starts with the DevModel struct itself (kHeader bytes): the pointer a stage holds to read the wave-uniform scalars is
+// that base.  Tables are 256-byte aligned and ordered by the stage that reads them (the constraint stage with the factorisation
+// and the solves, actuation, the position / velocity stage, the task, collision), so that neighbours share a base + immediate.
+// Every length is a kernel capacity: the tables whose length follows the model are padded to the capacity the builder enforces
+// anyway (m_row / m_col / colmadr: kMaxM, ell: one block per link, qpos0: kMaxDof + 4, pairtab: its fixed four waves).  The one
+// table without a bound, the factorisation schedule, is the arena's tail: a fixed start needs no capacity.
+//   X(field of DevModel, element type, elements)
+#define FFE_MODEL_TABLES(X)                                                                                                        \
+  X(d_madr, int, kLanePad) X(d_depth, int, kLanePad) X(d_ndesc, int, kLanePad) X(br_seq, unsigned int, 4 * kWave)                  \
+  X(d_kind, int, kLanePad) X(d_qadr, int, kLanePad) X(d_limited, int, kLanePad) X(d_margin, float, kLanePad)                       \
+  X(d_lo, float, kLanePad) X(d_hi, float, kLanePad) X(d_solimp, float, 5 * kLanePad) X(d_K, float, kLanePad)                       \
+  X(d_B, float, kLanePad) X(d_invw, float, kLanePad) X(d_damp, float, kLanePad) X(d_arm, float, kLanePad)                          \
+  X(l_dofmask, unsigned long long, kMaxLink + 1) X(m_row, unsigned char, kMaxM + 2) X(m_col, unsigned char, kMaxM + 2)             \
+  X(colmadr, unsigned short, kMaxM + 8)                                                                                            \
+  X(d_act_id, int, 2 * kLanePad) X(d_act_coef, float, 2 * kLanePad) X(t_qadr, int, kMaxWrap * kMaxAct)                             \
+  X(t_dof, int, kMaxWrap * kMaxAct) X(t_coef, float, kMaxWrap * kMaxAct) X(a_cl, int, kMaxAct) X(a_fl, int, kMaxAct)               \
+  X(a_action, int, kMaxAct) X(a_gain, float, kMaxAct) X(a_b0, float, kMaxAct) X(a_b1, float, kMaxAct) X(a_b2, float, kMaxAct)      \
+  X(a_clo, float, kMaxAct) X(a_chi, float, kMaxAct) X(a_flo, float, kMaxAct) X(a_fhi, float, kMaxAct)                              \
+  X(d_link, int, kLanePad) X(l_dofadr, int, kLanePad) X(l_dofnum, int, kLanePad) X(l_sub, int, kLanePad)                           \
+  X(l_anc, unsigned int, 2 * kLanePad) X(l_parent, int, kLanePad) X(l_mass, float, kLanePad) X(l_ipos, float, 3 * kLanePad)        \
+  X(l_inertia, float, 3 * kLanePad) X(l_imat, float, 9 * kLanePad) X(d_axis, float, 3 * kLanePad) X(d_qpos0, float, kLanePad)      \
+  X(l_quat, float, 4 * kLanePad) X(l_pos, float, 3 * kLanePad) X(l_reckind, int, kLanePad) X(l_recell, int, kLanePad)              \
+  X(l_reccoef, float, 8 * kLanePad) X(l_recpos, float, 3 * kLanePad) X(l_recmat, float, 9 * kLanePad)                              \
+  X(ell, float, 32 * kMaxLink) X(rr_coef, float, 8 * kLanePad) X(rr_pos, float, 3 * kLanePad) X(rr_mat, float, 9 * kLanePad)       \
+  X(d_stiff, float, kLanePad) X(d_sref, float, kLanePad)                                                                           \
+  X(wing_dof, int, 8) X(wing_qadr, int, 8) X(wing_action, int, 8) X(wing_ctrl, int, 8) X(obsj_qadr, int, kMaxObsJ)                 \
+  X(obsj_dof, int, kMaxObsJ) X(qpos0, float, kMaxDof + 4)                                                                          \
+  X(cg_link, int, kMaxGeom) X(cg_type, int, kMaxGeom) X(cg_pos, float, 3 * kMaxGeom) X(cg_quat, float, 4 * kMaxGeom)               \
+  X(cg_size, float, 3 * kMaxGeom) X(cg_brad, float, kMaxGeom) X(cg_invw, float, kMaxGeom) X(cg_ush, float4, 2 * kMaxGeom)          \
+  X(cp_pair, unsigned short, kMaxPair) X(pairtab, unsigned int, 4 * kWave)
+
+namespace lay {
+constexpr size_t kAlign = 256;
+constexpr size_t kHeader = 1024;  // the DevModel struct
+constexpr size_t up(size_t n) { return (n + kAlign - 1) & ~(kAlign - 1); }
+enum Id {
+#define X(n, t, c) id_##n,
+  FFE_MODEL_TABLES(X)
+#undef X
+  kTables
+};
+constexpr size_t kBytes[kTables] = {
+#define X(n, t, c) sizeof(t) * (size_t)(c),
+    FFE_MODEL_TABLES(X)
+#undef X
+};
+constexpr size_t start_of(int id) {
+  size_t o = kHeader;
+  for (int i = 0; i < id; i++) o += up(kBytes[i]);
+  return o;
+}
+#define X(n, t, c) constexpr size_t n = start_of(id_##n);
+FFE_MODEL_TABLES(X)
+#undef X
+constexpr size_t fsched = start_of(kTables);  // [fs_rounds + 10][64] words: the tail
+}  // namespace lay
+
 // ------------------------------------------------------------------------------------------------ device view
-// Pointers into the arena (device addresses once uploaded).  Lane-major tables: element (c, lane) at [c*64+lane].
-struct DevModel {
-  int nlink, nv, nq, nu, nM, nrootrec, nobsj, nwing, naction, nsub;
-  float h, gx, gy, gz, total_mass;
+// The head of the arena: wave-uniform scalars, grouped by the stage that reads them so that a stage's reads are neighbours, then the
+// tables' addresses (device addresses once uploaded; each equals arena + its lay:: offset).  The flight kernels read the tables at
+// their fixed offsets; the pointer fields serve everything else.  Lane-major tables: element (c, lane) at [c*64+lane].
+struct alignas(64) DevModel {
+  int nv, nroot, nbr_steps, nM;  // (nroot: dofs of the root chain (6); nbr_steps: longest branch sequence)
+  unsigned solve_dims;           // nv | nroot << 8 | nbr_steps << 16: what every triangular solve reads, in one word
+  int nbranch, fs_branch_rounds, fs_rounds;
+  float gx, gy, gz, h;
+  float total_mass;
+  int nlink, nrootrec, nu;
+  int any_b2;  // some actuator has a velocity term in its affine bias (none in the flight model)
+  int nq, nsub, nobsj, nwing, naction, user_action;
+  int ncg, ncp;  // ncg == 0: a model blob without geoms (contact-free configurations)
+  float c_margin, c_gap, c_K, c_B, c_solimp[5];
+  unsigned long long cg_mmask[2];  // geoms that carry the margin / gap (labrum, claws)
+  const unsigned char FFE_GLOBAL *arena;  // the arena's base = the address of this struct on the device
   // per dof
   const int FFE_GLOBAL *d_link, *d_madr, *d_depth, *d_kind, *d_qadr, *d_limited, *d_act_id, *d_ndesc;  // d_act_id: [2][64]
   const unsigned int FFE_GLOBAL *pairtab;  // [256] elimination pairs (s | t << 8), sorted by t then s
@@ -99,15 +173,12 @@ struct DevModel {
   // branches (abdomen chain, head subtree, wings, halteres); br_seq[w][lane] packs, 4 bytes per word, the elimination order
   // (leaf end first) of the branch the lane's dof belongs to, 0xff-padded; root-chain lanes and idle lanes hold 0xff only.
   const unsigned int FFE_GLOBAL *br_seq;   // [4][64]
-  int nbr_steps, nroot;                    // longest branch sequence; dofs of the root chain (6)
-  int any_b2;                              // some actuator has a velocity term in its affine bias (none in the flight model)
   // Branch-parallel factorisation schedule: step t eliminates the t-th pivot of every branch at once; the pair updates
   // M(a_s, a_t) -= M(k, a_s) M(k, a_t) / M(k, k) of all those pivots are dealt over the 64 lanes in rounds.  One word per
   // (round, lane): row start of the pivot | s << 9 | t << 14 | target << 19 | last round of its step << 30 | valid << 31, the
   // target being an entry of M, or 512 + 21 * branch + e for entry e of the root block (rows of the free joint's dofs), which
   // concurrent branches accumulate in private copies (folded in before the root chain is eliminated).
   const unsigned int FFE_GLOBAL *fsched;   // [fs_rounds + 1][64]
-  int fs_branch_rounds, fs_rounds, nbranch;
   const float FFE_GLOBAL *d_axis, *d_arm, *d_damp, *d_stiff, *d_sref, *d_lo, *d_hi, *d_margin, *d_invw, *d_K, *d_B, *d_solimp,
       *d_act_coef, *d_qpos0;  // d_axis [3][64]; d_solimp [5][64]; d_act_coef [2][64]
   // per link
@@ -127,21 +198,19 @@ struct DevModel {
   const float FFE_GLOBAL *a_gain, *a_b0, *a_b1, *a_b2, *a_clo, *a_chi, *a_flo, *a_fhi;
   // task bookkeeping
   const int FFE_GLOBAL *wing_dof, *wing_qadr, *wing_action, *wing_ctrl, *obsj_qadr, *obsj_dof;  // wing_ctrl: ctrl slot fed by the wing's action entry
-  int user_action;
   const float FFE_GLOBAL *qpos0;  // [nq]
   // ---- collision geoms (ref: tasks/base.py:299-302 disables the floor only: the fly's own geoms still collide in flight).  All
   //      70 geoms in model order, frames in their link (cg_pos [3][kMaxGeom], cg_quat [4][.], cg_size [3][.]); cp_pair = the static
   //      candidate list (flybody_amd/model/reach.py), g1 | g2 << 8 with g1 the lower type code (mj_collision's order), 0xffff padding;
-  //      l_dofmask[l] = dofs that move link l.  ncg == 0: a model blob without geoms (contact-free configurations).
-  int ncg, ncp;
-  float c_margin, c_gap, c_K, c_B, c_solimp[5];
-  unsigned long long cg_mmask[2];  // geoms that carry the margin / gap (labrum, claws)
+  //      l_dofmask[l] = dofs that move link l.
   const int FFE_GLOBAL *cg_link, *cg_type;
   const float FFE_GLOBAL *cg_pos, *cg_quat, *cg_size, *cg_brad, *cg_invw;
   const float4 FFE_GLOBAL *cg_ush;  // [kMaxGeom][2] the broad phase's form of each geom (cvx::ushape): radii + segment half-length, core segment
   const unsigned short FFE_GLOBAL *cp_pair;
   const unsigned long long FFE_GLOBAL *l_dofmask;
 };
+static_assert(sizeof(DevModel) <= lay::kHeader, "the struct is the arena's first kHeader bytes");
+static_assert(offsetof(DevModel, gx) % 16 == 0 && offsetof(DevModel, gz) == offsetof(DevModel, gx) + 8, "gravity is read as one 16-byte group");
 
 struct BoxCoef { float c[8]; };  // visc_ang, visc_lin, quad_lin[3], quad_ang[3]
 
@@ -167,13 +236,19 @@ inline void quat2mat_d(const double *q, double *m) {
   m[6] = 2 * (x * z - w * y); m[7] = 2 * (y * z + w * x); m[8] = w * w - x * x - y * y + z * z;
 }
 
-// Bump allocator for the arena; returns byte offsets, 16-byte aligned.
+// Writes the tables into the arena at their lay:: offsets (zero padding up to each capacity).
 class Arena {
  public:
+  Arena() : buf_(lay::fsched, 0) {}
   template <typename T>
-  size_t put(const std::vector<T> &v) {
-    size_t off = (buf_.size() + 15) & ~size_t(15);
-    buf_.resize(off + v.size() * sizeof(T) + 16);
+  size_t place(size_t off, size_t capacity, const std::vector<T> &v, const char *name) {
+    if (v.size() * sizeof(T) > capacity) throw std::runtime_error(std::string("model table exceeds its arena capacity: ") + name);
+    std::memcpy(buf_.data() + off, v.data(), v.size() * sizeof(T));
+    return off;
+  }
+  template <typename T>
+  size_t tail(size_t off, const std::vector<T> &v) {  // the one table of open length, behind everything else
+    buf_.resize(off + v.size() * sizeof(T) + 16, 0);
     std::memcpy(buf_.data() + off, v.data(), v.size() * sizeof(T));
     return off;
   }
@@ -196,22 +271,11 @@ struct HostModel {
       using P = std::remove_reference_t<decltype(p)>;
       p = (P)((size_t)base + (size_t)p);  // C-style: the member may carry a device address-space qualifier
     };
-    fix(dst.d_link); fix(dst.d_madr); fix(dst.d_depth); fix(dst.d_kind); fix(dst.d_qadr);
-    fix(dst.d_limited); fix(dst.d_act_id); fix(dst.d_ndesc); fix(dst.pairtab); fix(dst.br_seq); fix(dst.fsched); fix(dst.d_axis); fix(dst.d_arm); fix(dst.d_damp); fix(dst.d_stiff);
-    fix(dst.d_sref); fix(dst.d_lo); fix(dst.d_hi); fix(dst.d_margin); fix(dst.d_invw); fix(dst.d_K); fix(dst.d_B);
-    fix(dst.d_solimp); fix(dst.d_act_coef); fix(dst.d_qpos0);
-    fix(dst.l_anc); fix(dst.l_parent); fix(dst.l_dofadr); fix(dst.l_dofnum); fix(dst.l_sub); fix(dst.l_reckind); fix(dst.l_recell);
-    fix(dst.l_pos); fix(dst.l_quat); fix(dst.l_ipos); fix(dst.l_imat); fix(dst.l_inertia); fix(dst.l_mass);
-    fix(dst.l_recpos); fix(dst.l_recmat); fix(dst.l_reccoef);
-    fix(dst.rr_pos); fix(dst.rr_mat); fix(dst.rr_coef); fix(dst.ell);
-    fix(dst.m_row); fix(dst.m_col); fix(dst.colmadr);
-    fix(dst.a_cl); fix(dst.a_fl); fix(dst.a_action); fix(dst.t_qadr); fix(dst.t_dof); fix(dst.t_coef);
-    fix(dst.a_gain); fix(dst.a_b0); fix(dst.a_b1); fix(dst.a_b2); fix(dst.a_clo); fix(dst.a_chi); fix(dst.a_flo);
-    fix(dst.a_fhi);
-    fix(dst.wing_dof); fix(dst.wing_qadr); fix(dst.wing_action); fix(dst.wing_ctrl); fix(dst.obsj_qadr); fix(dst.obsj_dof);
-    fix(dst.qpos0);
-    fix(dst.cg_link); fix(dst.cg_type); fix(dst.cg_pos); fix(dst.cg_quat); fix(dst.cg_size); fix(dst.cg_brad); fix(dst.cg_invw); fix(dst.cg_ush);
-    fix(dst.cp_pair); fix(dst.l_dofmask);
+#define X(n, t, c) fix(dst.n);
+    FFE_MODEL_TABLES(X)
+#undef X
+    fix(dst.fsched);
+    fix(dst.arena);  // (offset 0: the base itself)
   }
 };
 
@@ -230,7 +294,7 @@ inline HostModel build_host_model(const Blob &b) {
   const int nv = static_cast<int>(dofpar.count);
   const int nq = static_cast<int>(b.get("qpos0").count);
   const int nu = static_cast<int>(b.get("act_trntype").count);
-  if (nl > kMaxLink || nv > kMaxDof || nu > kMaxAct) throw std::runtime_error("model exceeds kernel capacities");
+  if (nl > kMaxLink || nv > kMaxDof || nu > kMaxAct || nq > kMaxDof + 4) throw std::runtime_error("model exceeds kernel capacities");
   V.nlink = nl; V.nv = nv; V.nq = nq; V.nu = nu;
   V.h = static_cast<float>(h);
   V.gx = static_cast<float>(opt.f(3)); V.gy = static_cast<float>(opt.f(4)); V.gz = static_cast<float>(opt.f(5));
@@ -334,6 +398,7 @@ inline HostModel build_host_model(const Blob &b) {
     }
   }
   V.nbr_steps = nbr_steps; V.nroot = nroot;
+  V.solve_dims = static_cast<unsigned>(nv) | (static_cast<unsigned>(nroot) << 8) | (static_cast<unsigned>(nbr_steps) << 16);  // (nv <= kMaxDof, nbr_steps <= 16)
   std::vector<unsigned int> fsched;
   {
     std::vector<int> bstart, blen;
@@ -437,6 +502,7 @@ inline HostModel build_host_model(const Blob &b) {
   }
   V.nrootrec = nrr;
   const Tensor &fe_link = b.get("fell_link");
+  if (fe_link.count > static_cast<size_t>(kMaxLink)) throw std::runtime_error("more ellipsoid fluid geoms than links");
   std::vector<float> ell(32 * (fe_link.count ? fe_link.count : 1), 0.f);
   const double kPi = 3.14159265358979323846;
   for (size_t g = 0; g < fe_link.count; g++) {
@@ -608,44 +674,11 @@ inline HostModel build_host_model(const Blob &b) {
     }
   }
   // ---- pack ------------------------------------------------------------------------------------------
-  set_off(V.d_link, A.put(d_link));
-  set_off(V.d_madr, A.put(d_madr)); set_off(V.d_depth, A.put(d_depth));
-  set_off(V.d_kind, A.put(d_kind)); set_off(V.d_qadr, A.put(d_qadr));
-  set_off(V.d_limited, A.put(d_limited)); set_off(V.d_act_id, A.put(d_act_id));
-  set_off(V.d_ndesc, A.put(d_ndesc)); set_off(V.pairtab, A.put(pairtab)); set_off(V.br_seq, A.put(br_seq)); set_off(V.fsched, A.put(fsched));
-  set_off(V.d_axis, A.put(d_axis)); set_off(V.d_arm, A.put(d_arm));
-  set_off(V.d_damp, A.put(d_damp)); set_off(V.d_stiff, A.put(d_stiff));
-  set_off(V.d_sref, A.put(d_sref)); set_off(V.d_lo, A.put(d_lo));
-  set_off(V.d_hi, A.put(d_hi)); set_off(V.d_margin, A.put(d_margin));
-  set_off(V.d_invw, A.put(d_invw)); set_off(V.d_K, A.put(d_K));
-  set_off(V.d_B, A.put(d_B)); set_off(V.d_solimp, A.put(d_solimp));
-  set_off(V.d_act_coef, A.put(d_act_coef)); set_off(V.d_qpos0, A.put(d_qpos0));
-  set_off(V.l_anc, A.put(l_anc));
-  set_off(V.l_parent, A.put(l_parent)); set_off(V.l_dofadr, A.put(l_dofadr));
-  set_off(V.l_dofnum, A.put(l_dofnum)); set_off(V.l_sub, A.put(l_sub));
-  set_off(V.l_reckind, A.put(l_reckind)); set_off(V.l_recell, A.put(l_recell));
-  set_off(V.l_pos, A.put(l_pos)); set_off(V.l_quat, A.put(l_quat));
-  set_off(V.l_ipos, A.put(l_ipos)); set_off(V.l_imat, A.put(l_imat));
-  set_off(V.l_inertia, A.put(l_inertia)); set_off(V.l_mass, A.put(l_mass));
-  set_off(V.l_recpos, A.put(l_recpos)); set_off(V.l_recmat, A.put(l_recmat));
-  set_off(V.l_reccoef, A.put(l_reccoef));
-  set_off(V.rr_pos, A.put(rr_pos)); set_off(V.rr_mat, A.put(rr_mat));
-  set_off(V.rr_coef, A.put(rr_coef)); set_off(V.ell, A.put(ell));
-  set_off(V.m_row, A.put(m_row)); set_off(V.m_col, A.put(m_col)); set_off(V.colmadr, A.put(colmadr));
-  set_off(V.a_cl, A.put(a_cl));
-  set_off(V.a_fl, A.put(a_fl)); set_off(V.a_action, A.put(a_action));
-  set_off(V.t_qadr, A.put(t_qadr)); set_off(V.t_dof, A.put(t_dof)); set_off(V.t_coef, A.put(t_coef));
-  set_off(V.a_gain, A.put(a_gain)); set_off(V.a_b0, A.put(a_b0));
-  set_off(V.a_b1, A.put(a_b1)); set_off(V.a_b2, A.put(a_b2));
-  set_off(V.a_clo, A.put(a_clo)); set_off(V.a_chi, A.put(a_chi));
-  set_off(V.a_flo, A.put(a_flo)); set_off(V.a_fhi, A.put(a_fhi));
-  set_off(V.wing_dof, A.put(wing_dof)); set_off(V.wing_qadr, A.put(wing_qadr));
-  set_off(V.wing_action, A.put(wing_action)); set_off(V.wing_ctrl, A.put(wing_ctrl));
-  set_off(V.obsj_qadr, A.put(obsj_qadr)); set_off(V.obsj_dof, A.put(obsj_dof));
-  set_off(V.qpos0, A.put(qpos0));
-  set_off(V.cg_link, A.put(cg_link)); set_off(V.cg_type, A.put(cg_type)); set_off(V.cg_pos, A.put(cg_pos)); set_off(V.cg_quat, A.put(cg_quat));
-  set_off(V.cg_size, A.put(cg_size)); set_off(V.cg_brad, A.put(cg_brad)); set_off(V.cg_invw, A.put(cg_invw)); set_off(V.cg_ush, A.put(cg_ush));
-  set_off(V.cp_pair, A.put(cp_pair)); set_off(V.l_dofmask, A.put(l_dofmask));
+#define X(n, t, c) set_off(V.n, A.place(lay::n, lay::kBytes[lay::id_##n], n, #n));
+  FFE_MODEL_TABLES(X)
+#undef X
+  set_off(V.fsched, A.tail(lay::fsched, fsched));
+  set_off(V.arena, 0);
   H.arena = A.bytes();
   return H;
 }

@@ -243,6 +243,9 @@ __device__ __forceinline__ S6 ld6a(const float *p) {
   return {a.x, a.y, b.x, b.y, c.x, c.y};
 }
 __device__ __forceinline__ int rl_i(int v, int lane_idx) { return __builtin_amdgcn_readlane(v, lane_idx); }
+__device__ __forceinline__ unsigned long long rl_u64(unsigned long long v, int lane_idx) {
+  return (unsigned long long)(unsigned)__builtin_amdgcn_readlane((int)(unsigned)v, lane_idx) | ((unsigned long long)(unsigned)__builtin_amdgcn_readlane((int)(unsigned)(v >> 32), lane_idx) << 32);
+}
 __device__ __forceinline__ float rl_f(float v, int lane_idx) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), lane_idx)); }
 // Full-wave sum, result in every lane.  Four DPP steps fold each row of 16 lanes (quad swaps, half-row mirror, row
 // mirror), then the four row totals are read with v_readlane: no LDS traffic, ~11 instructions.
@@ -386,6 +389,30 @@ __device__ __forceinline__ const DevModel FFE_CONST &model(const Ctx &c) {
   asm volatile("" : "+s"(m));
   return *m;
 }
+// The model's tables sit at fixed places of the arena whose first bytes are the struct itself (dev_model.hpp, lay::), so the struct
+// pointer a stage holds is also the base of every table: an address is that base + a constant, folded into the load's immediate or
+// one scalar add, and no table pointer is fetched from the struct ahead of the read.  Built from the stage's own (laundered) pointer,
+// the view lives and dies with the stage like everything else derived from it; what a stage does not read costs nothing.
+template <typename E>
+__device__ __forceinline__ const E FFE_GLOBAL *table_at(const DevModel FFE_CONST *m, size_t off) {
+  return (const E FFE_GLOBAL *)((const char FFE_GLOBAL *)m + off);
+}
+// Four neighbouring scalars of the struct in one s_load_dwordx4 (dev_model.hpp lays the fields out for it: 16-byte groups by stage)
+__device__ __forceinline__ int4 ld4(const int FFE_CONST *p) { return *(const int4 FFE_CONST *)p; }
+__device__ __forceinline__ float4 ld4(const float FFE_CONST *p) { return *(const float4 FFE_CONST *)p; }
+struct Tabs {
+#define X(n, t, c) const t FFE_GLOBAL *n;
+  FFE_MODEL_TABLES(X)
+#undef X
+  const unsigned int FFE_GLOBAL *fsched;
+  __device__ __forceinline__ explicit Tabs(const DevModel FFE_CONST *m) {
+#define X(n, t, c) n = table_at<t>(m, lay::n);
+    FFE_MODEL_TABLES(X)
+#undef X
+    fsched = table_at<unsigned int>(m, lay::fsched);
+  }
+};
+__device__ __forceinline__ Tabs tables(const DevModel FFE_CONST &M) { return Tabs(&M); }
 // The same for what a stage derives from the lane id and the flag word.  Every stage addresses the tile by lane (lane * 24 + &T.cdof,
 // lane * 28 + &T.lT, ...) and tests flag bits; left alone, the compiler forms all of these addresses, compare masks and decoded bits
 // once, ahead of the substep loop, runs out of registers there and parks them in scratch - to fetch each back, a memory round trip,
@@ -502,14 +529,14 @@ static_assert(sizeof(CollB<kMC>) == 1072 && sizeof(CollB<kMCX>) == 1360 && sizeo
 __device__ __forceinline__ CollA &coll_a(Tile &T) { return *reinterpret_cast<CollA *>(&T.LD[0]); }
 template <int MC> __device__ __forceinline__ CollB<MC> &coll_b(Tile &T) { return *reinterpret_cast<CollB<MC> *>(&T.lT[0][0]); }
 
-__device__ __forceinline__ cvx::Geom load_geom(const CollA &A, const DevModel FFE_CONST &M, int g) {
+__device__ __forceinline__ cvx::Geom load_geom(const CollA &A, const Tabs &Tb, int g) {
   const float4 cc = A.gc[g], qq = A.gq[g];
-  return cvx::Geom{dm::V3{cc.x, cc.y, cc.z}, dm::Q4{qq.x, qq.y, qq.z, qq.w}, M.cg_size[g], M.cg_size[kMaxGeom + g], M.cg_size[2 * kMaxGeom + g], M.cg_type[g]};
+  return cvx::Geom{dm::V3{cc.x, cc.y, cc.z}, dm::Q4{qq.x, qq.y, qq.z, qq.w}, Tb.cg_size[g], Tb.cg_size[kMaxGeom + g], Tb.cg_size[2 * kMaxGeom + g], Tb.cg_type[g]};
 }
 
 // the broad phase's per-geom constants (cvx::ushape, made on the host)
-__device__ __forceinline__ cvx::UShape ush(const DevModel FFE_CONST &M, int g) {
-  const float4 u = M.cg_ush[2 * g], k = M.cg_ush[2 * g + 1];
+__device__ __forceinline__ cvx::UShape ush(const Tabs &Tb, int g) {
+  const float4 u = Tb.cg_ush[2 * g], k = Tb.cg_ush[2 * g + 1];
   return cvx::UShape{u.x, u.y, u.z, u.w, k.x, k.y, k.z, k.w};
 }
 
@@ -525,6 +552,7 @@ template <bool WITH_RARE, int MC>
 __device__ __forceinline__ int collide_narrow(Tile &T, const DevModel FFE_CONST &M, const int lane, int n2, int nk, int ovf) {
   CollA &A = coll_a(T);
   CollB<MC> &B = coll_b<MC>(T);
+  const Tabs Tb = tables(M);
   const unsigned long long mm0 = M.cg_mmask[0], mm1 = M.cg_mmask[1];
   const float mclass = M.c_margin;
   auto pair_margin = [&](int a, int b) {
@@ -541,14 +569,14 @@ __device__ __forceinline__ int collide_narrow(Tile &T, const DevModel FFE_CONST 
     a = w & 255; b = w >> 8;
     margin = pair_margin(a, b);
     const float *kn = B.cl2n[lane];
-    const cvx::Contact ct = cvx::collide<WITH_RARE>(load_geom(A, M, a), load_geom(A, M, b), dm::V3{kn[0], kn[1], kn[2]}, kn[3] != 0.f, kn[4]);
+    const cvx::Contact ct = cvx::collide<WITH_RARE>(load_geom(A, Tb, a), load_geom(A, Tb, b), dm::V3{kn[0], kn[1], kn[2]}, kn[3] != 0.f, kn[4]);
     dist = ct.dist; nrm = ct.n; cpos = ct.pos; ctt = ct.t;
     hit = dist < margin - (margin != 0.f ? M.c_gap : 0.f);  // (mj: dist <= margin is detected, dist < margin - gap is active; an inactive one takes part in nothing here)
   }
   {
     // the pair's direction, for the next substep's bound and warm start; when the cache cannot take them all, the classes whose cold
     // search costs most go first (ellipsoid - cylinder, then ellipsoid - ellipsoid, then the capsule classes' axis parameter)
-    const int ta = M.cg_type[a], tb = M.cg_type[b];
+    const int ta = Tb.cg_type[a], tb = Tb.cg_type[b];
     const int prio = lane < n2 ? (cvx::rare_class(ta, tb) ? 2 : (ta >= cvx::ELLIPSOID ? 1 : 0)) : -1;
     const unsigned long long b2 = __ballot(prio == 2), b1 = __ballot(prio == 1), b0 = __ballot(prio == 0), below = (1ull << lane) - 1ull;
     const int pos = nk + (prio == 2 ? __popcll(b2 & below) : prio == 1 ? __popcll(b2) + __popcll(b1 & below) : __popcll(b2) + __popcll(b1) + __popcll(b0 & below));
@@ -571,29 +599,40 @@ __device__ __forceinline__ int collide_narrow(Tile &T, const DevModel FFE_CONST 
   if (hit) {
     float *o = B.rec[idx];
     o[0] = nrm.x; o[1] = nrm.y; o[2] = nrm.z; o[3] = cpos.x; o[4] = cpos.y; o[5] = cpos.z; o[6] = dist;
-    o[7] = margin - (margin != 0.f ? M.c_gap : 0.f); o[8] = M.cg_invw[a] + M.cg_invw[b];
-    o[9] = __int_as_float(M.cg_link[a]); o[10] = __int_as_float(M.cg_link[b]); o[11] = __int_as_float((int)w);
+    o[7] = margin - (margin != 0.f ? M.c_gap : 0.f); o[8] = Tb.cg_invw[a] + Tb.cg_invw[b];
+    o[9] = __int_as_float(Tb.cg_link[a]); o[10] = __int_as_float(Tb.cg_link[b]); o[11] = __int_as_float((int)w);
   }
   SYNC();
   return n | (ovf << 8) | (nk << 16);
 }
 
 
+// The two functions below are real calls (the narrow phase of the rare classes needs registers of its own), and a call hands its
+// arguments over in vector registers: read through such a copy, every scalar of the struct and every table would be a vector load from a
+// 64-bit vector address.  The pointer is the same in all lanes, so it goes back to a scalar pair once, at entry; from there the
+// struct's scalars are s_loads and the tables global loads off that pair with constant offsets, as in the kernel.
+__device__ __forceinline__ const DevModel FFE_CONST *uniform_model(const DevModel FFE_CONST *p) {
+  const unsigned long long v = (unsigned long long)p;
+  const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)v), hi = __builtin_amdgcn_readfirstlane((unsigned)(v >> 32));
+  return (const DevModel FFE_CONST *)(((unsigned long long)hi << 32) | lo);
+}
+
 template <int MC>
 __device__ __noinline__ int flight_collide_a(Tile *Tp, const DevModel FFE_CONST *Mp, const int lane, const int ncache_, const int cpid) {
   Tile &T = *Tp;
-  const DevModel FFE_CONST &M = *Mp;
+  const DevModel FFE_CONST &M = *uniform_model(Mp);
+  const Tabs Tb = tables(M);
   CollA &A = coll_a(T);
   CollB<MC> &B = coll_b<MC>(T);
   const int ncg = M.ncg;
   CSTAMP_DECL;
   for (int g = lane; g < ncg; g += kWave) {
-    const int l = M.cg_link[g];
+    const int l = Tb.cg_link[g];
     const float *lq = A.lq[l];
     const dm::Q4 xq = {lq[0], lq[1], lq[2], lq[3]};
-    const dm::V3 gp = dm::V3{T.xpos[l][0], T.xpos[l][1], T.xpos[l][2]} + dm::qrot(xq, dm::V3{M.cg_pos[g], M.cg_pos[kMaxGeom + g], M.cg_pos[2 * kMaxGeom + g]});
-    const dm::Q4 gq = dm::qnormalize(dm::qmul(xq, dm::Q4{M.cg_quat[g], M.cg_quat[kMaxGeom + g], M.cg_quat[2 * kMaxGeom + g], M.cg_quat[3 * kMaxGeom + g]}));
-    A.gc[g] = make_float4(gp.x, gp.y, gp.z, M.cg_brad[g]);
+    const dm::V3 gp = dm::V3{T.xpos[l][0], T.xpos[l][1], T.xpos[l][2]} + dm::qrot(xq, dm::V3{Tb.cg_pos[g], Tb.cg_pos[kMaxGeom + g], Tb.cg_pos[2 * kMaxGeom + g]});
+    const dm::Q4 gq = dm::qnormalize(dm::qmul(xq, dm::Q4{Tb.cg_quat[g], Tb.cg_quat[kMaxGeom + g], Tb.cg_quat[2 * kMaxGeom + g], Tb.cg_quat[3 * kMaxGeom + g]}));
+    A.gc[g] = make_float4(gp.x, gp.y, gp.z, Tb.cg_brad[g]);
     A.gq[g] = make_float4(gq.w, gq.x, gq.y, gq.z);
   }
   SYNC();
@@ -607,7 +646,7 @@ __device__ __noinline__ int flight_collide_a(Tile *Tp, const DevModel FFE_CONST 
   const int ncp = M.ncp;
   unsigned pw[kMaxPair / kWave];
 #pragma unroll
-  for (int r = 0; r < kMaxPair / kWave; r++) pw[r] = M.cp_pair[r * kWave + lane];  // (issued together: one L2 round trip, not one per round)
+  for (int r = 0; r < kMaxPair / kWave; r++) pw[r] = Tb.cp_pair[r * kWave + lane];  // (issued together: one L2 round trip, not one per round)
 #pragma unroll
   for (int r = 0; r < kMaxPair / kWave; r++) {
     const int base = r * kWave;
@@ -631,7 +670,7 @@ __device__ __noinline__ int flight_collide_a(Tile *Tp, const DevModel FFE_CONST 
   // The cache's pairs, one per lane (lane k < ncache: entry k), with the key of the borrowing rule below (first geom | second geom's type << 8)
   const int ncache = __builtin_amdgcn_readfirstlane(ncache_);
   int ckey = -1;
-  if (lane < ncache) ckey = (cpid & 255) | (M.cg_type[min((cpid >> 8) & 255, kMaxGeom - 1)] << 8);
+  if (lane < ncache) ckey = (cpid & 255) | (Tb.cg_type[min((cpid >> 8) & 255, kMaxGeom - 1)] << 8);
   int n2 = 0, nk = 0;
   bool any_rare = false;
 #pragma unroll 1
@@ -644,9 +683,9 @@ __device__ __noinline__ int flight_collide_a(Tile *Tp, const DevModel FFE_CONST 
       w = B.cl1[base + lane];
       const int a = w & 255, b = w >> 8;
       const float4 ca = A.gc[a], qa = A.gq[a], cb = A.gc[b], qb = A.gq[b];
-      const cvx::UShape sa = ush(M, a), sb = ush(M, b);
+      const cvx::UShape sa = ush(Tb, a), sb = ush(Tb, b);
       const cvx::GeomU ga = cvx::make_u(dm::V3{ca.x, ca.y, ca.z}, dm::Q4{qa.x, qa.y, qa.z, qa.w}, sa), gb = cvx::make_u(dm::V3{cb.x, cb.y, cb.z}, dm::Q4{qb.x, qb.y, qb.z, qb.w}, sb);
-      const int ta = M.cg_type[a], tb = M.cg_type[b];
+      const int ta = Tb.cg_type[a], tb = Tb.cg_type[b];
       const float margin = pair_margin(a, b), incl = margin - (margin != 0.f ? M.c_gap : 0.f);  // (only a contact inside margin - gap matters here)
       pass = cvx::separation_bound_u(ga, gb) <= incl;
       // the pair's cache entry, and the last entry of its first geom against a geom of its second one's type (wave-uniform reads of the
@@ -674,7 +713,7 @@ __device__ __noinline__ int flight_collide_a(Tile *Tp, const DevModel FFE_CONST 
         pass = !keep;
       }
     }
-    any_rare = any_rare || __ballot(pass && cvx::rare_class(M.cg_type[w & 255], M.cg_type[w >> 8])) != 0ull;
+    any_rare = any_rare || __ballot(pass && cvx::rare_class(Tb.cg_type[w & 255], Tb.cg_type[w >> 8])) != 0ull;
     const unsigned long long bal = __ballot(pass), balk = __ballot(keep);
     const int idx = n2 + __popcll(bal & ((1ull << lane) - 1ull)), idk = nk + __popcll(balk & ((1ull << lane) - 1ull));
     if (pass && idx < kCL2) { B.cl2[idx] = (unsigned short)w; float *o = B.cl2n[idx]; o[0] = kn.x; o[1] = kn.y; o[2] = kn.z; o[3] = have_kn ? 1.f : 0.f; o[4] = kt; }
@@ -696,7 +735,7 @@ __device__ __noinline__ int flight_collide_a(Tile *Tp, const DevModel FFE_CONST 
 // the same with every pair class (entered only when the broad phase left an ellipsoid - cylinder or cylinder - cylinder pair)
 template <int MC>
 __device__ __noinline__ int flight_collide_b(Tile *Tp, const DevModel FFE_CONST *Mp, const int lane, const int packed) {
-  return collide_narrow<true, MC>(*Tp, *Mp, lane, packed & 0xff, (packed >> 8) & 0xff, (packed >> 16) & 1);
+  return collide_narrow<true, MC>(*Tp, *uniform_model(Mp), lane, packed & 0xff, (packed >> 8) & 0xff, (packed >> 16) & 1);
 }
 
 // the position stage's collision: cache in, contacts + cache out (lane-resident, see Ctx)
@@ -739,19 +778,20 @@ __device__ __forceinline__ void flight_collide(Ctx &c) {
 // mj_comVel, mj_passive, mj_rne).  Needs T.qpos / T.qvel; leaves cdof, cdofd, xpos, xmat, M, f_smooth_nb.
 __device__ __forceinline__ void stage1(Ctx &c) {
   const DevModel FFE_CONST &M = model(c);
+  const Tabs Tb = tables(M);
   Tile &T = c.T;
   const int lane = stage_lane(c), flags = stage_flags(c);
   const bool is_link = lane < M.nlink, is_dof = lane < M.nv;
-  const int l_dofadr = M.l_dofadr[lane], l_dofnum = M.l_dofnum[lane], l_sub = M.l_sub[lane];
-  const int d_link = M.d_link[lane], d_kind = M.d_kind[lane];
-  const unsigned anc_lo = M.l_anc[lane], anc_hi = M.l_anc[kLanePad + lane];  // ancestor links, nearest first, 0xff = none
+  const int l_dofadr = Tb.l_dofadr[lane], l_dofnum = Tb.l_dofnum[lane], l_sub = Tb.l_sub[lane];
+  const int d_link = Tb.d_link[lane], d_kind = Tb.d_kind[lane];
+  const unsigned anc_lo = Tb.l_anc[lane], anc_hi = Tb.l_anc[kLanePad + lane];  // ancestor links, nearest first, 0xff = none
   STAMP(8);  // everything between the last stamp and a stage 1 (integration, sensors, ghost, prologue)
   // inertial constants of this lane's link, needed after the frame composition below: requested now, so that their L2 round
   // trip runs under the kinematics instead of after its last hand-off
-  const int d_plink_ = M.l_parent[d_link], d_dof0_ = M.l_dofadr[d_link];  // (V3 below: parent link and first dof of this dof's link)
-  const float l_mass_ = M.l_mass[lane];
-  const V3 l_ipos_ = ldv_lane(M.l_ipos, lane), l_inertia_ = ldv_lane(M.l_inertia, lane);
-  const M3 l_imat_ = ldm_lane(M.l_imat, lane);
+  const int d_plink_ = Tb.l_parent[d_link], d_dof0_ = Tb.l_dofadr[d_link];  // (V3 below: parent link and first dof of this dof's link)
+  const float l_mass_ = Tb.l_mass[lane];
+  const V3 l_ipos_ = ldv_lane(Tb.l_ipos, lane), l_inertia_ = ldv_lane(Tb.l_inertia, lane);
+  const M3 l_imat_ = ldm_lane(Tb.l_imat, lane);
 
   // ---- K1: link frame in its parent (joint rotations folded in) + hinge axes in the final link frame
   if (is_link) {
@@ -769,7 +809,7 @@ __device__ __forceinline__ void stage1(Ctx &c) {
 #pragma unroll
       for (int j = 0; j < 3; j++) {
         const int d = l_dofadr + (j < l_dofnum ? j : 0);
-        jax[j] = ldv_lane(M.d_axis, d); jqa[j] = M.d_qadr[d]; jq0[j] = M.d_qpos0[d];
+        jax[j] = ldv_lane(Tb.d_axis, d); jqa[j] = Tb.d_qadr[d]; jq0[j] = Tb.d_qpos0[d];
       }
 #pragma unroll
       for (int j = 2; j >= 0; j--) {
@@ -780,8 +820,8 @@ __device__ __forceinline__ void stage1(Ctx &c) {
           qr = qmul(axis_angle(jax[j], T.qpos[jqa[j]] - jq0[j]), qr);
         }
       }
-      q = qmul(Q4{M.l_quat[lane], M.l_quat[kLanePad + lane], M.l_quat[2 * kLanePad + lane], M.l_quat[3 * kLanePad + lane]}, qr);
-      p = ldv_lane(M.l_pos, lane);
+      q = qmul(Q4{Tb.l_quat[lane], Tb.l_quat[kLanePad + lane], Tb.l_quat[2 * kLanePad + lane], Tb.l_quat[3 * kLanePad + lane]}, qr);
+      p = ldv_lane(Tb.l_pos, lane);
     }
     float *o = T.lT[lane];
     o[0] = p.x; o[1] = p.y; o[2] = p.z; o[3] = q.w; o[4] = q.x; o[5] = q.y; o[6] = q.z;
@@ -912,7 +952,7 @@ __device__ __forceinline__ void stage1(Ctx &c) {
       const int a = (int)(((it < 4 ? anc_lo : anc_hi) >> (8 * (it & 3))) & 0xffu);
       if (a != 0xff) cacc = cacc + ld6(T.la[a]);
     }
-    if (!(flags & FFE_NO_GRAVITY)) { cacc.l0 -= M.gx; cacc.l1 -= M.gy; cacc.l2 -= M.gz; }
+    if (!(flags & FFE_NO_GRAVITY)) { const float4 g = ld4(&M.gx); cacc.l0 -= g.x; cacc.l1 -= g.y; cacc.l2 -= g.z; }
     const I10 cin2 = ld10(T.cinert[lane]);
     const S6 cvel2 = ld6(T.lb[lane]);
     frc = mul_inert(cin2, cacc) + cross_force(cvel2, mul_inert(cin2, cvel2));
@@ -928,14 +968,14 @@ __device__ __forceinline__ void stage1(Ctx &c) {
     const V3 w_b = mtv(xm2, w_w), v_b = mtv(xm2, lin(cvel3) + cross(w_w, off));
     S6 wl = zero6();
     if (is_link) {
-      const int kind = M.l_reckind[lane];
-      if (kind == 1) wl = box_fluid_local(M.l_reccoef, lane, ldv_lane(M.l_recpos, lane), ldm_lane(M.l_recmat, lane), w_b, v_b);
-      else if (kind == 2) wl = ell_fluid_local(M.ell + 32 * M.l_recell[lane], ldv_lane(M.l_recpos, lane), ldm_lane(M.l_recmat, lane), w_b, v_b);
+      const int kind = Tb.l_reckind[lane];
+      if (kind == 1) wl = box_fluid_local(Tb.l_reccoef, lane, ldv_lane(Tb.l_recpos, lane), ldm_lane(Tb.l_recmat, lane), w_b, v_b);
+      else if (kind == 2) wl = ell_fluid_local(Tb.ell + 32 * Tb.l_recell[lane], ldv_lane(Tb.l_recpos, lane), ldm_lane(Tb.l_recmat, lane), w_b, v_b);
     }
     // bodies welded to the root link: one inertia-box record per lane, summed across the wave in root-link axes
     const V3 w0 = {rl_f(w_b.x, 0), rl_f(w_b.y, 0), rl_f(w_b.z, 0)}, v0 = {rl_f(v_b.x, 0), rl_f(v_b.y, 0), rl_f(v_b.z, 0)};
     S6 wr = zero6();
-    if (lane < M.nrootrec) wr = box_fluid_local(M.rr_coef, lane, ldv_lane(M.rr_pos, lane), ldm_lane(M.rr_mat, lane), w0, v0);
+    if (lane < M.nrootrec) wr = box_fluid_local(Tb.rr_coef, lane, ldv_lane(Tb.rr_pos, lane), ldm_lane(Tb.rr_mat, lane), w0, v0);
     wr = wave_sum6(wr);
     if (lane == 0) wl = wl + wr;
     if (is_link) {
@@ -976,9 +1016,9 @@ __device__ __forceinline__ void stage1(Ctx &c) {
     float bias = dot6(cd2, ld6(T.la[d_link]));
     float f = -bias;
     if (d_kind == 2) {
-      if (!(flags & FFE_NO_SPRING)) f -= M.d_stiff[lane] * (T.qpos[M.d_qadr[lane]] - M.d_sref[lane]);
+      if (!(flags & FFE_NO_SPRING)) f -= Tb.d_stiff[lane] * (T.qpos[Tb.d_qadr[lane]] - Tb.d_sref[lane]);
     }
-    if (!(flags & FFE_NO_DAMPER)) f -= M.d_damp[lane] * T.qvel[lane];
+    if (!(flags & FFE_NO_DAMPER)) f -= Tb.d_damp[lane] * T.qvel[lane];
     c.f_smooth_nb = f;
     st6(T.buf[lane], mul_inert(ld10(T.crb[d_link]), cd2));
   }
@@ -1003,6 +1043,7 @@ static_assert(offsetof(Tile, la) % 8 == 0 && sizeof(Tile::la) + sizeof(Tile::lb)
 template <bool DUAL>
 __device__ __forceinline__ void bfactor(Ctx &c, float add0, float add1) {
   const DevModel FFE_CONST &M = model(c);
+  const Tabs Tb = tables(M);
   Tile &T = c.T;
   const int lane = stage_lane(c);
   const int nv = M.nv;
@@ -1014,15 +1055,15 @@ __device__ __forceinline__ void bfactor(Ctx &c, float add0, float add1) {
     for (int r = 0; r < 7; r++) {
       const int e = lane + r * kWave;
       const bool ok = e < M.nM;
-      ei[r] = ok ? M.m_row[e] : 0;
-      ej[r] = ok ? M.m_col[e] : 0;
+      ei[r] = ok ? Tb.m_row[e] : 0;
+      ej[r] = ok ? Tb.m_col[e] : 0;
     }
 #pragma unroll
     for (int r = 0; r < 7; r++) {
       const int e = lane + r * kWave;
       if (e < M.nM) {
         float m = dot6(ld6a(T.cdof[ej[r]]), ld6a(T.buf[ei[r]]));
-        if (ei[r] == ej[r]) m += M.d_arm[ei[r]] + (DBG(c, DBG_SKIP_MENTRIES) ? 1.f : 0.f);
+        if (ei[r] == ej[r]) m += Tb.d_arm[ei[r]] + (DBG(c, DBG_SKIP_MENTRIES) ? 1.f : 0.f);
         if (DUAL) T.LD[e] = make_float2(m, m); else T.LD[e].x = m;
       }
     }
@@ -1038,7 +1079,7 @@ __device__ __forceinline__ void bfactor(Ctx &c, float add0, float add1) {
   SYNC();
   STAMP(4);  // M entries
   if (!DBG(c, DBG_SKIP_FACTOR)) {
-    const unsigned FFE_GLOBAL *tab = M.fsched + lane;
+    const unsigned FFE_GLOBAL *tab = Tb.fsched + lane;
     const int nbr_rounds = M.fs_branch_rounds, nrounds = M.fs_rounds;
     auto round = [&](unsigned w) {
       if (w >> 31) {
@@ -1117,10 +1158,11 @@ __device__ __forceinline__ int bperm_i(int v, int src_lane) { return __builtin_a
 // right-hand sides (`rhs`, `rhs_b`) through factor .x at once (the contact columns of stage 2)
 template <int MODE>
 __device__ __forceinline__ float2 bsolve(Ctx &c, float rhs, float rhs_b = 0.f) {
-  const DevModel FFE_CONST &M = *c.Mp;  // (three uniform scalars only: no need to launder the table pointer here)
+  const DevModel FFE_CONST &M = *c.Mp;  // (one uniform word only: no need to launder the table pointer here)
   Tile &T = c.T;
   const int lane = stage_lane(c);
-  const int nv = M.nv, nroot = M.nroot, nbr = M.nbr_steps;
+  const unsigned dims = M.solve_dims;  // one fetch for the three
+  const int nv = dims & 0xff, nroot = (dims >> 8) & 0xff, nbr = dims >> 16;
   const bool is_dof = lane < nv, branch = is_dof && lane >= nroot;
   const int d_madr = c.la_pack & 0x3ff, dep = (c.la_pack >> 10) & 0x3f, d_ndesc = c.la_pack >> 16;
   const int my_end = lane + d_ndesc, my_md = d_madr + dep;
@@ -1217,27 +1259,28 @@ template <int MC>
 __device__ __forceinline__ V3 stage2(Ctx &c, float qfrc_act, bool integrate, bool with_ghost, double ghost_accel_z, unsigned long long &lo_mask,
                      unsigned long long &hi_mask, unsigned long long &in_lo, unsigned long long &in_hi, int &iters_out) {
   const DevModel FFE_CONST &M = model(c);
+  const Tabs Tb = tables(M);
   Tile &T = c.T;
   const int lane = stage_lane(c), flags = stage_flags(c);
   // the factor / solve index words are stage-2 business only: re-read here, they are not carried through stage 1
-  c.la_pack = (unsigned)M.d_madr[lane] | ((unsigned)M.d_depth[lane] << 10) | ((unsigned)M.d_ndesc[lane] << 16);
-  c.seq0 = M.br_seq[lane]; c.seq1 = M.br_seq[kWave + lane]; c.seq2 = M.br_seq[2 * kWave + lane]; c.seq3 = M.br_seq[3 * kWave + lane];
+  c.la_pack = (unsigned)Tb.d_madr[lane] | ((unsigned)Tb.d_depth[lane] << 10) | ((unsigned)Tb.d_ndesc[lane] << 16);
+  c.seq0 = Tb.br_seq[lane]; c.seq1 = Tb.br_seq[kWave + lane]; c.seq2 = Tb.br_seq[2 * kWave + lane]; c.seq3 = Tb.br_seq[3 * kWave + lane];
   const bool is_dof = lane < M.nv;
-  const int d_kind = M.d_kind[lane];
+  const int d_kind = Tb.d_kind[lane];
   const float h = M.h;
   float f = is_dof ? c.f_smooth_nb + qfrc_act : 0.f;
   float qp = 0.f, qv = 0.f;
-  if (is_dof) { qv = T.qvel[lane]; if (d_kind == 2) qp = T.qpos[M.d_qadr[lane]]; }
+  if (is_dof) { qv = T.qvel[lane]; if (d_kind == 2) qp = T.qpos[Tb.d_qadr[lane]]; }
 
   // ---- mj_instantiateLimit / mj_makeImpedance / mj_referenceConstraint for this lane's hinge
   bool ex_lo = false, ex_hi = false;
   float D_lo = 0.f, D_hi = 0.f, ar_lo = 0.f, ar_hi = 0.f;
-  if (is_dof && d_kind == 2 && M.d_limited[lane] && !(flags & FFE_NO_LIMIT)) {
-    float margin = M.d_margin[lane];
-    float dist_lo = qp - M.d_lo[lane], dist_hi = M.d_hi[lane] - qp;
-    float dmin = M.d_solimp[lane], dmax = M.d_solimp[kLanePad + lane], width = M.d_solimp[2 * kLanePad + lane],
-          mid = M.d_solimp[3 * kLanePad + lane], power = M.d_solimp[4 * kLanePad + lane];
-    float K = M.d_K[lane], B = M.d_B[lane], iw = M.d_invw[lane];
+  if (is_dof && d_kind == 2 && Tb.d_limited[lane] && !(flags & FFE_NO_LIMIT)) {
+    float margin = Tb.d_margin[lane];
+    float dist_lo = qp - Tb.d_lo[lane], dist_hi = Tb.d_hi[lane] - qp;
+    float dmin = Tb.d_solimp[lane], dmax = Tb.d_solimp[kLanePad + lane], width = Tb.d_solimp[2 * kLanePad + lane],
+          mid = Tb.d_solimp[3 * kLanePad + lane], power = Tb.d_solimp[4 * kLanePad + lane];
+    float K = Tb.d_K[lane], B = Tb.d_B[lane], iw = Tb.d_invw[lane];
     if (dist_lo < margin) {
       ex_lo = true;
       float imp = impedance(dmin, dmax, width, mid, power, dist_lo, margin);
@@ -1264,7 +1307,7 @@ __device__ __forceinline__ V3 stage2(Ctx &c, float qfrc_act, bool integrate, boo
   float a = 0.f, ae = 0.f, fc = 0.f;
   int iters = 0;
   const bool want_euler = integrate && !(flags & FFE_NO_DAMPER);
-  const float hB = (is_dof && want_euler) ? h * M.d_damp[lane] : 0.f;
+  const float hB = (is_dof && want_euler) ? h * Tb.d_damp[lane] : 0.f;
   // ---- contact rows of this position stage (mj: mj_makeConstraint for condim-1 contacts: one frictionless row each,
   //      J = n . (jacp of geom2's body - jacp of geom1's at the contact point), mj_makeImpedance, mj_referenceConstraint).  The row is
   //      kept by columns: this lane's dof entry of every contact's row in jk[]; lane k computes contact k's D and aref.
@@ -1277,11 +1320,15 @@ __device__ __forceinline__ V3 stage2(Ctx &c, float qfrc_act, bool integrate, boo
     const V3 com = get_com(c);
     float dmin = fminf(fmaxf(M.c_solimp[0], 1e-4f), 0.9999f), dmax = fminf(fmaxf(M.c_solimp[1], 1e-4f), 0.9999f), width = fmaxf(0.f, M.c_solimp[2]),
           mid = fminf(fmaxf(M.c_solimp[3], 1e-4f), 0.9999f), power = fmaxf(1.f, M.c_solimp[4]);
+    // the dof masks of the contacts' links: lane k fetches those of contact k, both reads in flight at once and ahead of the loop
+    // (read per contact with the link broadcast first, each was a scalar fetch the loop's next instruction waited for)
+    unsigned long long lm1 = 0ull, lm2 = 0ull;
+    if (lane < nct) { lm1 = Tb.l_dofmask[c.ct_l1]; lm2 = Tb.l_dofmask[c.ct_l2]; }
 #pragma unroll
     for (int k = 0; k < MC; k++) {
       if (k < nct) {
         const V3 n = {rl_f(c.ct_nx, k), rl_f(c.ct_ny, k), rl_f(c.ct_nz, k)}, p = {rl_f(c.ct_px, k), rl_f(c.ct_py, k), rl_f(c.ct_pz, k)};
-        const unsigned long long m1 = M.l_dofmask[rl_i(c.ct_l1, k)], m2 = M.l_dofmask[rl_i(c.ct_l2, k)];
+        const unsigned long long m1 = rl_u64(lm1, k), m2 = rl_u64(lm2, k);
         const int sg = (int)((m2 >> lane) & 1ULL) - (int)((m1 >> lane) & 1ULL);
         if (is_dof && sg != 0) { const V3 u = lin(cd) + cross(ang(cd), p - com); jk[k] = (float)sg * dot(n, u); }
         const float vel = wave_sum(jk[k] * qv);
@@ -1481,7 +1528,7 @@ __device__ __forceinline__ V3 stage2(Ctx &c, float qfrc_act, bool integrate, boo
   V3 accel;
   {
     V3 ao = {__shfl(a, 0), __shfl(a, 1), __shfl(a, 2)};
-    if (!(flags & FFE_NO_GRAVITY)) { ao.x -= M.gx; ao.y -= M.gy; ao.z -= M.gz; }
+    if (!(flags & FFE_NO_GRAVITY)) { const float4 g = ld4(&M.gx); ao.x -= g.x; ao.y -= g.y; ao.z -= g.z; }
     accel = mtv(ldm(T.xmat[0]), ao);
   }
   if (!integrate) return accel;
@@ -1489,7 +1536,7 @@ __device__ __forceinline__ V3 stage2(Ctx &c, float qfrc_act, bool integrate, boo
   if (is_dof) {
     float nv_ = qv + h * ae;
     T.qvel[lane] = nv_;
-    if (d_kind == 2) T.qpos[M.d_qadr[lane]] = qp + h * nv_;
+    if (d_kind == 2) T.qpos[Tb.d_qadr[lane]] = qp + h * nv_;
   }
   SYNC();
   // Free-joint and ghost integration, one instruction stream for both: lanes 0-2 advance the root position, lanes 3-5
@@ -1527,14 +1574,16 @@ __device__ __forceinline__ V3 stage2(Ctx &c, float qfrc_act, bool integrate, boo
 // per substep only the length / velocity terms of the affine bias remain (velocity only if some actuator has a bias2).
 __device__ __forceinline__ float actuation_base(Ctx &c, float ctrl) {
   const DevModel FFE_CONST &M = model(c);
+  const Tabs Tb = tables(M);
   const int lane = c.lane;
   if ((c.flags & FFE_NO_ACTUATION) || lane >= M.nu) return 0.f;
-  const float clo = M.a_clo[lane], chi = M.a_chi[lane];
-  ctrl = M.a_cl[lane] ? fminf(fmaxf(ctrl, clo), chi) : ctrl;
-  return M.a_gain[lane] * ctrl + M.a_b0[lane];
+  const float clo = Tb.a_clo[lane], chi = Tb.a_chi[lane];
+  ctrl = Tb.a_cl[lane] ? fminf(fmaxf(ctrl, clo), chi) : ctrl;
+  return Tb.a_gain[lane] * ctrl + Tb.a_b0[lane];
 }
 __device__ __forceinline__ float actuation(Ctx &c, float abase) {
   const DevModel FFE_CONST &M = model(c);
+  const Tabs Tb = tables(M);
   Tile &T = c.T;
   const int lane = stage_lane(c), flags = stage_flags(c);
   if (flags & FFE_NO_ACTUATION) return 0.f;
@@ -1545,11 +1594,11 @@ __device__ __forceinline__ float actuation(Ctx &c, float abase) {
     const bool use_vel = M.any_b2 != 0;  // uniform
 #pragma unroll
     for (int w = 0; w < kMaxWrap; w++) {  // zero-padded transmission terms: joint actuators have one, fixed tendons several
-      tq[w] = M.t_qadr[w * kMaxAct + lane]; tc[w] = M.t_coef[w * kMaxAct + lane];
-      td[w] = use_vel ? M.t_dof[w * kMaxAct + lane] : 0;
+      tq[w] = Tb.t_qadr[w * kMaxAct + lane]; tc[w] = Tb.t_coef[w * kMaxAct + lane];
+      td[w] = use_vel ? Tb.t_dof[w * kMaxAct + lane] : 0;
     }
-    const int fl = M.a_fl[lane];
-    const float b1 = M.a_b1[lane], b2 = use_vel ? M.a_b2[lane] : 0.f, flo = M.a_flo[lane], fhi = M.a_fhi[lane];
+    const int fl = Tb.a_fl[lane];
+    const float b1 = Tb.a_b1[lane], b2 = use_vel ? Tb.a_b2[lane] : 0.f, flo = Tb.a_flo[lane], fhi = Tb.a_fhi[lane];
     // phase 2
     float len = 0.f, vel = 0.f;
 #pragma unroll
@@ -1561,9 +1610,9 @@ __device__ __forceinline__ float actuation(Ctx &c, float abase) {
   SYNC();
   float q = 0.f;
   if (lane < M.nv) {
-    int a0 = M.d_act_id[lane], a1 = M.d_act_id[kLanePad + lane];
-    if (a0 >= 0) q += M.d_act_coef[lane] * T.frc[a0];
-    if (a1 >= 0) q += M.d_act_coef[kLanePad + lane] * T.frc[a1];
+    int a0 = Tb.d_act_id[lane], a1 = Tb.d_act_id[kLanePad + lane];
+    if (a0 >= 0) q += Tb.d_act_coef[lane] * T.frc[a0];
+    if (a1 >= 0) q += Tb.d_act_coef[kLanePad + lane] * T.frc[a1];
   }
   SYNC();
   return q;
@@ -1623,6 +1672,7 @@ __device__ __forceinline__ ObsLayout obs_layout(int nj, int nref) {
 __device__ __forceinline__ void write_obs(Ctx &c, const TaskDev FFE_CONST &K, float *obs, V3 s_acc, V3 s_gyro, V3 s_vel, int traj_row0, int step_counter,
                           float &com_dist, Q4 &rq0) {
   const DevModel FFE_CONST &M = model(c);
+  const Tabs Tb = tables(M);
   Tile &T = c.T;
   const int lane = c.lane;
   const int nref = K.future_steps + 1;
@@ -1634,8 +1684,8 @@ __device__ __forceinline__ void write_obs(Ctx &c, const TaskDev FFE_CONST &K, fl
     obs[L.zaxis] = T.xmat[0][6]; obs[L.zaxis + 1] = T.xmat[0][7]; obs[L.zaxis + 2] = T.xmat[0][8];
   }
   if (lane < M.nobsj) {
-    obs[L.jpos + lane] = T.qpos[M.obsj_qadr[lane]];
-    obs[L.jvel + lane] = T.qvel[M.obsj_dof[lane]];
+    obs[L.jpos + lane] = T.qpos[Tb.obsj_qadr[lane]];
+    obs[L.jvel + lane] = T.qvel[Tb.obsj_dof[lane]];
   }
   float cd = 0.f;
   Q4 r0 = {1.f, 0.f, 0.f, 0.f};
@@ -1655,10 +1705,11 @@ __device__ __forceinline__ void write_obs(Ctx &c, const TaskDev FFE_CONST &K, fl
 
 __device__ __forceinline__ void load_lane_consts(Ctx &c) {
   const DevModel FFE_CONST &M = *c.Mp;
+  const Tabs Tb = tables(M);
   c.dinv[0] = c.dinv[1] = 0.f;
-  c.la_pack = (unsigned)M.d_madr[c.lane] | ((unsigned)M.d_depth[c.lane] << 10) | ((unsigned)M.d_ndesc[c.lane] << 16);
-  c.seq0 = M.br_seq[c.lane]; c.seq1 = M.br_seq[kWave + c.lane]; c.seq2 = M.br_seq[2 * kWave + c.lane]; c.seq3 = M.br_seq[3 * kWave + c.lane];
-  for (int e = c.lane; e < M.nM; e += kWave) c.T.colmadr[e] = M.colmadr[e];  // (host table: no dependent index chase at launch)
+  c.la_pack = (unsigned)Tb.d_madr[c.lane] | ((unsigned)Tb.d_depth[c.lane] << 10) | ((unsigned)Tb.d_ndesc[c.lane] << 16);
+  c.seq0 = Tb.br_seq[c.lane]; c.seq1 = Tb.br_seq[kWave + c.lane]; c.seq2 = Tb.br_seq[2 * kWave + c.lane]; c.seq3 = Tb.br_seq[3 * kWave + c.lane];
+  for (int e = c.lane; e < M.nM; e += kWave) c.T.colmadr[e] = Tb.colmadr[e];  // (host table: no dependent index chase at launch)
 }
 
 // ------------------------------------------------------------------------------------------------ the step kernel
@@ -1675,6 +1726,7 @@ __global__ __launch_bounds__(kWave, FFE_WAVES_PER_SIMD) void flight_step_kernel(
   const DevModel FFE_CONST *Mp = (const DevModel FFE_CONST *)Mp_;
   const TaskDev FFE_CONST *Kp = (const TaskDev FFE_CONST *)Kp_;
   const DevModel FFE_CONST &M = *Mp;
+  const Tabs Tb = tables(M);
   const TaskDev FFE_CONST &K = *Kp;
   if ((int)blockIdx.x >= batch) return;
   TRACE_BEGIN;
@@ -1767,7 +1819,7 @@ __global__ __launch_bounds__(kWave, FFE_WAVES_PER_SIMD) void flight_step_kernel(
     const int row0 = K.traj_off[traj_idx];
     traj_row0 = row0;
     const double *rq = K.ref_qpos + (size_t)row0 * 7, *rv = K.ref_qvel + (size_t)row0 * 6;
-    if (lane < kMaxDof + 4) { T.qpos[lane] = lane < M.nq ? M.qpos0[lane] : 0.f; T.qvel[lane] = 0.f; }
+    if (lane < kMaxDof + 4) { T.qpos[lane] = lane < M.nq ? Tb.qpos0[lane] : 0.f; T.qvel[lane] = 0.f; }
     SYNC();
     if (lane == 0) {
       T.qpos[3] = (float)rq[3]; T.qpos[4] = (float)rq[4]; T.qpos[5] = (float)rq[5]; T.qpos[6] = (float)rq[6];
@@ -1777,8 +1829,8 @@ __global__ __launch_bounds__(kWave, FFE_WAVES_PER_SIMD) void flight_step_kernel(
     if (lane < 3) T.rootpos[lane] = rq[lane];
     if (lane < M.nwing) {
       float q0 = K.traj[(size_t)(off + wb_step) * 6 + lane], q1 = K.traj[(size_t)(off + nxt) * 6 + lane];
-      T.qpos[M.wing_qadr[lane]] = q0;
-      T.qvel[M.wing_dof[lane]] = (float)(((double)q1 - (double)q0) / K.dt_ctrl);
+      T.qpos[Tb.wing_qadr[lane]] = q0;
+      T.qvel[Tb.wing_dof[lane]] = (float)(((double)q1 - (double)q0) / K.dt_ctrl);
     }
     lo_mask = hi_mask = in_lo = in_hi = 0ULL;
     SYNC();
@@ -1794,7 +1846,7 @@ __global__ __launch_bounds__(kWave, FFE_WAVES_PER_SIMD) void flight_step_kernel(
     // issued here in one batch, next to the state's own vectors: the prologue is a chain of dependent memory round trips at the
     // moment all resident waves start together, and each level removed from it is a microsecond or more per wave.
     const float *a_in = act + (size_t)env * M.naction;
-    const int ai = lane < M.nu ? M.a_action[lane] : -1;
+    const int ai = lane < M.nu ? Tb.a_action[lane] : -1;
     float a_raw = ai >= 0 ? a_in[ai] : 0.f;
     float au_raw = a_in[M.user_action];
     const int step1 = wb_step + 1 < wb_len ? wb_step + 1 : 0;
@@ -1834,8 +1886,8 @@ __global__ __launch_bounds__(kWave, FFE_WAVES_PER_SIMD) void flight_step_kernel(
     SYNC();
     if (lane < M.nwing) {
       // action[wings] += target - qpos[wing]; the wing actuators are the ctrl slots fed by those action entries
-      float add = tgt - T.qpos[M.wing_qadr[lane]];
-      const int u = M.wing_ctrl[lane];  // the ctrl slot fed by this wing's action entry
+      float add = tgt - T.qpos[Tb.wing_qadr[lane]];
+      const int u = Tb.wing_ctrl[lane];  // the ctrl slot fed by this wing's action entry
       if (u >= 0) T.ctrl[u] += add;
     }
     SYNC();
@@ -2223,7 +2275,9 @@ std::unique_ptr<EnvBackend> flight_create(const void *model_blob, size_t blob_si
   K.seed = seed; K.env_id_base = env_id_base;
   K.obs_dim = 12 + 2 * h->dm.nobsj + 7 * (t.future_steps + 1);
   h->host.nobs = K.obs_dim;
-  h->dm_dev = h->upload(&h->dm, 1);
+  // the struct is the head of the arena: the kernels take one pointer for the scalars and the tables
+  HIP_OK(hipMemcpy(h->arena, &h->dm, sizeof(DevModel), hipMemcpyHostToDevice));
+  h->dm_dev = reinterpret_cast<DevModel *>(h->arena);
   h->task_dev = h->upload(&h->task, 1);
   h->states = h->alloc<unsigned char>(h->state_stride * (size_t)batch);
   h->order = h->alloc<int>((size_t)batch);
