@@ -21,7 +21,7 @@ PER_SOURCE_FLAGS = {
     "walk_self_env.hip": ["-mllvm", "-sink-insts-to-avoid-spills=1"],  # likewise
     "walk_imit_self_env.hip": ["-mllvm", "-sink-insts-to-avoid-spills=1"],  # likewise
 }
-HEADERS = ["handle.hpp", "env_backend.hpp", "fly_env.hpp", "dev_model.hpp", "ball_model.hpp", "ball_env.hpp", "leg_dyn.hpp", "leg_stage1.inc", "row_newton.hpp", "walk_model.hpp", "walk_env.hpp", "walk_imu.hpp", "walk_floor.hpp", "walk_self.hpp", "walk_self_model.hpp", "walk_substeps.hpp", "walk_sense.hpp", "walk_self_sense.hpp", "dev_math.hpp", "convex.hpp", "launch_order.hpp", "nstep_ring.hpp", "walk_task.hpp", os.path.join("..", "..", "include", "flybody_env.h")]
+HEADERS = ["handle.hpp", "env_backend.hpp", "fly_env.hpp", "dev_model.hpp", "ball_model.hpp", "ball_env.hpp", "leg_dyn.hpp", "leg_stage1.inc", "row_newton.hpp", "walk_model.hpp", "walk_env.hpp", "walk_imu.hpp", "walk_floor.hpp", "walk_self.hpp", "walk_self_model.hpp", "walk_substeps.hpp", "self_pairs.hpp", "walk_sense.hpp", "walk_self_sense.hpp", "dev_math.hpp", "convex.hpp", "launch_order.hpp", "nstep_ring.hpp", "walk_task.hpp", os.path.join("..", "..", "include", "flybody_env.h")]
 
 
 def needs_build() -> bool:

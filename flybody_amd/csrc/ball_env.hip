@@ -48,7 +48,7 @@ struct alignas(16) BState {
   int step_bits;  // validity (ffe_get_validity): the overflow bits of the last launch alone (`overflow` is their OR over the episode)
   unsigned con_hist[2];  // active (inside includemargin) contacts of each of the control step's first 16 substeps, 4 bits each: parity tooling
   unsigned det_hist[2];  // detected (inside margin) contacts of its first 12 substeps, 5 bits each
-  float sd_n[NSD][4];    // separating-direction cache of the convex pairs (convex_collide)
+  float sd_n[NSD][4];    // separating-direction cache of the convex pairs (convex_pairs)
   unsigned short sd_pid[NSD];
   int sd_cnt, ws_n;
   int ep_flagged, pad2;  // control steps of the current episode whose launch raised an overflow bit
@@ -102,7 +102,7 @@ struct alignas(16) BTile {
   float r_sgn[RMAX], r_D[RMAX];
   unsigned char r_blk[RMAX], r_col[RMAX], r_dof[RMAX], rowof[NBLK][KCOL];
   float sens[24];  // running sums of the buffered sensors: force 18, touch 6
-  // separating directions of the convex pairs that reached the narrow phase, kept from substep to substep (convex_collide)
+  // separating directions of the convex pairs that reached the narrow phase, kept from substep to substep (convex_pairs)
   float sd_n[NSD][4];  // direction | the capsule's axis parameter of a capsule - convex pair
   unsigned short sd_pid[NSD];
   int sd_cnt;
@@ -131,7 +131,7 @@ struct Ctx {
   Q4 bq;
   V3 bw, btau;
   int nc, nact;           // ball contacts detected / of those, the ones inside includemargin (they get constraint rows)
-  int nsc;                // fly-fly contacts of this substep: slots nc .. nc + nsc - 1 of the contact arrays (see self_collide)
+  int nsc;                // fly-fly contacts of this substep: slots nc .. nc + nsc - 1 of the contact arrays (see prim_pairs)
   int ndrop;              // detected fly-fly contacts without a slot (inactive, no adhesion actuator involved)
   float wsl[3], wsc[3];   // warm start of the constraint solver: last substep's limit force per slot, contact force of this link
   int have_ws, overflow;
@@ -145,141 +145,53 @@ struct Ctx {
 
 #include "leg_dyn.hpp"  // BF_* flags, slot_on / l_parent / l_ndof / model, impedance, factor2 / solve4 / solve_dual
 #include "row_newton.hpp"  // the constraint solve (row_newton<RB, ConeRows>), cone_force, qcqp2
+#include "self_pairs.hpp"  // prim_pairs, convex_pairs, load_geom
 
 namespace ffb {
 
 
 // ------------------------------------------------------------------------------------------------ fly-fly collision
-// mj: mj_collision narrow phase for the fly's own sphere / capsule pairs: mjc_CapsuleCapsule (closest points of the two
-// segments, one contact; a sphere is a capsule of zero length, for which the same formulas reduce to mjc_SphereCapsule /
-// mjraw_SphereSphere).  Broad phase = MuJoCo's bounding-sphere test.  A detected contact (dist <= margin) takes the next
-// free slot of the contact arrays after the ball contacts: c_link = link of geom1 | link of geom2 << 8, c_frame[0..2] =
-// normal from geom1 to geom2, c_par = {K, B, invweight, 0, margin - gap}.  Returns the number of fly-fly contacts stored.
-__device__ __noinline__ int self_collide(BTile *Tp, ModelPtr Mp, const int lane, const int nc) {
-  BTile &T = *Tp;
-  const BallModel FFE_GLOBAL &M = *Mp;
-  // per slot: (centre, bounding radius), (axis, half length), radius
-  const float4 *pgc = reinterpret_cast<const float4 *>(&T.lk[0][0]), *pga = pgc + NPG;
-  const float *pgr = reinterpret_cast<const float *>(pgc + 2 * NPG);
-  const float mclaw = M.sc_margin;
-  const unsigned long long claws = M.sp_claw;
-  const int sphere = M.sp_sphere;
-  // lane s owns slot s and meets slots s + 1 .. s + NPG / 2 (mod NPG): every unordered pair once
-  const bool own = lane < NPG;
-  const unsigned long long partners = own ? M.sp_mask[lane] : 0ull;
-  const float4 o0 = own ? pgc[lane] : make_float4(0.f, 0.f, 0.f, 0.f);
-  const float oreach = o0.w + (((claws >> lane) & 1ull) ? mclaw : 0.f);
-  unsigned near = 0u;  // bit t - 1: the pair (lane, lane + t) passed the bounding-sphere test
-#pragma unroll 4
-  for (int t = 1; t <= NPG / 2; t++) {
-    int j = lane + t;
-    j = j >= NPG ? j - NPG : j;
-    if (own && ((partners >> j) & 1ull) && (t < NPG / 2 || lane < NPG / 2)) {
-      const float4 p0 = pgc[j];
-      const float dx = p0.x - o0.x, dy = p0.y - o0.y, dz = p0.z - o0.z;
-      const float reach = oreach + p0.w + mclaw;  // (the claw margin on both sides: a bound is all that is needed here)
-      if (dx * dx + dy * dy + dz * dz <= reach * reach) near |= 1u << (t - 1);
-    }
+// The two passes of self_pairs.hpp on the ball's tile.  The primitive geom slots are in T.lk (stage 1 publishes them), the geom frames in
+// T.gc / T.gq (`ball_convex` makes them), the pair lists beside the slots; the convex pass keeps its separating directions in T.sd_*.
+struct BallPairs {
+  static constexpr bool kSyncAtEnd = false, kHistory = true;
+  static constexpr int kFullBit = 8;
+  static __device__ __forceinline__ const float4 *slots(const BTile &T) { return reinterpret_cast<const float4 *>(&T.lk[0][0]); }
+  static __device__ __forceinline__ const float *radii(const BTile &T) { return reinterpret_cast<const float *>(slots(T) + 2 * NPG); }
+  static __device__ __forceinline__ const float4 *centres(const BTile &T) { return T.gc; }
+  static __device__ __forceinline__ Q4 quat(const BTile &T, const BallModel FFE_GLOBAL &, int g) { const float4 qq = T.gq[g]; return Q4{qq.x, qq.y, qq.z, qq.w}; }
+  static __device__ __forceinline__ unsigned short *cl1(BTile &T) { return T.cl1; }
+  static __device__ __forceinline__ unsigned short *cl2(BTile &T) { return T.cl2; }
+  __device__ __forceinline__ void fill_slots(BTile &, int) const {}                                     // (stage 1 has made them)
+  static __device__ __forceinline__ void fill_centres(BTile &, const BallModel FFE_GLOBAL &, int) {}  // (`ball_convex` has)
+  // A fly-fly contact in the layout of the ball contacts' arrays: c_link = link of geom1 | link of geom2 << 8, c_frame[0..2] = normal from
+  // geom1 to geom2, c_par = {K, B, invweight, 0, margin - gap}.  A geom of the thorax (fixed to the world) has no link: the moving
+  // geom's link is stored first and the normal turned, so that it still points from the first link's geom to the second's.
+  static __device__ __forceinline__ void put(BTile &T, const BallModel FFE_GLOBAL &M, int at, int la, int lb, int pid, V3 nrm, V3 cpos, float dist, float margin, float invw) {
+    if (la < 0) { la = lb; lb = 255; nrm = V3{-nrm.x, -nrm.y, -nrm.z}; }
+    else if (lb < 0) lb = 255;
+    const float incl = margin - (margin != 0.f ? M.sc_gap : 0.f);
+    T.c_link[at] = la | (lb << 8);
+    T.c_pid[at] = (unsigned short)pid;
+    T.c_excl[at] = dist >= incl ? 1 : 0;
+    T.c_dist[at] = dist;
+    T.c_pos[at][0] = cpos.x; T.c_pos[at][1] = cpos.y; T.c_pos[at][2] = cpos.z;
+    T.c_frame[at][0] = nrm.x; T.c_frame[at][1] = nrm.y; T.c_frame[at][2] = nrm.z;
+    T.c_par[at][0] = M.sc_K; T.c_par[at][1] = M.sc_B; T.c_par[at][2] = invw; T.c_par[at][3] = 0.f;
+    T.c_par[at][4] = incl;
   }
-  int nsc = 0, ovf = 0, ndrop = 0;
-#pragma unroll 1
-  while (__ballot(near != 0u) != 0ull) {
-    bool hit = false;
-    float dist = 0.f, margin = 0.f;
-    V3 nrm = {1.f, 0.f, 0.f}, cpos = {0.f, 0.f, 0.f};
-    int s1 = 0, s2 = 0;
-    if (near) {
-      const int t = __ffs(near);
-      near &= near - 1u;
-      int j = lane + t;
-      j = j >= NPG ? j - NPG : j;
-      // mj: geom1 is the one with the lower type code (the sphere), else the one that comes first in the model
-      const bool swap = j == sphere || (lane != sphere && j < lane);
-      s1 = swap ? j : lane; s2 = swap ? lane : j;
-      const float4 ca = pgc[s1], aa = pga[s1], cb_ = pgc[s2], ab = pga[s2];
-      const V3 p1 = {ca.x, ca.y, ca.z}, a1 = {aa.x, aa.y, aa.z}, p2 = {cb_.x, cb_.y, cb_.z}, a2 = {ab.x, ab.y, ab.z};
-      const float l1 = aa.w, r1 = pgr[s1], l2 = ab.w, r2 = pgr[s2];
-      margin = (((claws >> s1) | (claws >> s2)) & 1ull) ? mclaw : 0.f;
-      const V3 dif = p1 - p2;
-      const float mb = -dot(a1, a2), u = -dot(a1, dif), v = dot(a2, dif), det = 1.f - mb * mb;
-      float x1, x2;
-      if (fabsf(det) >= 1e-6f) {
-        const float idet = 1.f / det;
-        x1 = (u - mb * v) * idet; x2 = (v - mb * u) * idet;
-        if (x1 > l1) { x1 = l1; x2 = v - mb * l1; } else if (x1 < -l1) { x1 = -l1; x2 = v + mb * l1; }
-        if (x2 > l2) { x2 = l2; x1 = fminf(fmaxf(u - mb * l2, -l1), l1); }
-        else if (x2 < -l2) { x2 = -l2; x1 = fminf(fmaxf(u + mb * l2, -l1), l1); }
-      } else {  // parallel axes: centre of the overlapping stretch
-        const float c2 = u, lo = fmaxf(-l1, c2 - l2), hi = fminf(l1, c2 + l2);
-        x1 = lo <= hi ? 0.5f * (lo + hi) : (c2 > 0.f ? l1 : -l1);
-        x2 = fminf(fmaxf((x1 - c2) * (mb < 0.f ? 1.f : -1.f), -l2), l2);
-      }
-      const V3 q1 = p1 + x1 * a1, q2 = p2 + x2 * a2, d12 = q2 - q1;
-      const float cd = fsqrt(dot(d12, d12));
-      hit = cd <= margin + r1 + r2;
-      if (cd >= 1e-15f) nrm = frcp(cd) * d12;
-      dist = cd - r1 - r2;
-      cpos = q1 + (r1 + 0.5f * dist) * nrm;
-    }
-    // A contact inside its margin but outside margin - gap exerts no force; it only matters as one of the contacts an adhesion
-    // actuator spreads its pull over (mjTRN_BODY).  Without such an actuator on either link it gets no slot (and no solver row);
-    // it is still counted (ndrop) so that the number of detected contacts stays MuJoCo's.
-    const bool dropped = hit && dist >= margin - (margin != 0.f ? M.sc_gap : 0.f) && M.l_adh[M.pgs_link[s1]] < 0 && M.l_adh[M.pgs_link[s2]] < 0;
-    hit = hit && !dropped;
-    ndrop += __popcll(__ballot(dropped));
-    const unsigned long long bal = __ballot(hit);
-    if (bal) {
-      const int idx = nc + nsc + __popcll(bal & ((1ull << lane) - 1ull));
-      auto store = [&](int at) {
-        const float incl = margin - (margin != 0.f ? M.sc_gap : 0.f);
-        T.c_link[at] = M.pgs_link[s1] | (M.pgs_link[s2] << 8);
-        T.c_pid[at] = (unsigned short)(0x8000 | s1 | (s2 << 6));
-        T.c_excl[at] = dist >= incl ? 1 : 0;
-        T.c_dist[at] = dist;
-        T.c_pos[at][0] = cpos.x; T.c_pos[at][1] = cpos.y; T.c_pos[at][2] = cpos.z;
-        T.c_frame[at][0] = nrm.x; T.c_frame[at][1] = nrm.y; T.c_frame[at][2] = nrm.z;
-        T.c_par[at][0] = M.sc_K; T.c_par[at][1] = M.sc_B; T.c_par[at][2] = M.pgs_invw[s1] + M.pgs_invw[s2]; T.c_par[at][3] = 0.f;
-        T.c_par[at][4] = incl;
-      };
-      if (hit && idx < NC) store(idx);
-      const int n = __popcll(bal);
-      const bool over = nc + nsc + n > NC;
-      nsc = min(nsc + n, NC - nc);
-      if (over && nc < NC) {
-        // More contacts than the tile holds: the env is flagged, and a hit without a slot takes the place of the shallowest fly-fly
-        // contact held so far if it is deeper (as for the ball contacts and the convex pairs: a deep contact is never the one dropped).
-        ovf = 1;
-        DM_SYNC();
-        for (unsigned long long left = __ballot(hit && idx >= NC); left; left &= left - 1) {
-          const int j = __ffsll((long long)left) - 1;
-          float shallow = -1e30f;
-          int at = -1;
-          for (int k = nc; k < NC; k++) { const float dk = T.c_dist[k]; if (dk > shallow) { shallow = dk; at = k; } }
-          if (__shfl(dist, j) < shallow) { if (lane == j) store(at); DM_SYNC(); }
-        }
-      } else if (over) ovf = 1;
-    }
-  }
-  return nsc | (ovf << 8) | (ndrop << 16);
-}
+};
 
 // ------------------------------------------------------------------------------------------------ convex pairs
 // mj: mjc_Convex for the pairs with an ellipsoid or a cylinder on one side (thorax, head, rostrum, labrum, wings, coxae, abdomen
 // segments; fruitfly.xml:323-443), restated in csrc/convex.hpp.  The geoms' world frames are made once per substep from the link
 // poses the lanes publish (`T.lp`) into `T.gc` (centre | bounding radius) / `T.gq` (orientation).
-__device__ __forceinline__ cvx::Geom load_geom(const BTile &T, const BallModel FFE_GLOBAL &M, int g) {
-  const float4 cc = T.gc[g], qq = T.gq[g];
-  return cvx::Geom{V3{cc.x, cc.y, cc.z}, Q4{qq.x, qq.y, qq.z, qq.w}, M.cg_size[0][g], M.cg_size[1][g], M.cg_size[2][g], M.cg_type[g]};
-}
-
+//
 // Ball (geom1, a sphere) against the ellipsoids / cylinders that can reach it (abdomen segments: mjc_SphereCylinder; labrum, wings:
 // the sphere's centre against the ellipsoid's signed distance): condim-3 ball contacts like the leg capsules', appended to the
-// `nc0` ball contacts stage 1 has just stored.  Also makes the geom frames for `convex_collide`.  Returns the number appended
+// `nc0` ball contacts stage 1 has just stored.  Also makes the geom frames for `convex_pairs`.  Returns the number appended
 // | overflow << 8.
-#ifndef FFB_BALLCVX_ATTR
-#define FFB_BALLCVX_ATTR __noinline__
-#endif
-__device__ FFB_BALLCVX_ATTR int ball_convex(BTile *Tp, ModelPtr Mp, const int lane, const int nc0) {
+__device__ __noinline__ int ball_convex(BTile *Tp, ModelPtr Mp, const int lane, const int nc0) {
   BTile &T = *Tp;
   const BallModel FFE_GLOBAL &M = *Mp;
   const int ncg = M.ncg;
@@ -308,7 +220,7 @@ __device__ FFB_BALLCVX_ATTR int ball_convex(BTile *Tp, ModelPtr Mp, const int la
     const float4 cc = T.gc[g];
     const float dx = cc.x - ball.c.x, dy = cc.y - ball.c.y, dz = cc.z - ball.c.z, reach = M.b_radius + cc.w + M.xb_margin[lane];
     if (dx * dx + dy * dy + dz * dz <= reach * reach) {  // mj: the bounding-sphere test of mj_collision
-      const cvx::PResult r = cvx::prim_convex<1>(ball, load_geom(T, M, g));
+      const cvx::PResult r = cvx::prim_convex<1>(ball, load_geom<BallPairs>(T, M, g));
       dist = r.dist; nrm = r.n; cpos = r.pos;
       hit = dist <= M.xb_margin[lane];
       incl = M.xb_margin[lane] - M.xb_gap[lane];
@@ -337,154 +249,6 @@ __device__ FFB_BALLCVX_ATTR int ball_convex(BTile *Tp, ModelPtr Mp, const int la
   }
   DM_SYNC();
   return min(n, NC - nc0) | ((nc0 + n > NC ? 1 : 0) << 8);
-}
-
-// The fly's own convex pairs.  Broad phase: MuJoCo's bounding-sphere test over the static candidate list (flybody_amd/model/reach.py),
-// then - on the survivors - a rigorous lower bound of the distance from one separating direction (cvx::separation_bound); a pair
-// whose bound exceeds its margin cannot touch.  Narrow phase: one lane per remaining pair (cvx::collide).  A contact (dist <= margin)
-// takes the next free slot after the `nprev` contacts already stored, in the same layout as self_collide's; a geom of the thorax
-// (fixed to the world) has no link: the moving geom's link is stored first and the normal turned, so that it still points from the
-// first link's geom to the second's.  Returns the number of contacts stored | overflow << 8.
-#ifndef FFB_CONVEX_ATTR
-#define FFB_CONVEX_ATTR __noinline__
-#endif
-__device__ FFB_CONVEX_ATTR int convex_collide(BTile *Tp, ModelPtr Mp, const int lane, const int nprev) {
-  BTile &T = *Tp;
-  const BallModel FFE_GLOBAL &M = *Mp;
-  const unsigned long long mm0 = M.cg_mmask[0], mm1 = M.cg_mmask[1];
-  const float mclaw = M.sc_margin;
-  auto pair_margin = [&](int a, int b) {
-    const bool ma = a < 64 ? ((mm0 >> a) & 1ull) : ((mm1 >> (a - 64)) & 1ull), mb = b < 64 ? ((mm0 >> b) & 1ull) : ((mm1 >> (b - 64)) & 1ull);
-    return (ma || mb) ? mclaw : 0.f;
-  };
-  int n1 = 0, ovf = 0;
-#ifdef CVXDBG_NO_SPHERE
-  const int ncp = 0;
-#else
-  const int ncp = M.ncp;
-#endif
-#pragma unroll 2
-  for (int base = 0; base < ncp; base += 64) {
-    const unsigned w = M.cp_pair[base + lane];
-    bool pass = false;
-    if (w != 0xffffu) {
-      const int a = w & 255, b = w >> 8;
-      const float4 ca = T.gc[a], cb = T.gc[b];
-      const float dx = cb.x - ca.x, dy = cb.y - ca.y, dz = cb.z - ca.z, reach = ca.w + cb.w + pair_margin(a, b);
-      pass = dx * dx + dy * dy + dz * dz <= reach * reach;
-    }
-    const unsigned long long bal = __ballot(pass);
-    const int idx = n1 + __popcll(bal & ((1ull << lane) - 1ull));
-    if (pass && idx < CL1) T.cl1[idx] = (unsigned short)w;
-    n1 += __popcll(bal);
-  }
-  if (n1 > CL1) { n1 = CL1; ovf = 1; }
-#ifdef CVXDBG_NO_BOUND
-  n1 = 0;
-#endif
-  DM_SYNC();
-  // Second test: a separating direction proves the pair apart.  Besides the two directions of cvx::separation_bound, the one the
-  // narrow phase found for this pair on the last substep it ran (`sd_*`): pairs that stay near each other without touching (a hind
-  // coxa beside the abdomen, stacked abdomen discs) then cost two support evaluations per substep instead of a narrow phase.
-  int n2 = 0, nk = 0;
-  const int ncache = T.sd_cnt;
-#pragma unroll 1
-  for (int base = 0; base < n1; base += 64) {
-    bool pass = false, keep = false, have_kn = false;
-    unsigned w = 0u;
-    V3 kn = {0.f, 0.f, 0.f};
-    float kt = 0.f;
-    if (base + lane < n1) {
-      w = T.cl1[base + lane];
-      const int a = w & 255, b = w >> 8;
-      const cvx::Geom ga = load_geom(T, M, a), gb = load_geom(T, M, b);
-      // the distance that matters: the margin where an adhesion actuator shares its pull over every detected contact of its body,
-      // margin - gap (a contact beyond it exerts no force and gets no slot) otherwise
-      float thr = pair_margin(a, b);
-      {
-        const int la_ = M.cg_link[a], lb_ = M.cg_link[b];
-        if ((la_ < 0 || M.l_adh[la_] < 0) && (lb_ < 0 || M.l_adh[lb_] < 0) && thr != 0.f) thr -= M.sc_gap;
-      }
-      pass = cvx::separation_bound(ga, gb) <= thr;
-      if (pass) {
-        for (int k = 0; k < ncache; k++) {
-          if (T.sd_pid[k] == w) {
-            kn = V3{T.sd_n[k][0], T.sd_n[k][1], T.sd_n[k][2]};
-            kt = T.sd_n[k][3];
-            keep = -cvx::overlap(ga, gb, kn) > thr;
-            have_kn = true;
-          }
-        }
-        pass = !keep;
-      }
-    }
-    const unsigned long long bal = __ballot(pass), balk = __ballot(keep);
-    const int idx = n2 + __popcll(bal & ((1ull << lane) - 1ull)), idk = nk + __popcll(balk & ((1ull << lane) - 1ull));
-    if (pass && idx < CL2) { T.cl2[idx] = (unsigned short)w; float *o = T.cl2n[idx]; o[0] = kn.x; o[1] = kn.y; o[2] = kn.z; o[3] = have_kn ? 1.f : 0.f; o[4] = kt; }
-    if (keep && idk < NSD) { T.tc_pid[idk] = (unsigned short)w; T.tc_n[idk][0] = kn.x; T.tc_n[idk][1] = kn.y; T.tc_n[idk][2] = kn.z; T.tc_n[idk][3] = kt; }
-    n2 += __popcll(bal);
-    nk = min(nk + __popcll(balk), NSD);
-  }
-  if (n2 > CL2) { n2 = CL2; ovf = 1; }
-#ifdef CVXDBG_NO_NARROW
-  n2 = 0;
-#endif
-  DM_SYNC();
-  bool hit = false, dropped = false;
-  float dist = 0.f, margin = 0.f, ctt = 0.f;
-  V3 nrm = {1.f, 0.f, 0.f}, cpos = {0.f, 0.f, 0.f};
-  int a = 0, b = 0;
-  if (lane < n2) {
-    const unsigned w = T.cl2[lane];
-    a = w & 255; b = w >> 8;
-    margin = pair_margin(a, b);
-    const float *kn = T.cl2n[lane];
-    const cvx::Contact ct = cvx::collide(load_geom(T, M, a), load_geom(T, M, b), V3{kn[0], kn[1], kn[2]}, kn[3] != 0.f, kn[4]);
-    dist = ct.dist; nrm = ct.n; cpos = ct.pos; ctt = ct.t;
-    hit = dist <= margin;
-    // (an inactive contact no adhesion actuator takes part in gets no slot: see self_collide)
-    if (hit && dist >= margin - (margin != 0.f ? M.sc_gap : 0.f)) {
-      const int la_ = M.cg_link[a], lb_ = M.cg_link[b];
-      dropped = (la_ < 0 || M.l_adh[la_] < 0) && (lb_ < 0 || M.l_adh[lb_] < 0);
-      hit = !dropped;
-    }
-    if (nk + lane < NSD) {  // its direction, for the next substep's second test
-      T.tc_pid[nk + lane] = (unsigned short)w; T.tc_n[nk + lane][0] = nrm.x; T.tc_n[nk + lane][1] = nrm.y; T.tc_n[nk + lane][2] = nrm.z; T.tc_n[nk + lane][3] = ctt;
-    }
-  }
-  nk = min(nk + n2, NSD);
-  DM_SYNC();
-  if (lane < nk) { T.sd_pid[lane] = T.tc_pid[lane]; T.sd_n[lane][0] = T.tc_n[lane][0]; T.sd_n[lane][1] = T.tc_n[lane][1]; T.sd_n[lane][2] = T.tc_n[lane][2]; T.sd_n[lane][3] = T.tc_n[lane][3]; }
-  if (lane == 0) T.sd_cnt = nk;
-  unsigned long long bal = __ballot(hit);
-  if (nprev + __popcll(bal) > NC) {  // more than the free slots: the env is flagged and the deepest are kept (as for the ball contacts)
-    ovf = 1;
-    int rank = 0;
-    for (unsigned long long m = bal; m; m &= m - 1) {
-      const int j = __ffsll((long long)m) - 1;
-      const float dj = __shfl(dist, j);
-      if (dj < dist || (dj == dist && j < lane)) rank++;
-    }
-    hit = hit && rank < NC - nprev;
-    bal = __ballot(hit);
-  }
-  const int n = __popcll(bal), idx = nprev + __popcll(bal & ((1ull << lane) - 1ull));
-  if (hit && idx < NC) {
-    int la = M.cg_link[a], lb = M.cg_link[b];
-    if (la < 0) { la = lb; lb = 255; nrm = V3{-nrm.x, -nrm.y, -nrm.z}; }
-    else if (lb < 0) lb = 255;
-    const float incl = margin - (margin != 0.f ? M.sc_gap : 0.f);
-    T.c_link[idx] = la | (lb << 8);
-    T.c_pid[idx] = (unsigned short)(a | (b << 8));
-    T.c_excl[idx] = dist >= incl ? 1 : 0;
-    T.c_dist[idx] = dist;
-    T.c_pos[idx][0] = cpos.x; T.c_pos[idx][1] = cpos.y; T.c_pos[idx][2] = cpos.z;
-    T.c_frame[idx][0] = nrm.x; T.c_frame[idx][1] = nrm.y; T.c_frame[idx][2] = nrm.z;
-    T.c_par[idx][0] = M.sc_K; T.c_par[idx][1] = M.sc_B; T.c_par[idx][2] = M.cg_invw[a] + M.cg_invw[b]; T.c_par[idx][3] = 0.f;
-    T.c_par[idx][4] = incl;
-  }
-  DM_SYNC();
-  return n | (ovf << 8) | (__popcll(__ballot(dropped)) << 16);
 }
 
 // Fly-fly contact slots keep the dofs of geom2's chain (14 bytes), and the block-local solve column of that chain (byte 14),
@@ -748,17 +512,13 @@ __device__ __forceinline__ void stage1(C &c) {
       reinterpret_cast<float *>(o + 2 * NPG)[M.pg2_slot] = M.pg2_rad;
     }
     DM_SYNC();
-#ifdef FFB_SC_NOCALL
-    const int sc = 0;
-#else
-    const int sc = __builtin_amdgcn_readfirstlane(self_collide(c.T, (ModelPtr)c.M, lane, c.nc));  // wave-uniform by construction
-#endif
+    const int sc = __builtin_amdgcn_readfirstlane(prim_pairs(c.T, (ModelPtr)c.M, BallPairs{}, lane, c.nc));  // wave-uniform by construction
     c.nsc = sc & 0xff;
     if ((sc >> 8) & 0xff) c.overflow |= 1;
     c.ndrop = sc >> 16;
     BSTAMP(11);  // sphere / capsule pairs
     // ---- and over its pairs with an ellipsoid or cylinder on one side
-    const int cc = __builtin_amdgcn_readfirstlane(convex_collide(c.T, (ModelPtr)c.M, lane, c.nc + c.nsc));
+    const int cc = __builtin_amdgcn_readfirstlane(convex_pairs<BallPairs>(c.T, (ModelPtr)c.M, lane, c.nc + c.nsc));
     c.nsc += cc & 0xff;
     if ((cc >> 8) & 0xff) c.overflow |= 1;
     c.ndrop += cc >> 16;

@@ -5,7 +5,7 @@
 // walk_self_env.hip are compiled as they were.  It is `imitation_floor_step` whose substep is `floor_self_step`'s - the code of
 // walk_substeps.hpp on the tile `WTileSX`, which is a sense tile and a self tile at once:
 //   front    the action row or the reset row, as `imitation_floor_step`;
-//   substep  stage 1, `floor_collide`, then `self_prim_collide` and `self_convex_collide`; stage 2 with `contact_forces` (floor cone blocks,
+//   substep  stage 1, `floor_collide`, then `prim_pairs` and `convex_pairs` (self_pairs.hpp); stage 2 with `contact_forces` (floor cone blocks,
 //            one normal row per fly-fly contact, joint limits; ConeRowsResidual, from lambda = 0, the model's noslip sweeps, adhesion shared
 //            over all contacts of a body), ten times in registers; a reset row runs stage 1, the three collision passes and the
 //            acceleration half with its contact solve once and integrates nothing;

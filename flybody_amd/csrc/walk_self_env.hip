@@ -4,9 +4,9 @@
 // The sixth free-root step kernel, in a translation unit of its own so that the five of walk_env.hip and walk_floor_env.hip are compiled
 // as they were.  It is `floor_step` with two more collision passes and one more kind of constraint row - the code of walk_substeps.hpp
 // on the tile `WTileX`:
-//   collision  `floor_collide`, then `self_prim_collide` (the 48 sphere / capsule geoms against each other) and `self_convex_collide`
-//              (the pairs with an ellipsoid or a cylinder on one side, cvx:: of convex.hpp), both restated from ball_env.hip in the root
-//              frame; the floor's contacts keep the first slots, NC = 16 in all, the deepest are kept beyond that;
+//   collision  `floor_collide`, then `prim_pairs` (the 48 sphere / capsule geoms against each other) and `convex_pairs`
+//              (the pairs with an ellipsoid or a cylinder on one side, cvx:: of convex.hpp): the two passes of self_pairs.hpp, which
+//              ball_env.hip runs too, here in the root frame; the floor's contacts keep the first slots, NC = 16 in all, the deepest are kept beyond that;
 //   rows       `contact_forces`: floor cone blocks, one normal row per fly-fly contact over the hinges of two chains (no entry on the
 //              root: walk_self.hpp), joint limits; from lambda = 0, the model's noslip sweeps, adhesion shared over all contacts of a body.
 // There is no "no floor in reach" shortcut (the mouth parts touch in every pose) and no state besides WState: a launch's result is a

@@ -20,6 +20,7 @@
 #include "walk_sense.hpp"
 #include "walk_self_sense.hpp"
 #include "walk_self.hpp"
+#include "self_pairs.hpp"
 
 namespace ffw {
 using namespace dm;
@@ -636,9 +637,9 @@ __device__ __forceinline__ void floor_frame(const C &c, float (&fr)[9]) {
 constexpr float kFloorScale = 1e-2f;
 
 // ------------------------------------------------------------------------------------------------ the fly's own contacts
-// (FFE_WALK_SELF)  ball_env.hip's `self_collide` and `convex_collide` restated on the walker's tile, in
-// the root frame: the geoms' frames come from the link poses `floor_collide` has published (T.lp), the narrow phase of the convex pairs
-// is cvx:: of convex.hpp as it is.  Both run after `floor_collide`, whose contacts keep the first slots; the fly-fly contacts follow.
+// (FFE_WALK_SELF)  The two collision passes of self_pairs.hpp on the walker's tile, in the root frame: the
+// geoms' frames come from the link poses `floor_collide` has published (T.lp), the narrow phase of the convex pairs is cvx:: of
+// convex.hpp as it is.  Both run after `floor_collide`, whose contacts keep the first slots; the fly-fly contacts follow.
 // Templates on the tile so that only the kernel that calls them instantiates them.
 //
 // Stores fly-fly contact `at`: geom1 on link l1, geom2 on link l2 (-1: the thorax), normal n from geom1 to geom2.  A pair whose geom2
@@ -672,230 +673,57 @@ __device__ __forceinline__ void self_put(TileX &T, const BallModel FFE_GLOBAL &M
   } else { T.c_link1[at] = 255; T.c_blk1[at] = 255; T.c_amask1[at] = 0; }
 }
 
-// mj: mj_collision over the fly's own sphere / capsule pairs (mjc_CapsuleCapsule; a sphere is a capsule of zero length), condim 1: see
-// ball_env.hip `self_collide`.  Lane s makes slot s from the floor table's geom s (the same 48 geoms) and then meets slots s + 1 .. s +
-// NPG / 2 (mod NPG).  A detected contact takes the next slot after the `nprev` contacts stored so far; beyond NC the deepest fly-fly
-// contacts are kept.  A contact inside its margin but outside margin - gap with no adhesion actuator on either link takes no slot and is
-// counted apart.  Returns contacts stored | overflow << 8 | contacts without a slot << 16.  Out of line and a leaf.
+// self_pairs.hpp on a walker's tile: the primitive geom slots and, after them, the geom centres and the pair lists in T.X4, the slots' radii
+// behind the link poses in T.G; a geom's orientation from its link's pose; no separating direction is remembered from substep to
+// substep (a launch's result is a function of its state alone, the narrow phase always starts cold); a full pair list has its own bit.
 template <class TileX>
-__device__ __noinline__ int self_prim_collide(TileX *Tp, ModelPtr Mp, const WalkExtra FFE_GLOBAL *Xp, const int lane, const int nprev) {
-  TileX &T = *Tp;
-  const BallModel FFE_GLOBAL &M = *Mp;
-  const WalkExtra FFE_GLOBAL &X = *Xp;
-  float4 *pgc = &T.X4[0], *pga = pgc + NPG;  // (centre, bounding radius), (axis, half length)
-  float *pgr = &T.G[NL * 14];                // radius: behind the link poses
-  const bool own = lane < NPG;
-  if (own) {
-    const float *lp = T.lp[X.f_link[lane]];
-    const M3 R = q2m(Q4{lp[3], lp[4], lp[5], lp[6]});
-    const V3 gc = V3{lp[0], lp[1], lp[2]} + mv(R, V3{X.f_pos[0][lane], X.f_pos[1][lane], X.f_pos[2][lane]});
-    const V3 ga = mv(R, V3{X.f_axis[0][lane], X.f_axis[1][lane], X.f_axis[2][lane]});
-    const float half = X.f_half[lane], rad = X.f_rad[lane];
-    pgc[lane] = make_float4(gc.x, gc.y, gc.z, half + rad);
-    pga[lane] = make_float4(ga.x, ga.y, ga.z, half);
-    pgr[lane] = rad;
-  }
-  DM_SYNC();
-  const float mclaw = M.sc_margin;
-  const unsigned long long claws = M.sp_claw;
-  const int sphere = M.sp_sphere;
-  const unsigned long long partners = own ? M.sp_mask[lane] : 0ull;
-  const float4 o0 = own ? pgc[lane] : make_float4(0.f, 0.f, 0.f, 0.f);
-  const float oreach = o0.w + (((claws >> lane) & 1ull) ? mclaw : 0.f);
-  unsigned near = 0u;  // bit t - 1: the pair (lane, lane + t) passed the bounding-sphere test
-#pragma unroll 4
-  for (int t = 1; t <= NPG / 2; t++) {
-    int j = lane + t;
-    j = j >= NPG ? j - NPG : j;
-    if (own && ((partners >> j) & 1ull) && (t < NPG / 2 || lane < NPG / 2)) {
-      const float4 p0 = pgc[j];
-      const float dx = p0.x - o0.x, dy = p0.y - o0.y, dz = p0.z - o0.z;
-      const float reach = oreach + p0.w + mclaw;
-      if (dx * dx + dy * dy + dz * dz <= reach * reach) near |= 1u << (t - 1);
-    }
-  }
-  int nsc = 0, ovf = 0, ndrop = 0;
-#pragma unroll 1
-  while (__ballot(near != 0u) != 0ull) {
-    bool hit = false;
-    float dist = 0.f, margin = 0.f;
-    V3 nrm = {1.f, 0.f, 0.f}, cpos = {0.f, 0.f, 0.f};
-    int s1 = 0, s2 = 0;
-    if (near) {
-      const int t = __ffs(near);
-      near &= near - 1u;
-      int j = lane + t;
-      j = j >= NPG ? j - NPG : j;
-      // mj: geom1 is the one with the lower type code (the sphere), else the one that comes first in the model
-      const bool swap = j == sphere || (lane != sphere && j < lane);
-      s1 = swap ? j : lane; s2 = swap ? lane : j;
-      const float4 ca = pgc[s1], aa = pga[s1], cb_ = pgc[s2], ab = pga[s2];
-      const V3 p1 = {ca.x, ca.y, ca.z}, a1 = {aa.x, aa.y, aa.z}, p2 = {cb_.x, cb_.y, cb_.z}, a2 = {ab.x, ab.y, ab.z};
-      const float l1 = aa.w, r1 = pgr[s1], l2 = ab.w, r2 = pgr[s2];
-      margin = (((claws >> s1) | (claws >> s2)) & 1ull) ? mclaw : 0.f;
-      const V3 dif = p1 - p2;
-      const float mb = -dot(a1, a2), u = -dot(a1, dif), v = dot(a2, dif), det = 1.f - mb * mb;
-      float x1, x2;
-      if (fabsf(det) >= 1e-6f) {
-        const float idet = 1.f / det;
-        x1 = (u - mb * v) * idet; x2 = (v - mb * u) * idet;
-        if (x1 > l1) { x1 = l1; x2 = v - mb * l1; } else if (x1 < -l1) { x1 = -l1; x2 = v + mb * l1; }
-        if (x2 > l2) { x2 = l2; x1 = fminf(fmaxf(u - mb * l2, -l1), l1); }
-        else if (x2 < -l2) { x2 = -l2; x1 = fminf(fmaxf(u + mb * l2, -l1), l1); }
-      } else {  // parallel axes: centre of the overlapping stretch
-        const float c2 = u, lo = fmaxf(-l1, c2 - l2), hi = fminf(l1, c2 + l2);
-        x1 = lo <= hi ? 0.5f * (lo + hi) : (c2 > 0.f ? l1 : -l1);
-        x2 = fminf(fmaxf((x1 - c2) * (mb < 0.f ? 1.f : -1.f), -l2), l2);
-      }
-      const V3 q1 = p1 + x1 * a1, q2 = p2 + x2 * a2, d12 = q2 - q1;
-      const float cd = fsqrt(dot(d12, d12));
-      hit = cd <= margin + r1 + r2;
-      if (cd >= 1e-15f) nrm = frcp(cd) * d12;
-      dist = cd - r1 - r2;
-      cpos = q1 + (r1 + 0.5f * dist) * nrm;
-    }
-    const bool dropped = hit && dist >= margin - (margin != 0.f ? M.sc_gap : 0.f) && M.l_adh[M.pgs_link[s1]] < 0 && M.l_adh[M.pgs_link[s2]] < 0;
-    hit = hit && !dropped;
-    ndrop += __popcll(__ballot(dropped));
-    const unsigned long long bal = __ballot(hit);
-    if (bal) {
-      const int idx = nprev + nsc + __popcll(bal & ((1ull << lane) - 1ull));
-      auto store = [&](int at) { self_put(T, M, at, M.pgs_link[s1], M.pgs_link[s2], nrm, cpos, dist, margin, M.pgs_invw[s1] + M.pgs_invw[s2]); };
-      if (hit && idx < NC) store(idx);
-      const int n = __popcll(bal);
-      const bool over = nprev + nsc + n > NC;
-      nsc = min(nsc + n, NC - nprev);
-      if (over && nprev < NC) {
-        // a hit without a slot takes the place of the shallowest fly-fly contact held so far if it is deeper
-        ovf = 1;
-        DM_SYNC();
-        for (unsigned long long left = __ballot(hit && idx >= NC); left; left &= left - 1) {
-          const int j = __ffsll((long long)left) - 1;
-          float shallow = -1e30f;
-          int at = -1;
-          for (int k = nprev; k < NC; k++) { const float dk = T.c_dist[k]; if (dk > shallow) { shallow = dk; at = k; } }
-          if (__shfl(dist, j) < shallow) { if (lane == j) store(at); DM_SYNC(); }
-        }
-      } else if (over) ovf = 1;
-    }
-  }
-  DM_SYNC();
-  return nsc | (ovf << 8) | (ndrop << 16);
-}
-
-// the world (here: root) frame of fly geom g: its centre from the table the convex pass has made, its orientation from its link's pose
-template <class TileX>
-__device__ __forceinline__ cvx::Geom self_geom(const TileX &T, const BallModel FFE_GLOBAL &M, const float4 *gc, const int g) {
-  const float4 cc = gc[g];
-  Q4 q = {M.cg_quat[0][g], M.cg_quat[1][g], M.cg_quat[2][g], M.cg_quat[3][g]};
-  const int l = M.cg_link[g];
-  if (l >= 0) { const float *lp = T.lp[l]; q = qnormalize(qmul(Q4{lp[3], lp[4], lp[5], lp[6]}, q)); }
-  return cvx::Geom{V3{cc.x, cc.y, cc.z}, q, M.cg_size[0][g], M.cg_size[1][g], M.cg_size[2][g], M.cg_type[g]};
-}
-
-// The fly's own pairs with an ellipsoid or a cylinder on one side (mj: mjc_Convex): see ball_env.hip `convex_collide`.  Bounding-sphere
-// test over the static candidate list, a separating-direction bound on the survivors, then one lane per remaining pair in the narrow
-// phase (cvx::collide).  No separating direction is remembered from substep to substep: a launch's result is a function of its state
-// alone, and the narrow phase always starts cold.  Returns contacts stored | overflow << 8 | (a pair list was full: candidates were
-// left out) << 9 | contacts without a slot << 16.  Out of line and a leaf.
-template <class TileX>
-__device__ __noinline__ int self_convex_collide(TileX *Tp, ModelPtr Mp, const int lane, const int nprev) {
-  TileX &T = *Tp;
-  const BallModel FFE_GLOBAL &M = *Mp;
-  float4 *gc = &T.X4[0];
-  unsigned short *cl1 = reinterpret_cast<unsigned short *>(gc + NG), *cl2 = cl1 + ((CL1 + 7) / 8) * 8;
-  const int ncg = M.ncg;
-  for (int g = lane; g < ncg; g += 64) {
+struct WalkPairs {
+  static constexpr bool kSyncAtEnd = true, kHistory = false;
+  static constexpr int kFullBit = 9;
+  static __device__ __forceinline__ float4 *slots(TileX &T) { return &T.X4[0]; }
+  static __device__ __forceinline__ float *radii(TileX &T) { return &T.G[NL * 14]; }
+  static __device__ __forceinline__ float4 *centres(TileX &T) { return &T.X4[0]; }
+  static __device__ __forceinline__ const float4 *centres(const TileX &T) { return &T.X4[0]; }
+  static __device__ __forceinline__ unsigned short *cl1(TileX &T) { return reinterpret_cast<unsigned short *>(&T.X4[0] + NG); }
+  static __device__ __forceinline__ unsigned short *cl2(TileX &T) { return cl1(T) + ((CL1 + 7) / 8) * 8; }
+  static __device__ __forceinline__ Q4 quat(const TileX &T, const BallModel FFE_GLOBAL &M, const int g) {
+    Q4 q = {M.cg_quat[0][g], M.cg_quat[1][g], M.cg_quat[2][g], M.cg_quat[3][g]};
     const int l = M.cg_link[g];
-    V3 gp = {M.cg_pos[0][g], M.cg_pos[1][g], M.cg_pos[2][g]};
-    if (l >= 0) { const float *lp = T.lp[l]; gp = V3{lp[0], lp[1], lp[2]} + qrot(Q4{lp[3], lp[4], lp[5], lp[6]}, gp); }
-    gc[g] = make_float4(gp.x, gp.y, gp.z, M.cg_brad[g]);
+    if (l >= 0) { const float *lp = T.lp[l]; q = qnormalize(qmul(Q4{lp[3], lp[4], lp[5], lp[6]}, q)); }
+    return q;
   }
-  DM_SYNC();
-  const unsigned long long mm0 = M.cg_mmask[0], mm1 = M.cg_mmask[1];
-  const float mclaw = M.sc_margin;
-  auto pair_margin = [&](int a, int b) {
-    const bool ma = a < 64 ? ((mm0 >> a) & 1ull) : ((mm1 >> (a - 64)) & 1ull), mb = b < 64 ? ((mm0 >> b) & 1ull) : ((mm1 >> (b - 64)) & 1ull);
-    return (ma || mb) ? mclaw : 0.f;
-  };
-  auto no_adhesion = [&](int a, int b) {
-    const int la_ = M.cg_link[a], lb_ = M.cg_link[b];
-    return (la_ < 0 || M.l_adh[la_] < 0) && (lb_ < 0 || M.l_adh[lb_] < 0);
-  };
-  int n1 = 0, full = 0;
-  const int ncp = M.ncp;
-#pragma unroll 1
-  for (int base = 0; base < ncp; base += 64) {
-    const unsigned w = M.cp_pair[base + lane];
-    bool pass = false;
-    if (w != 0xffffu) {
-      const int a = w & 255, b = w >> 8;
-      const float4 ca = gc[a], cb = gc[b];
-      const float dx = cb.x - ca.x, dy = cb.y - ca.y, dz = cb.z - ca.z, reach = ca.w + cb.w + pair_margin(a, b);
-      pass = dx * dx + dy * dy + dz * dz <= reach * reach;
+  static __device__ __forceinline__ void put(TileX &T, const BallModel FFE_GLOBAL &M, int at, int l1, int l2, int, V3 n, V3 p, float dist, float margin, float invw) {
+    self_put(T, M, at, l1, l2, n, p, dist, margin, invw);
+  }
+  const WalkExtra FFE_GLOBAL *Xp;
+  // lane s makes slot s from the floor table's geom s (the same 48 geoms)
+  __device__ __forceinline__ void fill_slots(TileX &T, const int lane) const {
+    const WalkExtra FFE_GLOBAL &X = *Xp;
+    if (lane < NPG) {
+      const float *lp = T.lp[X.f_link[lane]];
+      const M3 R = q2m(Q4{lp[3], lp[4], lp[5], lp[6]});
+      const V3 gc = V3{lp[0], lp[1], lp[2]} + mv(R, V3{X.f_pos[0][lane], X.f_pos[1][lane], X.f_pos[2][lane]});
+      const V3 ga = mv(R, V3{X.f_axis[0][lane], X.f_axis[1][lane], X.f_axis[2][lane]});
+      const float half = X.f_half[lane], rad = X.f_rad[lane];
+      slots(T)[lane] = make_float4(gc.x, gc.y, gc.z, half + rad);
+      slots(T)[NPG + lane] = make_float4(ga.x, ga.y, ga.z, half);
+      radii(T)[lane] = rad;
     }
-    const unsigned long long bal = __ballot(pass);
-    const int idx = n1 + __popcll(bal & ((1ull << lane) - 1ull));
-    if (pass && idx < CL1) cl1[idx] = (unsigned short)w;
-    n1 += __popcll(bal);
+    DM_SYNC();
   }
-  if (n1 > CL1) { n1 = CL1; full = 1; }
-  DM_SYNC();
-  int n2 = 0;
-#pragma unroll 1
-  for (int base = 0; base < n1; base += 64) {
-    bool pass = false;
-    unsigned w = 0u;
-    if (base + lane < n1) {
-      w = cl1[base + lane];
-      const int a = w & 255, b = w >> 8;
-      // the distance that matters: the margin where an adhesion actuator shares its pull over every detected contact of its body,
-      // margin - gap (a contact beyond it exerts no force and gets no slot) otherwise
-      float thr = pair_margin(a, b);
-      if (thr != 0.f && no_adhesion(a, b)) thr -= M.sc_gap;
-      pass = cvx::separation_bound(self_geom(T, M, gc, a), self_geom(T, M, gc, b)) <= thr;
+  // the geoms' centres in the root frame
+  static __device__ __forceinline__ void fill_centres(TileX &T, const BallModel FFE_GLOBAL &M, const int lane) {
+    const int ncg = M.ncg;
+    for (int g = lane; g < ncg; g += 64) {
+      const int l = M.cg_link[g];
+      V3 gp = {M.cg_pos[0][g], M.cg_pos[1][g], M.cg_pos[2][g]};
+      if (l >= 0) { const float *lp = T.lp[l]; gp = V3{lp[0], lp[1], lp[2]} + qrot(Q4{lp[3], lp[4], lp[5], lp[6]}, gp); }
+      centres(T)[g] = make_float4(gp.x, gp.y, gp.z, M.cg_brad[g]);
     }
-    const unsigned long long bal = __ballot(pass);
-    const int idx = n2 + __popcll(bal & ((1ull << lane) - 1ull));
-    if (pass && idx < CL2) cl2[idx] = (unsigned short)w;
-    n2 += __popcll(bal);
+    DM_SYNC();
   }
-  if (n2 > CL2) { n2 = CL2; full = 1; }
-  DM_SYNC();
-  bool hit = false, dropped = false;
-  float dist = 0.f, margin = 0.f;
-  V3 nrm = {1.f, 0.f, 0.f}, cpos = {0.f, 0.f, 0.f};
-  int a = 0, b = 0;
-  if (lane < n2) {
-    const unsigned w = cl2[lane];
-    a = w & 255; b = w >> 8;
-    margin = pair_margin(a, b);
-    const cvx::Contact ct = cvx::collide(self_geom(T, M, gc, a), self_geom(T, M, gc, b));
-    dist = ct.dist; nrm = ct.n; cpos = ct.pos;
-    hit = dist <= margin;
-    if (hit && dist >= margin - (margin != 0.f ? M.sc_gap : 0.f)) {  // (inactive and no adhesion actuator takes part: no slot)
-      dropped = no_adhesion(a, b);
-      hit = !dropped;
-    }
-  }
-  unsigned long long bal = __ballot(hit);
-  int ovf = 0;
-  if (nprev + __popcll(bal) > NC) {  // more than the free slots: the env is flagged and the deepest are kept
-    ovf = 1;
-    int rank = 0;
-    for (unsigned long long m = bal; m; m &= m - 1) {
-      const int j = __ffsll((long long)m) - 1;
-      const float dj = __shfl(dist, j);
-      if (dj < dist || (dj == dist && j < lane)) rank++;
-    }
-    hit = hit && rank < NC - nprev;
-    bal = __ballot(hit);
-  }
-  const int n = __popcll(bal), idx = nprev + __popcll(bal & ((1ull << lane) - 1ull));
-  if (hit && idx < NC) self_put(T, M, idx, M.cg_link[a], M.cg_link[b], nrm, cpos, dist, margin, M.cg_invw[a] + M.cg_invw[b]);
-  DM_SYNC();
-  return n | (ovf << 8) | (full << 9) | (__popcll(__ballot(dropped)) << 16);
-}
+};
+
 
 // sum over the fly-fly contacts whose row touches hinge f of J[k][f] w[k - nc] (w: the rows' forces or the adhesion pulls)
 template <class TileX>
@@ -1679,8 +1507,8 @@ __device__ __forceinline__ void walk_substeps(Tile &T, const WalkModel *__restri
         //      Every substep runs both passes (the mouth parts touch in every pose: there is no "nothing in reach" shortcut).
         if (lane < 6) T.sv0[lane] = comp(c.V0, lane);  // (visible after the first pass's own barrier, as the three stores below)
         if (lane < c.fl.nc) { T.c_link1[lane] = 255; T.c_blk1[lane] = 255; T.c_amask1[lane] = 0; }  // a floor slot: one chain
-        const int sc = __builtin_amdgcn_readfirstlane(self_prim_collide(c.T, (ModelPtr)c.M, c.X, lane, c.fl.nc));
-        const int cc = __builtin_amdgcn_readfirstlane(self_convex_collide(c.T, (ModelPtr)c.M, lane, c.fl.nc + (sc & 0xff)));
+        const int sc = __builtin_amdgcn_readfirstlane(prim_pairs(c.T, (ModelPtr)c.M, WalkPairs<Tile>{c.X}, lane, c.fl.nc));
+        const int cc = __builtin_amdgcn_readfirstlane(convex_pairs<WalkPairs<Tile>>(c.T, (ModelPtr)c.M, lane, c.fl.nc + (sc & 0xff)));
         c.fl.ns = (sc & 0xff) + (cc & 0xff);
         if (((sc | cc) >> 8) & 1) c.overflow |= 1;
         if ((cc >> 9) & 1) c.overflow |= 8;
