@@ -30,6 +30,7 @@ FFE_WALK_FLOOR = 2048  # ffe_create_walk_physics only: the floor plane against t
 #                        with FFE_WALK_EPISODES the walk_imitation environment on the floor)
 FFE_WALK_SELF = 4096  # ffe_create_walk_physics only: the fly's own contacts on the floor handle, bare physics or environment (provisional opt-in)
 FFE_WALK_SELF_EPISODES = 8192  # ffe_create_walk_physics only: next to FFE_WALK_SELF under the environment (the three bits alone stay refused)
+FFE_WALK_FLOOR_CONVEX = 32768  # ffe_create_walk_physics only: the floor against the fly's ellipsoids and cylinders, bare physics with FFE_WALK_FLOOR | FFE_WALK_SELF
 
 
 # `env.validity()`: four int32 [B] views of one [B, 4] device buffer (include/flybody_env.h, ffe_get_validity)
@@ -509,6 +510,11 @@ class BatchedWalkPhysics(EnvHandle):
     them.  `get_task_state()` int 5 then counts both kinds, int 3 the fly-fly ones among them, real 1 is taken over both kinds, and
     step_bits bit value 8 says that a convex candidate pair was left out because a pair list of the substep was full.
 
+    `floor_convex=True` (keyword-only; step 3d; it needs both `floor_contacts=True` and `self_contacts=True`) adds FFE_WALK_FLOOR_CONVEX:
+    the floor plane also against the fly's 16 ellipsoids (thorax, head, mouth parts, wings, coxae) and 6 cylinders (abdomen), so that a
+    fly on its back or on its abdomen rests on the floor.  Their contacts are floor contacts like the others (slots behind the
+    primitive floor contacts, the 16 deepest of both kinds kept); `get_task_state()` real 2 counts them among int 5.
+
     Tensor conventions are `BatchedBallEnv`'s: `get_state` returns float64 cuda tensors qpos[B, 109] = root position (float64 on the
     device too), root quaternion, 102 hinges and qvel[B, 108] = root linear velocity (world frame), root angular velocity (body
     frame), hinges; `set_state` takes the same and normalises the quaternion; `physics_step` takes float32 ctrl[B, 59]."""
@@ -516,15 +522,20 @@ class BatchedWalkPhysics(EnvHandle):
     task_kind = "walk_physics"
 
     def __init__(self, *, batch_size: int, device: int = 0, physics_flags: int = FFE_NO_CONTACT | FFE_NO_LIMIT, blob_path: str = WALK_BLOB,
-                 joint_limits: bool = False, floor_contacts: bool = False, self_contacts: bool = False):
+                 joint_limits: bool = False, floor_contacts: bool = False, self_contacts: bool = False, floor_convex: bool = False):
         if self_contacts and not floor_contacts:
             raise ValueError("BatchedWalkPhysics: self_contacts=True needs floor_contacts=True (the fly's own contacts are built on the floor handle)")
+        if floor_convex and not (floor_contacts and self_contacts):
+            raise ValueError("BatchedWalkPhysics: floor_convex=True needs floor_contacts=True and self_contacts=True (the floor against "
+                             "ellipsoids and cylinders is built on the handle that carries both)")
         if joint_limits or floor_contacts:
             physics_flags = (int(physics_flags) & ~(FFE_NO_CONTACT | FFE_NO_LIMIT)) | FFE_NO_CONTACT | FFE_WALK_JOINT_LIMITS
         if floor_contacts:
             physics_flags |= FFE_WALK_FLOOR
         if self_contacts:
             physics_flags |= FFE_WALK_SELF
+        if floor_convex:
+            physics_flags |= FFE_WALK_FLOOR_CONVEX
         self._open(batch_size, device)
         with open(blob_path, "rb") as f:
             blob = f.read()

@@ -208,7 +208,9 @@ __global__ void episode_init_kernel(EpState *eps, int batch) {
 //             contacts kept in the last substep (floor and, with FFE_WALK_SELF, fly-fly), 0 off the floor; solver iterations of the last
 //             substep; overflow bits of the last launch
 //   reals     on the floor the sum of the contacts' normal forces and the smallest contact distance (0 without a contact; with
-//             FFE_WALK_SELF over both kinds), and on an episode handle, where int 3 is taken, the fly-fly count in real 2; zeros otherwise
+//             FFE_WALK_SELF over both kinds), and on an episode handle, where int 3 is taken, the fly-fly count in real 2; on a bare-physics
+//             handle with FFE_WALK_FLOOR_CONVEX real 2 is the plane-ellipsoid / plane-cylinder contacts among int 5 (bits 8 .. 15 of the
+//             record's nself, zero from every other kernel); zeros otherwise
 //   validity  {overflow bits of the last launch (1 more contacts than slots, 2 more rows than RMAX, 4 more rows in a block than columns,
 //             8 a convex candidate pair left out because a pair list of the substep was full), episode_flagged_steps, episode_bits,
 //             episode_steps}, the last three zero without an episode record
@@ -219,11 +221,11 @@ __global__ void walk_report_kernel(const EpState *eps, const WState *states, con
   if (ints) {
     int *o = ints + (size_t)i * 8;
     o[0] = eps ? eps[i].clip : 0; o[1] = eps ? eps[i].step : 0; o[2] = eps ? (int)(unsigned)eps[i].episode : 0;
-    o[3] = eps ? eps[i].needs_reset : (rec ? rec[i].nself : 0);
+    o[3] = eps ? eps[i].needs_reset : (rec ? (rec[i].nself & 0xff) : 0);
     o[4] = S.nlim; o[5] = rec ? rec[i].ncon : 0; o[6] = S.iters; o[7] = S.step_bits;
     double *r = reals + (size_t)i * 8;
     for (int k = 0; k < 8; k++) r[k] = 0.0;
-    if (rec) { r[0] = (double)rec[i].fsum; r[1] = (double)rec[i].mind; if (eps) r[2] = (double)rec[i].nself; }
+    if (rec) { r[0] = (double)rec[i].fsum; r[1] = (double)rec[i].mind; r[2] = eps ? (double)rec[i].nself : (double)(rec[i].nself >> 8); }
   }
   if (info) *reinterpret_cast<int4 *>(info + (size_t)i * 4) = eps ? make_int4(S.step_bits, eps[i].ep_flagged, eps[i].ep_bits, eps[i].step) : make_int4(S.step_bits, 0, 0, 0);
 }
@@ -284,6 +286,8 @@ struct WalkEnv final : ffe::EnvBackend {
   WalkHost host;
   ffe::DeviceBuffers mem{"ffe_create_walk_physics"};  // everything below lives here
   WalkModel *model_dev = nullptr;
+  WalkModelFull *full_dev = nullptr;  // FFE_WALK_FLOOR_CONVEX only: the model with the second floor table behind it (model_dev = &full_dev->m);
+                                      // floor_full_step of walk_full_env.hip steps this handle
   WState *states = nullptr;
   // episode handle only
   ffe_walktask_handle task = nullptr;  // the float32 task layer of this env
@@ -331,7 +335,8 @@ struct WalkEnv final : ffe::EnvBackend {
     hipStream_t s = (hipStream_t)stream;
     if (mode == 2) {  // bare physics: act = ctrl[B][59]
       if (!act || nphys <= 0) throw std::runtime_error("walk physics: null control buffer or no steps");
-      if (self) launch_floor_self_step(model_dev, flags, states, act, rec, batch, nphys, s);
+      if (full_dev) launch_floor_full_step(full_dev, flags, states, act, rec, batch, nphys, s);
+      else if (self) launch_floor_self_step(model_dev, flags, states, act, rec, batch, nphys, s);
       else if (floor) hipLaunchKernelGGL(floor_step, dim3(batch), dim3(64), 0, s, model_dev, flags, states, act, rec, batch, nphys);
       else if (limits) hipLaunchKernelGGL(walk_limits_kernel, dim3(batch), dim3(64), 0, s, model_dev, flags, states, act, batch, nphys);
       else hipLaunchKernelGGL(walk_step_kernel, dim3(batch), dim3(64), 0, s, model_dev, flags, states, act, batch, nphys);
@@ -487,7 +492,14 @@ std::unique_ptr<ffe::EnvBackend> walk_create(const void *blob, size_t blob_size,
   const bool limits = (physics_flags & BF_WALK_JOINT_LIMITS) != 0;
   const bool episodes = (physics_flags & BF_WALK_EPISODES) != 0, floor = (physics_flags & BF_WALK_FLOOR) != 0;
   const bool self = (physics_flags & BF_WALK_SELF) != 0, self_env = (physics_flags & BF_WALK_SELF_EPISODES) != 0;
-  if (self || self_env) {  // the fly's own contacts: refusals of their own, which the table does not express
+  const bool convex = (physics_flags & BF_WALK_FLOOR_CONVEX) != 0;
+  if (convex) {  // the floor against ellipsoids and cylinders: one accepted set, bare physics
+    if ((physics_flags & ~kSwitches) != (BF_NO_CONTACT | BF_WALK_JOINT_LIMITS | BF_WALK_FLOOR | BF_WALK_SELF | BF_WALK_FLOOR_CONVEX))
+      throw std::runtime_error("ffe_create_walk_physics: FFE_WALK_FLOOR_CONVEX (the floor plane against the fly's ellipsoids and cylinders, bare "
+                               "physics) is accepted only as FFE_NO_CONTACT | FFE_WALK_JOINT_LIMITS | FFE_WALK_FLOOR | FFE_WALK_SELF | "
+                               "FFE_WALK_FLOOR_CONVEX plus the force switches, FFE_NO_NOSLIP and FFE_NO_ADHESION: it excludes FFE_NO_LIMIT, and "
+                               "under the environment (FFE_WALK_EPISODES) it is not built yet");
+  } else if (self || self_env) {  // the fly's own contacts: refusals of their own, which the table does not express
     if (episodes && !floor)
       throw std::runtime_error("ffe_create_walk_physics: FFE_WALK_SELF (the fly's own contacts) with FFE_WALK_EPISODES needs FFE_WALK_FLOOR: the "
                                "walk_imitation environment with the floor off does not carry the fly's own contacts");
@@ -517,8 +529,20 @@ std::unique_ptr<ffe::EnvBackend> walk_create(const void *blob, size_t blob_size,
   if (self) build_walk_self(b, e->host);  // (before the model goes to the device)
   if (floor && !e->host.m.x.f_ok)
     throw std::runtime_error("ffe_create_walk_physics: FFE_WALK_FLOOR: the floor's contacts are expected to be condim 3 with one solimp");
+  if (convex) {
+    build_walk_floor_convex(b, e->host);
+    if (!e->host.xc.ok)
+      throw std::runtime_error("ffe_create_walk_physics: FFE_WALK_FLOOR_CONVEX: the floor's contacts with the ellipsoids and cylinders are expected to "
+                               "be condim 3 with the solimp of its other contacts");
+  }
   e->host.m.b.nsub = 10;  // the reference's control step of 2 ms over the model's 0.2 ms (bare physics: ffe_spec's figure alone)
-  e->model_dev = e->mem.zeroed<WalkModel>(1);
+  if (convex) {
+    e->full_dev = e->mem.zeroed<WalkModelFull>(1);
+    e->model_dev = &e->full_dev->m;
+    HIP_OK(hipMemcpy(&e->full_dev->xc, &e->host.xc, sizeof(WalkFloorConvex), hipMemcpyHostToDevice));
+  } else {
+    e->model_dev = e->mem.zeroed<WalkModel>(1);
+  }
   HIP_OK(hipMemcpy(e->model_dev, &e->host.m, sizeof(WalkModel), hipMemcpyHostToDevice));
   e->states = e->mem.zeroed<WState>((size_t)batch);
   hipLaunchKernelGGL(walk_init_states, dim3(batch), dim3(64), 0, 0, e->states, e->model_dev, batch);

@@ -43,11 +43,33 @@ struct WalkModel {
   WalkExtra x;
 };
 
+// ---- the floor plane against the fly's ellipsoid / cylinder geoms (FFE_WALK_FLOOR_CONVEX; lane = row in
+//      the second floor pass): the geoms of these two types that pass mj_collision's filters against the floor geom, in model order, with
+//      the pair's parameters by `floor_geom_params`.  A table of its own: WalkExtra keeps its bytes and the 48 rows of f_* their order
+//      (`build_walk_self` checks both), and 48 + 22 rows would not fit NL lanes.  A contact names its geom in the tile's c_geom as
+//      NPG + row: 0 .. NPG - 1 are the rows of WalkExtra::f_*.
+constexpr int NFC = 24;  // rows (22 on the shipped model), padded
+struct WalkFloorConvex {
+  int n, ok;                         // rows; 0 if some pair is not condim 3 or does not share WalkExtra::f_solimp (the bit is then refused)
+  int geom[NFC], type[NFC];          // the geom's index in the model; 4 ellipsoid, 5 cylinder
+  int link[NFC], adh[NFC], blk[NFC], amask[NFC];  // link of the geom (-1: a geom of the root body, which has no chain: blk 255, amask 0),
+                                                  // its body's adhesion actuator (-1: none), block and dof mask of its chain
+  float pos[3][NFC], quat[4][NFC], size[3][NFC];  // frame in its link (in the root for a root geom), sizes
+  float fric[NFC], K[NFC], B[NFC], margin[NFC], gap[NFC], invw[NFC];
+};
+// The model of a handle with that bit: the table lies directly behind the WalkModel every walk kernel reads, so that the one kernel that
+// knows of it finds it from the WalkExtra pointer it already carries.
+struct WalkModelFull {
+  WalkModel m;
+  WalkFloorConvex xc;
+};
+
 struct WalkHost {
   WalkModel m;
   std::vector<float> action_min, action_max;
   double root_mass = 0, total_mass = 0;
   int nq = 109, nv = 108;
+  WalkFloorConvex xc{};  // filled by build_walk_floor_convex (walk_self_model.hpp) for a handle with FFE_WALK_FLOOR_CONVEX alone
 };
 
 // One floor candidate in float64: the geom in its link's frame and the contact parameters of the pair (floor geom `fg`, geom `g`) by
@@ -192,7 +214,7 @@ inline WalkHost build_walk_model(const Blob &b) {
     for (int l = 0; l < NL; l++) { X.f_link[l] = -1; X.f_adh[l] = -1; }
     for (int g = 0; g < (int)gbody.count; g++) {
       const int body = gbody.i(g), l = lane_of[(size_t)body], ty = gtype.i(g);
-      if (l < 0 || (ty != 2 && ty != 3)) continue;  // a plane against an ellipsoid or a cylinder is not built
+      if (l < 0 || (ty != 2 && ty != 3)) continue;  // (a plane against an ellipsoid or a cylinder: WalkFloorConvex, a table of its own)
       if (!((gct.i(fg) & gca.i(g)) || (gct.i(g) & gca.i(fg)))) continue;
       bool skip = false;
       for (int e = 0; e < nex; e++) skip |= (excl.i(2 * e) == 0 && excl.i(2 * e + 1) == body) || (excl.i(2 * e) == body && excl.i(2 * e + 1) == 0);

@@ -9,8 +9,8 @@
 //   a geom of the thorax has no link (`cg_link` -1) and its frame in the root is its frame in the thorax body: the root frame IS the
 //            thorax frame;
 //   the blob's candidate list (`cand_g1` / `cand_g2`, flybody_amd/model/reach.py) also holds the 70 pairs with the floor plane: the 48
-//            (plane, sphere / capsule) ones are the floor pass's, the 22 (plane, ellipsoid / cylinder) ones are not built (the oracle does
-//            not restate them either); neither kind is a fly-fly pair and both are skipped here.
+//            (plane, sphere / capsule) ones are the floor pass's, the 22 (plane, ellipsoid / cylinder) ones the second floor pass's
+//            (`build_walk_floor_convex` below; the oracle does not restate them); neither kind is a fly-fly pair and both are skipped here.
 // No kernel but `floor_self_step` reads these fields, and `walk_create` calls this only for a handle with the bit.
 #pragma once
 
@@ -127,11 +127,51 @@ inline void build_walk_self(const Blob &b, WalkHost &W) {
   for (size_t k = 0; k < cg1.count; k++) {
     int g1 = cg1.i(k), g2 = cg2.i(k);
     if (gtype.i(g1) > gtype.i(g2)) std::swap(g1, g2);
-    if (gtype.i(g1) == 0) continue;                      // a pair with the floor plane: the floor pass's, or not built
+    if (gtype.i(g1) == 0) continue;                      // a pair with the floor plane: one of the two floor passes'
     if (gtype.i(g1) < 4 && gtype.i(g2) < 4) continue;    // a sphere / capsule pair: sp_mask has it
     if (fg[(size_t)g1] < 0 || fg[(size_t)g2] < 0) throw std::runtime_error("walk model: a candidate pair names an unknown geom");
     if (M.ncp >= NCP) throw std::runtime_error("walk model: more convex candidate pairs than the list holds");
     M.cp_pair[M.ncp++] = (unsigned short)(fg[(size_t)g1] | (fg[(size_t)g2] << 8));
+  }
+}
+
+// The second floor table (FFE_WALK_FLOOR_CONVEX): the (plane, ellipsoid / cylinder) pairs the two tables
+// above leave out, filtered as `build_walk_model` filters the 48 primitive ones.  A geom of the thorax has no link: the thorax is the root.
+inline void build_walk_floor_convex(const Blob &b, WalkHost &W) {
+  using namespace detail;
+  const BallModel &M = W.m.b;
+  const WalkExtra &X = W.m.x;
+  WalkFloorConvex &F = W.xc;
+  std::memset(&F, 0, sizeof(F));
+  const Tensor &gbody = b.get("geom_bodyid"), &gtype = b.get("geom_type"), &gsize = b.get("geom_size"), &gpos = b.get("geom_pos"),
+               &gquat = b.get("geom_quat"), &gct = b.get("geom_contype"), &gca = b.get("geom_conaffinity"), &excl = b.get("exclude_pairs"),
+               &bpar = b.get("body_parentid");
+  const int nb = (int)bpar.count, fg = X.floor_geom, nex = (int)excl.count / 2, thorax = 1;
+  std::vector<int> lane_of((size_t)nb, -1);
+  for (int l = 0; l < NL; l++) lane_of[(size_t)M.l_body[l]] = l;
+  F.ok = 1;
+  for (int g = 0; g < (int)gbody.count; g++) {
+    const int body = gbody.i(g), l = lane_of[(size_t)body], ty = gtype.i(g);
+    if (g == fg || (ty != 4 && ty != 5)) continue;
+    if (!((gct.i(fg) & gca.i(g)) || (gct.i(g) & gca.i(fg)))) continue;
+    bool skip = false;
+    for (int e = 0; e < nex; e++) skip |= (excl.i(2 * e) == 0 && excl.i(2 * e + 1) == body) || (excl.i(2 * e) == body && excl.i(2 * e + 1) == 0);
+    if (skip) continue;
+    if (l < 0 && body != thorax) throw std::runtime_error("walk model: a floor candidate on an unexpected body");
+    if (F.n >= NFC) throw std::runtime_error("walk model: more ellipsoid / cylinder floor candidates than the table holds");
+    const int s = F.n++;
+    const FloorGeom fp = floor_geom_params(b, fg, g);
+    F.geom[s] = g; F.type[s] = ty; F.link[s] = l;
+    if (l >= 0) {
+      const int last = M.s_dof[M.l_ndof[l] - 1][l];
+      F.adh[s] = M.l_adh[l]; F.blk[s] = M.d_blk[last]; F.amask[s] = M.d_amask[last];
+    } else { F.adh[s] = -1; F.blk[s] = 255; F.amask[s] = 0; }
+    for (int k = 0; k < 3; k++) { F.pos[k][s] = (float)gpos.f(3 * g + k); F.size[k][s] = (float)gsize.f(3 * g + k); }
+    for (int k = 0; k < 4; k++) F.quat[k][s] = (float)gquat.f(4 * g + k);
+    F.fric[s] = (float)fp.fric; F.K[s] = (float)fp.K; F.B[s] = (float)fp.B; F.margin[s] = (float)fp.margin; F.gap[s] = (float)fp.gap;
+    F.invw[s] = (float)fp.invw;
+    if (fp.condim != 3) F.ok = 0;
+    for (int k = 0; k < 5; k++) if (X.f_solimp[k] != (float)fp.solimp[k]) F.ok = 0;  // the same rule as f_ok
   }
 }
 

@@ -17,6 +17,7 @@
 #include "row_newton.hpp"
 #include "walk_imu.hpp"
 #include "walk_floor.hpp"
+#include "walk_floor_convex.hpp"
 #include "walk_sense.hpp"
 #include "walk_self_sense.hpp"
 #include "walk_self.hpp"
@@ -44,6 +45,7 @@ constexpr int BF_WALK_EPISODES = 1024;     // FFE_WALK_EPISODES: host side only
 constexpr int BF_WALK_FLOOR = 2048;        // FFE_WALK_FLOOR: host side only (it selects the floor kernel)
 constexpr int BF_WALK_SELF = 4096;         // FFE_WALK_SELF: host side only (it selects the kernel with the fly's own contacts)
 constexpr int BF_WALK_SELF_EPISODES = 8192;  // FFE_WALK_SELF_EPISODES: host side only (FFE_WALK_SELF under the environment is asked for by it)
+constexpr int BF_WALK_FLOOR_CONVEX = 32768;  // FFE_WALK_FLOOR_CONVEX: host side only (it selects the kernel with the second floor pass)
 constexpr int LCOL = 16;                  // solve columns per block of M: a block has at most NSTEP = 14 hinges, each with one limit row
 static_assert(NSTEP <= LCOL, "a block's limit rows must fit its columns");
 
@@ -54,6 +56,7 @@ struct TileKind {
   static constexpr bool kSense = false;         // the sensor sums of the environment on the floor
   static constexpr bool kSelf = false;          // the second chain of a fly-fly contact
   static constexpr bool kPackedNormal = false;  // a fly-fly slot keeps its normal in floats it leaves unused (WTileSX)
+  static constexpr bool kConvexFloor = false;   // the second floor pass: the plane against ellipsoids and cylinders (WTileXC)
 };
 
 struct alignas(16) WTile : TileKind {
@@ -146,7 +149,9 @@ struct FloorCtx {
   int nc;          // contacts kept in this substep
   float mind;      // smallest distance
 };
-struct FloorRec { int ncon; float fsum, mind; int nself; };  // (nself: the fly-fly contacts among ncon; 0 without FFE_WALK_SELF)
+// (nself: the fly-fly contacts among ncon, 0 without FFE_WALK_SELF; with FFE_WALK_FLOOR_CONVEX bits 8 .. 15 count the plane-ellipsoid /
+//  plane-cylinder contacts among ncon: both are at most NC = 16, and every other kernel leaves those bits zero)
+struct FloorRec { int ncon; float fsum, mind; int nself; };
 
 // Tile of the episode kernel: the limits kernel's, plus the sensor sums of a control step (accelerometer 3, gyro 3, velocimeter 3,
 // force 18, touch 6: the order of the oracle's buffer)
@@ -196,6 +201,23 @@ static_assert((NG + (CL1 * 2 + 15) / 16 + (CL2 * 2 + 15) / 16) <= NDP, "the geom
 struct SelfCtx : FloorCtx {
   int ns;          // fly-fly contacts kept in this substep: slots nc .. nc + ns - 1
 };
+// Tile of the kernel with the second floor pass (walk_full_env.hip `floor_full_step`, FFE_WALK_FLOOR_CONVEX; DESIGN.md section 12 step
+// 3d): the self tile as it is.  A plane-ellipsoid / plane-cylinder contact is a floor slot like any other - it sits behind the primitive
+// floor contacts and in front of the fly-fly ones, and `nc` counts both kinds - whose c_geom is NPG + its row of WalkFloorConvex; a slot
+// of a root geom has c_link = c_blk = 255 and an empty c_amask (no chain: its rows have the root entries alone).  The pass needs no
+// scratch: a lane keeps its row's candidates in registers, and in the overflow case a primitive slot moves through its lane's registers.
+struct alignas(16) WTileXC : WTileX {
+  static constexpr bool kConvexFloor = true;
+};
+static_assert(sizeof(WTileXC) == sizeof(WTileX), "the second floor pass adds nothing to the tile");
+static_assert(NPG + NFC <= 255 && NFC <= 64 && NC <= 64, "c_geom names both tables' rows in a byte; a lane per row and per slot");
+struct FullCtx : SelfCtx {
+  int nv;          // plane-ellipsoid / plane-cylinder contacts among the nc floor contacts of this substep
+};
+// the table of the second floor pass: directly behind the WalkModel whose WalkExtra the wave carries (WalkModelFull)
+__device__ __forceinline__ const WalkFloorConvex FFE_GLOBAL *convex_table(const WalkExtra FFE_GLOBAL *X) {
+  return (const WalkFloorConvex FFE_GLOBAL *)((const char FFE_GLOBAL *)X - offsetof(WalkModel, x) + offsetof(WalkModelFull, xc));
+}
 struct NoSelf { constexpr operator int() const { return 0; } };  // the fly-fly count of a tile without them: an argument that takes no register
 __device__ __forceinline__ NoSelf self_count(const FloorCtx &) { return {}; }
 __device__ __forceinline__ int self_count(const SelfCtx &fl) { return fl.ns; }
@@ -282,7 +304,7 @@ struct CtxT {
   I10 Itree;    // spatial inertia of the whole tree about the root origin = M_rr
   S6 Ftot;      // bias force of the whole tree without gravity = -(root rows of the smooth force)
   int overflow; // limits kernel: overflow bits of this launch
-  std::conditional_t<Tile::kSelf, SelfCtx, std::conditional_t<Tile::kFloor, FloorCtx, NoEpisode>> fl;
+  std::conditional_t<Tile::kConvexFloor, FullCtx, std::conditional_t<Tile::kSelf, SelfCtx, std::conditional_t<Tile::kFloor, FloorCtx, NoEpisode>>> fl;
 };
 
 // ------------------------------------------------------------------------------------------------ stage 1
@@ -636,6 +658,135 @@ __device__ __forceinline__ void floor_frame(const C &c, float (&fr)[9]) {
 // times closer (with FFE_NO_NOSLIP, where no sweep polishes the tangential forces, the one-substep error of root_ang was 3.6e-4 at 1).
 constexpr float kFloorScale = 1e-2f;
 
+// ------------------------------------------------------------------------------------------------ the second floor pass
+// (FFE_WALK_FLOOR_CONVEX)  mj: mj_collision for the pairs (floor plane, ellipsoid / cylinder of the fly):
+// mjc_PlaneConvex and mjc_PlaneCylinder as walk_floor_convex.hpp restates them, in the root frame.  Lane g tests row g of WalkFloorConvex
+// against the pose its link published in T.lp (`floor_collide` has run); a root geom's pose is the identity and it moves with the root's
+// own (w_b, v_b) in T.sv0.  A row gives up to four contacts, each in a fixed register slot.  Kept contacts follow the `nprim` primitive
+// floor contacts in (row, contact) order.  More than NC in all: the NC deepest floor contacts of both kinds are kept - ties go to the
+// earlier slot, a primitive contact before any of this pass - and the primitive slots that remain are moved up, in order, through their
+// lanes' registers.  Returns contacts of this pass | overflow << 8 | primitive contacts left << 16.  Out of line and a leaf.
+template <class TileX>
+__device__ __noinline__ int floor_convex_collide(TileX *Tp, const WalkFloorConvex FFE_GLOBAL *Fp, const int lane, const int nprim, const float nx, const float ny,
+                                                 const float nz, const double height) {
+  TileX &T = *Tp;
+  const WalkFloorConvex FFE_GLOBAL &F = *Fp;
+  DM_SYNC();  // (T.sv0 was written just before the call)
+  const float n[3] = {nx, ny, nz};
+  const float inf = __builtin_inff();
+  float sp[4][3], dd[4] = {inf, inf, inf, inf}, incl = 0.f;
+  int mask = 0, link = -1;
+#pragma unroll
+  for (int e = 0; e < 4; e++) sp[e][0] = sp[e][1] = sp[e][2] = 0.f;
+  const int nrow = F.n;
+  if (lane < nrow) {
+    link = F.link[lane];
+    Q4 q = {F.quat[0][lane], F.quat[1][lane], F.quat[2][lane], F.quat[3][lane]};
+    V3 cv = {F.pos[0][lane], F.pos[1][lane], F.pos[2][lane]};
+    if (link >= 0) {
+      const float *lp = T.lp[link];
+      const Q4 lq = {lp[3], lp[4], lp[5], lp[6]};
+      cv = V3{lp[0], lp[1], lp[2]} + qrot(lq, cv);
+      q = qnormalize(qmul(lq, q));
+    }
+    const M3 Rr = q2m(q);
+    const float R[9] = {Rr.m0, Rr.m1, Rr.m2, Rr.m3, Rr.m4, Rr.m5, Rr.m6, Rr.m7, Rr.m8}, cc[3] = {cv.x, cv.y, cv.z};
+    const float margin = F.margin[lane];
+    incl = margin - F.gap[lane];
+    if (F.type[lane] == 4) {
+      const float s[3] = {F.size[0][lane], F.size[1][lane], F.size[2][lane]};
+      wfc::ellipsoid_support<float>(n, cc, R, s, sp[0]);
+      dd[0] = wf::plane_distance<float>(height, n, sp[0], 0.f);
+      mask = dd[0] <= margin ? 1 : 0;
+    } else {
+      const float dist0 = wf::plane_distance<float>(height, n, cc, 0.f);
+      mask = wfc::plane_cylinder<float>(n, cc, R, F.size[0][lane], F.size[1][lane], dist0, margin, sp, dd);
+    }
+    // inside the margin but not inside margin - gap: exerts nothing, kept only where an adhesion actuator counts it (as the fly-fly passes)
+    const bool counted = F.adh[lane] >= 0;
+#pragma unroll
+    for (int e = 0; e < 4; e++) {
+      if (dd[e] >= incl && !counted) mask &= ~(1 << e);
+      if (!((mask >> e) & 1)) dd[e] = inf;
+    }
+  }
+  unsigned long long be[4];
+  int total = 0;
+#pragma unroll
+  for (int e = 0; e < 4; e++) { be[e] = __ballot((mask >> e) & 1); total += (int)__popcll(be[e]); }
+  const unsigned long long lt = (1ull << lane) - 1ull;
+  int np = nprim, over = 0;
+  if (nprim + total > NC) {
+    over = 1;
+    // ranks over the union: key of primitive slot k = k, of (row g, contact e) = NC + 4 g + e
+    const float dp = lane < nprim ? T.c_dist[lane] : inf;
+    int rp = 0, r[4] = {0, 0, 0, 0};
+    const int nj = max(nprim, nrow);
+    for (int j = 0; j < nj; j++) {
+      const float djp = __shfl(dp, j);
+      if (djp < dp || (djp == dp && j < lane)) rp++;
+#pragma unroll
+      for (int e = 0; e < 4; e++) if (djp <= dd[e]) r[e]++;
+#pragma unroll
+      for (int e2 = 0; e2 < 4; e2++) {
+        const float dj = __shfl(dd[e2], j);
+        if (dj < dp) rp++;
+#pragma unroll
+        for (int e = 0; e < 4; e++) if (dj < dd[e] || (dj == dd[e] && (j < lane || (j == lane && e2 < e)))) r[e]++;
+      }
+    }
+    // (an absent candidate is +inf: it beats nothing that is there, and its own rank is not read)
+    const bool keep = lane < nprim && rp < NC;
+#pragma unroll
+    for (int e = 0; e < 4; e++) if (r[e] >= NC) mask &= ~(1 << e);
+    const unsigned long long bk = __ballot(keep);
+    np = (int)__popcll(bk);
+    // move the primitive slots that stay: read, barrier, write
+    float m_pos[3] = {0.f, 0.f, 0.f}, m_vel[3] = {0.f, 0.f, 0.f}, m_dist = 0.f;
+    int m_excl = 0, m_geom = 0, m_link = 0, m_blk = 0, m_amask = 0;
+    if (keep) {
+#pragma unroll
+      for (int k = 0; k < 3; k++) { m_pos[k] = T.c_pos[lane][k]; m_vel[k] = T.c_vel[lane][k]; }
+      m_dist = T.c_dist[lane]; m_excl = T.c_excl[lane]; m_geom = T.c_geom[lane]; m_link = T.c_link[lane]; m_blk = T.c_blk[lane]; m_amask = T.c_amask[lane];
+    }
+    DM_SYNC();
+    if (keep) {
+      const int at = (int)__popcll(bk & lt);
+#pragma unroll
+      for (int k = 0; k < 3; k++) { T.c_pos[at][k] = m_pos[k]; T.c_vel[at][k] = m_vel[k]; }
+      T.c_dist[at] = m_dist; T.c_excl[at] = (unsigned char)m_excl; T.c_geom[at] = (unsigned char)m_geom; T.c_link[at] = (unsigned char)m_link;
+      T.c_blk[at] = (unsigned char)m_blk; T.c_amask[at] = (unsigned short)m_amask;
+    }
+    total = 0;
+#pragma unroll
+    for (int e = 0; e < 4; e++) { be[e] = __ballot((mask >> e) & 1); total += (int)__popcll(be[e]); }
+  }
+  int idx = np;
+#pragma unroll
+  for (int e = 0; e < 4; e++) idx += (int)__popcll(be[e] & lt);
+#pragma unroll
+  for (int e = 0; e < 4; e++) {
+    if ((mask >> e) & 1) {
+      if (idx < NC) {
+        const float dist = dd[e];
+        float p[3], v[3];
+        wf::contact_position<float>(sp[e], n, 0.f, dist, p);
+        wf::point_velocity<float>(link >= 0 ? &T.lp[link][7] : T.sv0, p, v);
+        T.c_pos[idx][0] = p[0]; T.c_pos[idx][1] = p[1]; T.c_pos[idx][2] = p[2];
+        T.c_vel[idx][0] = v[0]; T.c_vel[idx][1] = v[1]; T.c_vel[idx][2] = v[2];
+        T.c_dist[idx] = dist;
+        T.c_excl[idx] = dist >= incl ? 1 : 0;
+        T.c_geom[idx] = (unsigned char)(NPG + lane);
+        T.c_link[idx] = (unsigned char)(link >= 0 ? link : 255);
+        T.c_blk[idx] = (unsigned char)F.blk[lane]; T.c_amask[idx] = (unsigned short)F.amask[lane];
+      }
+      idx++;
+    }
+  }
+  DM_SYNC();
+  return min(total, NC - np) | (over << 8) | (np << 16);
+}
+
 // ------------------------------------------------------------------------------------------------ the fly's own contacts
 // (FFE_WALK_SELF)  The two collision passes of self_pairs.hpp on the walker's tile, in the root frame: the
 // geoms' frames come from the link poses `floor_collide` has published (T.lp), the narrow phase of the convex pairs is cvx:: of
@@ -782,7 +933,29 @@ __device__ __forceinline__ int contact_forces(C &c, const int R, const int (&lro
   if constexpr (SELF) { if (srow) self_nrm(T, nc + lane - nrc, er); }
   // ---- per floor contact: impedance, D, friction, -aref on its three rows, and the adhesion pull (mj: mj_transmission mjTRN_BODY: -force
   //      along the normal row, the mean over the body's contacts, the ones inside the gap included)
-  if (lane < nc) {
+  if constexpr (Tile::kConvexFloor) {
+    // c_geom runs over both floor tables: 0 .. NPG - 1 the rows of X.f_*, NPG + row those of the second pass's table
+    if (lane < nc) {
+      const WalkFloorConvex FFE_GLOBAL &F = *convex_table(c.X);
+      const int g = T.c_geom[lane], gc = g - NPG;
+      const bool cv = gc >= 0;
+      const float dist = T.c_dist[lane], incl = cv ? F.margin[gc] - F.gap[gc] : X.f_margin[g] - X.f_gap[g];
+      float si_[5];
+#pragma unroll
+      for (int q2 = 0; q2 < 5; q2++) si_[q2] = X.f_solimp[q2];
+      const float imp = impedance(si_, fabsf(dist - incl));
+      const float R0 = fmaxf(1e-15f, (1.f - imp) * (cv ? F.invw[gc] : X.f_invw[g]) * frcp(imp));
+      T.c_D[lane] = T.c_excl[lane] ? 0.f : frcp(R0);
+      T.c_mu[lane] = cv ? F.fric[gc] : X.f_fric[g];
+      const float B = cv ? F.B[gc] : X.f_B[g], K = cv ? F.K[gc] : X.f_K[g];
+      T.r_y0[3 * lane] = B * wf::dot3<float>(&fr[0], T.c_vel[lane]) + K * imp * (dist - incl);
+      T.r_y0[3 * lane + 1] = B * wf::dot3<float>(&fr[3], T.c_vel[lane]);
+      T.r_y0[3 * lane + 2] = B * wf::dot3<float>(&fr[6], T.c_vel[lane]);
+      const int adh = cv ? F.adh[gc] : X.f_adh[g];
+      const int cnt = adh >= 0 ? contacts_of(T.c_link[lane]) : 1;  // (a root geom has no link and no actuator)
+      T.c_w[lane] = adh >= 0 ? -T.frc[adh] / (float)cnt : 0.f;
+    }
+  } else if (lane < nc) {
     const int g = T.c_geom[lane];
     const float dist = T.c_dist[lane], incl = X.f_margin[g] - X.f_gap[g];
     float si_[5];
@@ -853,12 +1026,14 @@ __device__ __forceinline__ int contact_forces(C &c, const int R, const int (&lro
     }
     if (row) {
       T.r_col[lane] = (unsigned char)mycol;
-      if (mycol < KCOL) T.rowof[myb][mycol] = (unsigned char)lane;
+      // (a row of a root geom's contact - block 255 - has no hinge entry: no column, and it asks for no block solve)
+      if (mycol < KCOL && (!Tile::kConvexFloor || myb != 255)) T.rowof[myb][mycol] = (unsigned char)lane;
       if constexpr (SELF) {
         if (myb2 >= 0 && mycol2 < KCOL) T.rowof[myb2][mycol2] = (unsigned char)lane;
         if (myb2 < 0) mycol2 = mycol;
         if (srow) T.c_col1[nc + lane - nrc] = (unsigned char)mycol2;
         mycol = max(mycol, mycol2) + 1;
+        if constexpr (Tile::kConvexFloor) { if (myb == 255) mycol = 0; }
       } else {
         mycol += 1;
       }
@@ -878,7 +1053,9 @@ __device__ __forceinline__ int contact_forces(C &c, const int R, const int (&lro
   const int mycol = row ? (int)T.r_col[lane] : 0;
   // this row: its contact, the link whose chain it spans (a fly-fly row: the links of geom2 and geom1), a limit row's hinge
   const int ck = crow ? lane / 3 : (srow ? nc + lane - nrc : 0);
-  const int lpos = jrow ? (int)T.c_link[ck] : 0, npos = jrow ? M.l_nchain[lpos] : 0;
+  bool rootrow = false;  // a row of a root geom's contact: no chain, the root entries alone
+  if constexpr (Tile::kConvexFloor) rootrow = crow && T.c_link[ck] == 255;
+  const int lpos = (jrow && !rootrow) ? (int)T.c_link[ck] : 0, npos = (jrow && !rootrow) ? M.l_nchain[lpos] : 0;
   int lneg = 255, nneg = 0;
   if constexpr (SELF) { lneg = jrow ? (int)T.c_link1[ck] : 255; nneg = lneg != 255 ? M.l_nchain[lneg] : 0; }
   const int rdof = (row && !jrow) ? (int)T.r_dof[lane] : 0;
@@ -992,7 +1169,7 @@ __device__ __forceinline__ int contact_forces(C &c, const int R, const int (&lro
           if (half == 0) { a0.x += jv * y.x; a0.y += jv * y.y; a0.z += jv * y.z; a0.w += jv * y.w; }
           else { a1.x += jv * y.x; a1.y += jv * y.y; a1.z += jv * y.z; a1.w += jv * y.w; }
         });
-        g_add(a0, myb, cb);
+        if (!rootrow) g_add(a0, myb, cb);
         if (nneg) g_add(a1, myb2 >= 0 ? myb2 : myb, cb);
       } else if (row) {
         const float4 y = T.X4[rdof];
@@ -1502,6 +1679,17 @@ __device__ __forceinline__ void walk_substeps(Tile &T, const WalkModel *__restri
       float md = 0.f;
       for (int k = 0; k < c.fl.nc; k++) md = k == 0 ? T.c_dist[0] : fminf(md, T.c_dist[k]);
       c.fl.mind = md;
+      if constexpr (Tile::kConvexFloor) {
+        // ---- the second floor pass: ellipsoids and cylinders, behind the primitive floor contacts; `nc` then counts both kinds
+        if (lane < 6) T.sv0[lane] = comp(c.V0, lane);  // (the pass starts on a barrier)
+        const int vc = __builtin_amdgcn_readfirstlane(floor_convex_collide(c.T, convex_table(c.X), lane, c.fl.nc, nb.x, nb.y, nb.z, height));
+        c.fl.nv = vc & 0xff;
+        c.fl.nc = ((vc >> 16) & 0xff) + c.fl.nv;
+        if ((vc >> 8) & 1) c.overflow |= 1;
+        md = 0.f;
+        for (int k = 0; k < c.fl.nc; k++) md = k == 0 ? T.c_dist[0] : fminf(md, T.c_dist[k]);
+        c.fl.mind = md;
+      }
       if constexpr (Tile::kSelf) {
         // ---- the fly's own contacts behind the floor's: sphere / capsule pairs, then the pairs with an ellipsoid or a cylinder.
         //      Every substep runs both passes (the mouth parts touch in every pose: there is no "nothing in reach" shortcut).
@@ -1546,7 +1734,8 @@ __device__ __forceinline__ void walk_substeps(Tile &T, const WalkModel *__restri
     if constexpr (LIMITS) { S.nlim = nlim; S.iters = iters; S.step_bits = c.overflow; }
     if constexpr (FLOOR) {
       const int ns = self_count(c.fl);
-      contact_record(ep)[env] = FloorRec{c.fl.nc + ns, T.rootf[6], c.fl.mind, ns};
+      if constexpr (Tile::kConvexFloor) contact_record(ep)[env] = FloorRec{c.fl.nc + ns, T.rootf[6], c.fl.mind, ns | (c.fl.nv << 8)};
+      else contact_record(ep)[env] = FloorRec{c.fl.nc + ns, T.rootf[6], c.fl.mind, ns};
     }
   }
   if constexpr (EP) {
@@ -1587,5 +1776,7 @@ void launch_imitation_self_step(const WalkModel *model, int flags, WState *state
 // `nphys` substeps of bare physics with the floor and the fly's own contacts (walk_self_env.hip): launches `floor_self_step` on `stream`;
 // the caller checks hipGetLastError.
 void launch_floor_self_step(const WalkModel *model, int flags, WState *states, const float *ctrl, FloorRec *rec, int batch, int nphys, hipStream_t stream);
+// ... and with the second floor pass, the plane against ellipsoids and cylinders (walk_full_env.hip): launches `floor_full_step`
+void launch_floor_full_step(const WalkModelFull *model, int flags, WState *states, const float *ctrl, FloorRec *rec, int batch, int nphys, hipStream_t stream);
 
 }  // namespace ffw

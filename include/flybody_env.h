@@ -87,7 +87,15 @@ enum {
   /* ffe_create_walk_physics only: asks for FFE_WALK_SELF under the environment.  It exists because FFE_WALK_EPISODES | FFE_WALK_FLOOR |
    * FFE_WALK_SELF by themselves are a pinned refusal of that create call, as plain FFE_NO_CONTACT is (see FFE_WALK_JOINT_LIMITS):
    * accepted only together with exactly those three and the task, refused in every other set.  Provisional as the four above. */
-  FFE_WALK_SELF_EPISODES = 8192
+  FFE_WALK_SELF_EPISODES = 8192,
+  /* ffe_create_walk_physics only: the floor plane against the fly's remaining geoms too - its 16 ellipsoids (two on the thorax, head,
+   * rostrum, haustellum halves, four wing blades, six coxae) and 6 cylinders (the abdomen segments) - on the bare-physics handle that
+   * carries the floor and the fly's own contacts (csrc/walk_full_env.hip).  With it every geom of fruitfly.xml that the reference's
+   * Walking task collides with its floor (tasks/base.py:331-364) does so here.  Accepted only as FFE_NO_CONTACT | FFE_WALK_JOINT_LIMITS |
+   * FFE_WALK_FLOOR | FFE_WALK_SELF | FFE_WALK_FLOOR_CONVEX plus force switches, FFE_NO_NOSLIP and FFE_NO_ADHESION, bare physics; every
+   * other set with it, any set with FFE_WALK_EPISODES included, is refused with a text naming the bit (the environment is the next
+   * step).  (16384 is not used: a set with it is a pinned refusal.)  Provisional as the five above. */
+  FFE_WALK_FLOOR_CONVEX = 32768
 };
 
 typedef struct ffe_walk_task_s ffe_walk_task; /* the walk_imitation task layer's inputs, defined with ffe_walktask_create below */
@@ -171,8 +179,8 @@ int ffe_create_walk_on_ball(const void *model_blob, size_t blob_size, const ffe_
  * protocol on the device, a fly that falls freely (or floats with FFE_NO_GRAVITY).  FFE_WALK_FLOOR adds the floor plane against the
  * fly's 48 sphere / capsule geoms (elliptic cones, noslip, adhesion) to the bare-physics handle or, together with FFE_WALK_EPISODES,
  * to the environment, whose force and touch columns are then live; FFE_WALK_SELF adds the fly's own contacts to the bare-physics floor
- * handle or, together with FFE_WALK_EPISODES | FFE_WALK_FLOOR | FFE_WALK_SELF_EPISODES, to the environment on the floor.  The floor against ellipsoids and
- * cylinders is not built yet. */
+ * handle or, together with FFE_WALK_EPISODES | FFE_WALK_FLOOR | FFE_WALK_SELF_EPISODES, to the environment on the floor.  FFE_WALK_FLOOR_CONVEX adds
+ * the floor against the fly's ellipsoids and cylinders to the bare-physics handle with both; under the environment it is not built yet. */
 typedef struct {
   /* FFE_NO_CONTACT and exactly one of FFE_NO_LIMIT (smooth dynamics alone) or FFE_WALK_JOINT_LIMITS (joint limits on: up to 48 limit
    * rows per env and substep), plus any of the force switches FFE_NO_FLUID / _DAMPER / _SPRING / _GRAVITY / _ACTUATION; every other
@@ -190,6 +198,8 @@ typedef struct {
    *   FFE_NO_CONTACT | FFE_WALK_JOINT_LIMITS                                          + joint limits
    *   FFE_NO_CONTACT | FFE_WALK_JOINT_LIMITS | FFE_WALK_FLOOR                         + the floor plane (bare physics)
    *   FFE_NO_CONTACT | FFE_WALK_JOINT_LIMITS | FFE_WALK_FLOOR | FFE_WALK_SELF         + the fly's own contacts (bare physics)
+   *   FFE_NO_CONTACT | FFE_WALK_JOINT_LIMITS | FFE_WALK_FLOOR | FFE_WALK_SELF | FFE_WALK_FLOOR_CONVEX
+   *                                                                                   + the floor against ellipsoids and cylinders (bare physics)
    *   FFE_NO_CONTACT | FFE_WALK_JOINT_LIMITS | FFE_WALK_EPISODES                      walk_imitation, floor off
    *   FFE_NO_CONTACT | FFE_WALK_JOINT_LIMITS | FFE_WALK_EPISODES | FFE_WALK_FLOOR     walk_imitation on the floor plane
    *   FFE_NO_CONTACT | FFE_WALK_JOINT_LIMITS | FFE_WALK_EPISODES | FFE_WALK_FLOOR | FFE_WALK_SELF | FFE_WALK_SELF_EPISODES
@@ -232,6 +242,12 @@ typedef struct {
  *   ffe_get_task_state  int 5 = all contacts kept in the last substep, floor and fly-fly (a contact inside its margin but outside
  *                       margin - gap is kept only where an adhesion actuator counts it), int 3 = the fly-fly contacts among them,
  *                       real 0 = the sum of the floor contacts' normal forces as before, real 1 = the smallest distance over both kinds
+ * A handle created with FFE_WALK_FLOOR_CONVEX reports what a FFE_WALK_SELF handle reports, every column keeping its meaning: int 5 counts
+ * all contacts kept (floor contacts of both kinds and fly-fly), int 3 the fly-fly ones, real 0 sums the normal forces of the floor
+ * contacts of both kinds, real 1 is the smallest distance over all three kinds, bit value 1 = more contacts than slots (the 16 deepest
+ * floor contacts of both kinds keep the first slots).  The plane-ellipsoid / plane-cylinder contacts among int 5 are reported in real 2:
+ * that column is zero on every other bare-physics handle (on an environment with FFE_WALK_SELF it is the fly-fly count, and this bit is
+ * refused there), whereas every int is taken.
  * A handle created with FFE_WALK_EPISODES is an environment (everything above still works on it): ffe_reset, ffe_reset_envs, ffe_step,
  * ffe_force_next_episode (the clip; the phase array is ignored), ffe_time_steps and ffe_time_kernel work as on a walk_on_ball handle,
  * and ffe_spec reports obs_dim 741 with the offsets of the row: accelerometer 3 | actuator_activation 59 | appendages_pos 21 |
