@@ -30,7 +30,7 @@ FFE_WALK_FLOOR = 2048  # ffe_create_walk_physics only: the floor plane against t
 #                        with FFE_WALK_EPISODES the walk_imitation environment on the floor)
 FFE_WALK_SELF = 4096  # ffe_create_walk_physics only: the fly's own contacts on the floor handle, bare physics or environment (provisional opt-in)
 FFE_WALK_SELF_EPISODES = 8192  # ffe_create_walk_physics only: next to FFE_WALK_SELF under the environment (the three bits alone stay refused)
-FFE_WALK_FLOOR_CONVEX = 32768  # ffe_create_walk_physics only: the floor against the fly's ellipsoids and cylinders, bare physics with FFE_WALK_FLOOR | FFE_WALK_SELF
+FFE_WALK_FLOOR_CONVEX = 32768  # ffe_create_walk_physics only: the floor against the fly's ellipsoids and cylinders, with FFE_WALK_FLOOR | FFE_WALK_SELF (bare physics or environment)
 
 
 # `env.validity()`: four int32 [B] views of one [B, 4] device buffer (include/flybody_env.h, ffe_get_validity)
@@ -415,6 +415,13 @@ class BatchedWalkEnv(BatchedFlyEnv):
     (int 3 is needs_reset on an env), real 1 is taken over both kinds, and step_bits bit value 8 says that a convex candidate pair was
     left out because a pair list of the substep was full.  The plane against ellipsoids and cylinders stays off.
 
+    `floor_convex=True` (keyword-only; it needs `floor_contacts=True` and `self_contacts=True`) adds
+    FFE_WALK_FLOOR_CONVEX: the floor plane against the fly's 16 ellipsoids and 6 cylinders as in
+    `BatchedWalkPhysics(floor_contacts=True, self_contacts=True, floor_convex=True)`, floor cone blocks like the others, so that a
+    fallen fly rests on its thorax, head, wings, coxae and abdomen.  This is the reference's whole contact set.  int 5 then counts
+    all three kinds of contact, reals[:, 3] the plane-ellipsoid / plane-cylinder ones among them (zero on every other env), and
+    bit 1 of step_bits says that more than 16 contacts were found and the deepest floor contacts were kept.
+
     `refs`: a `tasks.walking.WalkRefSet`; `view`: the `WalkModelView` that names the tracked joints and sites (None: the default
     one).  `get_state` / `set_state` / `get_act` / `set_act` / `physics_step` are `BatchedWalkPhysics`'s."""
 
@@ -423,11 +430,15 @@ class BatchedWalkEnv(BatchedFlyEnv):
     def __init__(self, refs, view=None, *, batch_size: int, device: int = 0, seed: int = 0, env_id_base: int = 0, future_steps: int = 64,
                  time_limit: float = 10.0, terminal_com_dist: float = 0.3, control_timestep: float = 2e-3, pad_first_obs: bool = False,
                  physics_flags: int = 0, canonical_actions: bool = False, clip_actions: bool = False, double_buffer: bool = False,
-                 inference_mode: bool = False, blob_path: str = WALK_BLOB, floor_contacts: bool = False, self_contacts: bool = False):
+                 inference_mode: bool = False, blob_path: str = WALK_BLOB, floor_contacts: bool = False, self_contacts: bool = False,
+                 floor_convex: bool = False):
         import json
 
         if self_contacts and not floor_contacts:
             raise ValueError("BatchedWalkEnv: self_contacts=True needs floor_contacts=True (the fly's own contacts are built on the floor env)")
+        if floor_convex and not (floor_contacts and self_contacts):
+            raise ValueError("BatchedWalkEnv: floor_convex=True needs floor_contacts=True and self_contacts=True (the floor against "
+                             "ellipsoids and cylinders is built on the env with the fly's own contacts)")
 
         from .model.blob import read_blob
         from .tasks.walk_tracker import make_task
@@ -449,13 +460,16 @@ class BatchedWalkEnv(BatchedFlyEnv):
         if self.floor_contacts:
             force_switches |= int(physics_flags) & (128 | 256)  # FFE_NO_NOSLIP / FFE_NO_ADHESION
             if int(physics_flags) & ~(force_switches | FFE_NO_CONTACT | FFE_WALK_JOINT_LIMITS | FFE_WALK_EPISODES | FFE_WALK_FLOOR
-                                      | (FFE_WALK_SELF | FFE_WALK_SELF_EPISODES if self_contacts else 0)):
+                                      | (FFE_WALK_SELF | FFE_WALK_SELF_EPISODES if self_contacts else 0)
+                                      | (FFE_WALK_FLOOR_CONVEX if floor_convex else 0)):
                 raise ValueError("BatchedWalkEnv(floor_contacts=True): physics_flags takes the force switches, FFE_NO_NOSLIP and FFE_NO_ADHESION only")
         elif int(physics_flags) & ~(force_switches | FFE_NO_CONTACT | FFE_WALK_JOINT_LIMITS | FFE_WALK_EPISODES):
             raise ValueError("BatchedWalkEnv: physics_flags takes the force switches only (floor contacts are not built; joint limits are on)")
         self.self_contacts = bool(self_contacts)
+        self.floor_convex = bool(floor_convex)
         self.physics_flags = (force_switches | FFE_NO_CONTACT | FFE_WALK_JOINT_LIMITS | FFE_WALK_EPISODES | (FFE_WALK_FLOOR if self.floor_contacts else 0)
-                              | (FFE_WALK_SELF | FFE_WALK_SELF_EPISODES if self.self_contacts else 0))
+                              | (FFE_WALK_SELF | FFE_WALK_SELF_EPISODES if self.self_contacts else 0)
+                              | (FFE_WALK_FLOOR_CONVEX if self.floor_convex else 0))
         task = _capi.WalkPhysicsTask(physics_flags=self.physics_flags, task=C.pointer(wtask), seed=int(seed), env_id_base=int(env_id_base),
                                      time_limit_steps=time_limit_control_steps(time_limit, h_phys, nsub), pad_first_obs=int(pad_first_obs),
                                      canonical_actions=int(canonical_actions), clip_actions=int(clip_actions))

@@ -8,7 +8,7 @@ import subprocess
 _HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(_HERE, "csrc")
 LIB = os.path.join(CSRC, "libflybody_env.so")
-SOURCES = ["capi.hip", "fly_env.hip", "ball_env.hip", "walk_env.hip", "walk_floor_env.hip", "walk_self_env.hip", "walk_imit_self_env.hip", "walk_full_env.hip", "nstep.hip", "replay.hip", "episode_log.hip", "walk_task.hip"]
+SOURCES = ["capi.hip", "fly_env.hip", "ball_env.hip", "walk_env.hip", "walk_floor_env.hip", "walk_self_env.hip", "walk_imit_self_env.hip", "walk_full_env.hip", "walk_imit_full_env.hip", "nstep.hip", "replay.hip", "episode_log.hip", "walk_task.hip"]
 # Loop-invariant code motion hoists per-lane LDS addresses and literal constants out of the substep loop of the two step
 # kernels and then spills them.  flight: no machine LICM -> 119 VGPRs, 0 B scratch (was 56 B; +0.5 % env-steps/s);
 # walk_on_ball: sinking invariants back into the loop where that avoids a spill -> 176 B scratch (was 548 B; +1.2 %).  Measured
@@ -21,6 +21,7 @@ PER_SOURCE_FLAGS = {
     "walk_self_env.hip": ["-mllvm", "-sink-insts-to-avoid-spills=1"],  # likewise
     "walk_imit_self_env.hip": ["-mllvm", "-sink-insts-to-avoid-spills=1"],  # likewise
     "walk_full_env.hip": ["-mllvm", "-sink-insts-to-avoid-spills=1"],  # likewise
+    "walk_imit_full_env.hip": ["-mllvm", "-sink-insts-to-avoid-spills=1"],  # likewise
 }
 HEADERS = ["handle.hpp", "env_backend.hpp", "fly_env.hpp", "dev_model.hpp", "ball_model.hpp", "ball_env.hpp", "leg_dyn.hpp", "leg_stage1.inc", "row_newton.hpp", "walk_model.hpp", "walk_env.hpp", "walk_imu.hpp", "walk_floor.hpp", "walk_floor_convex.hpp", "walk_self.hpp", "walk_self_model.hpp", "walk_substeps.hpp", "self_pairs.hpp", "walk_sense.hpp", "walk_self_sense.hpp", "dev_math.hpp", "convex.hpp", "launch_order.hpp", "nstep_ring.hpp", "walk_task.hpp", os.path.join("..", "..", "include", "flybody_env.h")]
 

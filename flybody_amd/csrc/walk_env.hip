@@ -210,7 +210,8 @@ __global__ void episode_init_kernel(EpState *eps, int batch) {
 //   reals     on the floor the sum of the contacts' normal forces and the smallest contact distance (0 without a contact; with
 //             FFE_WALK_SELF over both kinds), and on an episode handle, where int 3 is taken, the fly-fly count in real 2; on a bare-physics
 //             handle with FFE_WALK_FLOOR_CONVEX real 2 is the plane-ellipsoid / plane-cylinder contacts among int 5 (bits 8 .. 15 of the
-//             record's nself, zero from every other kernel); zeros otherwise
+//             record's nself, zero from every other kernel), on an episode handle with that bit, where real 2 is taken, they are real 3;
+//             zeros otherwise
 //   validity  {overflow bits of the last launch (1 more contacts than slots, 2 more rows than RMAX, 4 more rows in a block than columns,
 //             8 a convex candidate pair left out because a pair list of the substep was full), episode_flagged_steps, episode_bits,
 //             episode_steps}, the last three zero without an episode record
@@ -225,7 +226,7 @@ __global__ void walk_report_kernel(const EpState *eps, const WState *states, con
     o[4] = S.nlim; o[5] = rec ? rec[i].ncon : 0; o[6] = S.iters; o[7] = S.step_bits;
     double *r = reals + (size_t)i * 8;
     for (int k = 0; k < 8; k++) r[k] = 0.0;
-    if (rec) { r[0] = (double)rec[i].fsum; r[1] = (double)rec[i].mind; r[2] = eps ? (double)rec[i].nself : (double)(rec[i].nself >> 8); }
+    if (rec) { r[0] = (double)rec[i].fsum; r[1] = (double)rec[i].mind; r[2] = eps ? (double)(rec[i].nself & 0xff) : (double)(rec[i].nself >> 8); if (eps) r[3] = (double)(rec[i].nself >> 8); }
   }
   if (info) *reinterpret_cast<int4 *>(info + (size_t)i * 4) = eps ? make_int4(S.step_bits, eps[i].ep_flagged, eps[i].ep_bits, eps[i].step) : make_int4(S.step_bits, 0, 0, 0);
 }
@@ -274,7 +275,7 @@ __global__ void walk_act_kernel(WState *states, double *act, int batch, int set)
 // Bare physics (reset, step, forced episodes and the timers are refused) or, created with FFE_WALK_EPISODES, the walk_imitation
 // environment with the floor off or, with FFE_WALK_FLOOR too, on the floor (step 4c: the third of the five
 // launches is then `imitation_floor_step` of walk_floor_env.hip; step 4d, with FFE_WALK_SELF on top: `imitation_self_step` of
-// walk_imit_self_env.hip).
+// walk_imit_self_env.hip; step 4e, with FFE_WALK_FLOOR_CONVEX on top: `imitation_full_step` of walk_imit_full_env.hip).
 struct WalkEnv final : ffe::EnvBackend {
   int flags = 0;
   bool limits = false;    // FFE_WALK_JOINT_LIMITS: walk_limits_kernel steps this handle
@@ -287,7 +288,8 @@ struct WalkEnv final : ffe::EnvBackend {
   ffe::DeviceBuffers mem{"ffe_create_walk_physics"};  // everything below lives here
   WalkModel *model_dev = nullptr;
   WalkModelFull *full_dev = nullptr;  // FFE_WALK_FLOOR_CONVEX only: the model with the second floor table behind it (model_dev = &full_dev->m);
-                                      // floor_full_step of walk_full_env.hip steps this handle
+                                      // floor_full_step of walk_full_env.hip steps this handle (with `episodes`: imitation_full_step
+                                      // of walk_imit_full_env.hip)
   WState *states = nullptr;
   // episode handle only
   ffe_walktask_handle task = nullptr;  // the float32 task layer of this env
@@ -352,7 +354,8 @@ struct WalkEnv final : ffe::EnvBackend {
     task_ok(ffe_walktask_reference_pose(task, clip, zero, batch, const_cast<double *>(args.pose), nullptr, stream), "walk_imitation");
     const ImitArgs &a = args;
     tm.start(s);
-    if (self) launch_imitation_self_step(model_dev, flags, states, args_dev, act, obs, batch, s);
+    if (full_dev) launch_imitation_full_step(full_dev, flags, states, args_dev, act, obs, batch, s);
+    else if (self) launch_imitation_self_step(model_dev, flags, states, args_dev, act, obs, batch, s);
     else if (floor) launch_imitation_floor_step(model_dev, flags, states, args_dev, act, obs, batch, s);
     else hipLaunchKernelGGL(imitation_step_kernel, dim3(batch), dim3(64), 0, s, model_dev, flags, states, args_dev, act, obs, batch);
     HIP_OK(hipGetLastError());
@@ -493,12 +496,21 @@ std::unique_ptr<ffe::EnvBackend> walk_create(const void *blob, size_t blob_size,
   const bool episodes = (physics_flags & BF_WALK_EPISODES) != 0, floor = (physics_flags & BF_WALK_FLOOR) != 0;
   const bool self = (physics_flags & BF_WALK_SELF) != 0, self_env = (physics_flags & BF_WALK_SELF_EPISODES) != 0;
   const bool convex = (physics_flags & BF_WALK_FLOOR_CONVEX) != 0;
-  if (convex) {  // the floor against ellipsoids and cylinders: one accepted set, bare physics
-    if ((physics_flags & ~kSwitches) != (BF_NO_CONTACT | BF_WALK_JOINT_LIMITS | BF_WALK_FLOOR | BF_WALK_SELF | BF_WALK_FLOOR_CONVEX))
-      throw std::runtime_error("ffe_create_walk_physics: FFE_WALK_FLOOR_CONVEX (the floor plane against the fly's ellipsoids and cylinders, bare "
-                               "physics) is accepted only as FFE_NO_CONTACT | FFE_WALK_JOINT_LIMITS | FFE_WALK_FLOOR | FFE_WALK_SELF | "
-                               "FFE_WALK_FLOOR_CONVEX plus the force switches, FFE_NO_NOSLIP and FFE_NO_ADHESION: it excludes FFE_NO_LIMIT, and "
-                               "under the environment (FFE_WALK_EPISODES) it is not built yet");
+  if (convex) {  // the floor against ellipsoids and cylinders: two accepted sets, bare physics and the environment with the task
+    constexpr int kFull = BF_NO_CONTACT | BF_WALK_JOINT_LIMITS | BF_WALK_FLOOR | BF_WALK_SELF | BF_WALK_FLOOR_CONVEX;
+    if (episodes != self_env)
+      throw std::runtime_error("ffe_create_walk_physics: FFE_WALK_FLOOR_CONVEX under the environment is asked for with FFE_WALK_EPISODES | "
+                               "FFE_WALK_SELF_EPISODES together (on FFE_NO_CONTACT | FFE_WALK_JOINT_LIMITS | FFE_WALK_FLOOR | FFE_WALK_SELF | "
+                               "FFE_WALK_FLOOR_CONVEX and with the task): one of the two bits without the other is refused");
+    if ((physics_flags & ~(kSwitches | BF_WALK_EPISODES | BF_WALK_SELF_EPISODES)) != kFull)
+      throw std::runtime_error("ffe_create_walk_physics: FFE_WALK_FLOOR_CONVEX (the floor plane against the fly's ellipsoids and cylinders) is "
+                               "accepted only as FFE_NO_CONTACT | FFE_WALK_JOINT_LIMITS | FFE_WALK_FLOOR | FFE_WALK_SELF | FFE_WALK_FLOOR_CONVEX "
+                               "(bare physics) or as that set | FFE_WALK_EPISODES | FFE_WALK_SELF_EPISODES with the task (the walk_imitation "
+                               "environment), each plus the force switches, FFE_NO_NOSLIP and FFE_NO_ADHESION: it excludes FFE_NO_LIMIT");
+    if (episodes && !task.task)
+      throw std::runtime_error("ffe_create_walk_physics: FFE_WALK_FLOOR_CONVEX with FFE_WALK_EPISODES | FFE_WALK_SELF_EPISODES needs the task (a "
+                               "null ffe_walk_task pointer): a handle without one does not carry the episode protocol; without the two bits "
+                               "FFE_WALK_FLOOR_CONVEX makes the bare-physics handle");
   } else if (self || self_env) {  // the fly's own contacts: refusals of their own, which the table does not express
     if (episodes && !floor)
       throw std::runtime_error("ffe_create_walk_physics: FFE_WALK_SELF (the fly's own contacts) with FFE_WALK_EPISODES needs FFE_WALK_FLOOR: the "
@@ -536,6 +548,8 @@ std::unique_ptr<ffe::EnvBackend> walk_create(const void *blob, size_t blob_size,
                                "be condim 3 with the solimp of its other contacts");
   }
   e->host.m.b.nsub = 10;  // the reference's control step of 2 ms over the model's 0.2 ms (bare physics: ffe_spec's figure alone)
+  // one place decides the allocation, from `convex` alone and before any kernel is chosen: every launch of a kernel with the second
+  // floor pass goes through `full_dev`, whose type a plain WalkModel allocation does not have
   if (convex) {
     e->full_dev = e->mem.zeroed<WalkModelFull>(1);
     e->model_dev = &e->full_dev->m;

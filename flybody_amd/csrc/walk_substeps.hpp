@@ -2,8 +2,8 @@
 // tiles, the wave's context, stage 1 / stage 2 with the limit block and the one contact block (`contact_forces`: the floor's rows and, on
 // a self tile, the fly's own) and sensor pass (`contact_sense`), the substep loop and the state export.
 // walk_env.hip (the four kernels of bare physics and of the floor-off environment), walk_floor_env.hip (the environment on the floor),
-// walk_self_env.hip (bare physics with the fly's own contacts) and walk_imit_self_env.hip (the environment on the floor with the fly's
-// own contacts) include it; what the code does is described at the head of walk_env.hip and where each part starts.
+// walk_self_env.hip (bare physics with the fly's own contacts), walk_imit_self_env.hip (the environment on the floor with the fly's
+// own contacts), walk_full_env.hip and walk_imit_full_env.hip (the same two with the plane against ellipsoids and cylinders) include it; what the code does is described at the head of walk_env.hip and where each part starts.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -251,6 +251,23 @@ static_assert(sizeof(WTileSX) <= 20480, "the tile must leave room for 8 waves pe
 static_assert(NL * 14 <= kSensePark && kSensePark + 3 * 64 <= RMAX * (RMAX + 1) / 2,
               "the parked right-hand side lies behind the sensor pass's link exchange, inside G");
 static_assert(NPG <= 3 * 64, "the slot radii of the collision pass and the parked right-hand side share the same floats of G, one after the other");
+// Tile of the episode kernel with every contact of the reference's task (walk_imit_full_env.hip `imitation_full_step`; DESIGN.md section
+// 12 step 4e): `WTileSX` as it is, with the second floor pass switched on.  `floor_convex_collide` runs between `floor_collide` and the
+// fly-fly passes and needs no scratch of its own, so the overlays of step 4d hold with it in between:
+//   it reads      the link poses `lp` (head of G) that `floor_collide` published and T.sv0; both stay as they are until `prim_pairs`
+//                 fills X4 and the radii behind `lp`, which happens after its closing barrier;
+//   it writes     contact slots alone (c_pos .. c_amask of slots < NC), none of which lies in a union;
+//   afterwards    a plane-ellipsoid / plane-cylinder slot is a floor slot: `kPackedNormal` never packs a normal into it (slots k < nc keep
+//                 c_vel and c_mu for the cone block), and `contact_sense` finds its link by comparing c_link with the lane, so 255 (a
+//                 thorax geom) matches no lane and c_geom >= NPG is never used as an index there.
+struct alignas(16) WTileSXC : WTileSX {
+  static constexpr bool kConvexFloor = true;
+};
+static_assert(sizeof(WTileSXC) == sizeof(WTileSX), "the second floor pass adds nothing to the tile");
+static_assert(sizeof(WTileSXC) <= 20480, "the tile must leave room for 8 waves per CU");
+static_assert(WTileSXC::kSense && WTileSXC::kSelf && WTileSXC::kPackedNormal && WTileSXC::kFloor, "a sense tile and a self tile with the packed normal");
+static_assert(NL <= 64 && NL < 255, "c_link = 255 names no lane: the sensor pass skips a root geom's contact by comparison alone");
+static_assert(NPG + NFC <= 255 && NC <= 64 && NFC <= 64, "as for WTileXC: c_geom names both tables' rows in a byte; a lane per row and per slot");
 // the normal (from geom1's link to geom2's) of fly-fly slot k
 template <class TileX>
 __device__ __forceinline__ void self_nrm(const TileX &T, const int k, float (&n)[3]) {
@@ -1778,5 +1795,9 @@ void launch_imitation_self_step(const WalkModel *model, int flags, WState *state
 void launch_floor_self_step(const WalkModel *model, int flags, WState *states, const float *ctrl, FloorRec *rec, int batch, int nphys, hipStream_t stream);
 // ... and with the second floor pass, the plane against ellipsoids and cylinders (walk_full_env.hip): launches `floor_full_step`
 void launch_floor_full_step(const WalkModelFull *model, int flags, WState *states, const float *ctrl, FloorRec *rec, int batch, int nphys, hipStream_t stream);
+// One control step of walk_imitation with every contact of the reference's task (walk_imit_full_env.hip): launches `imitation_full_step`
+// on `stream`.  It takes the model with the second floor table behind it, so a plain WalkModel allocation cannot reach it.
+void launch_imitation_full_step(const WalkModelFull *model, int flags, WState *states, const ImitArgs *args, const float *action, float *obs, int batch,
+                                hipStream_t stream);
 
 }  // namespace ffw

@@ -92,9 +92,11 @@ enum {
    * rostrum, haustellum halves, four wing blades, six coxae) and 6 cylinders (the abdomen segments) - on the bare-physics handle that
    * carries the floor and the fly's own contacts (csrc/walk_full_env.hip).  With it every geom of fruitfly.xml that the reference's
    * Walking task collides with its floor (tasks/base.py:331-364) does so here.  Accepted only as FFE_NO_CONTACT | FFE_WALK_JOINT_LIMITS |
-   * FFE_WALK_FLOOR | FFE_WALK_SELF | FFE_WALK_FLOOR_CONVEX plus force switches, FFE_NO_NOSLIP and FFE_NO_ADHESION, bare physics; every
-   * other set with it, any set with FFE_WALK_EPISODES included, is refused with a text naming the bit (the environment is the next
-   * step).  (16384 is not used: a set with it is a pinned refusal.)  Provisional as the five above. */
+   * FFE_WALK_FLOOR | FFE_WALK_SELF | FFE_WALK_FLOOR_CONVEX plus force switches, FFE_NO_NOSLIP and FFE_NO_ADHESION, bare physics, or as
+   * that set | FFE_WALK_EPISODES | FFE_WALK_SELF_EPISODES with the task: the walk_imitation environment with every contact of the
+   * reference's task (csrc/walk_imit_full_env.hip).  Every other set with it - with only one of FFE_WALK_EPISODES and
+   * FFE_WALK_SELF_EPISODES, with both and a null `task`, without FFE_WALK_SELF - is refused with a text naming the bit.  (16384 is not
+   * used: a set with it is a pinned refusal.)  Provisional as the five above. */
   FFE_WALK_FLOOR_CONVEX = 32768
 };
 
@@ -180,7 +182,8 @@ int ffe_create_walk_on_ball(const void *model_blob, size_t blob_size, const ffe_
  * fly's 48 sphere / capsule geoms (elliptic cones, noslip, adhesion) to the bare-physics handle or, together with FFE_WALK_EPISODES,
  * to the environment, whose force and touch columns are then live; FFE_WALK_SELF adds the fly's own contacts to the bare-physics floor
  * handle or, together with FFE_WALK_EPISODES | FFE_WALK_FLOOR | FFE_WALK_SELF_EPISODES, to the environment on the floor.  FFE_WALK_FLOOR_CONVEX adds
- * the floor against the fly's ellipsoids and cylinders to the bare-physics handle with both; under the environment it is not built yet. */
+ * the floor against the fly's ellipsoids and cylinders to the bare-physics handle with both or, with FFE_WALK_EPISODES |
+ * FFE_WALK_SELF_EPISODES and the task on top, to the environment with both. */
 typedef struct {
   /* FFE_NO_CONTACT and exactly one of FFE_NO_LIMIT (smooth dynamics alone) or FFE_WALK_JOINT_LIMITS (joint limits on: up to 48 limit
    * rows per env and substep), plus any of the force switches FFE_NO_FLUID / _DAMPER / _SPRING / _GRAVITY / _ACTUATION; every other
@@ -193,7 +196,8 @@ typedef struct {
    * FFE_WALK_FLOOR | FFE_WALK_SELF plus the same switches, bare physics, or with FFE_WALK_EPISODES | FFE_WALK_SELF_EPISODES and the
    * task on top of exactly that; every other set with it - without FFE_WALK_FLOOR, with FFE_NO_LIMIT, with FFE_WALK_EPISODES and a null
    * `task` (a handle without the task does not carry the episode protocol), with only one of FFE_WALK_EPISODES and
-   * FFE_WALK_SELF_EPISODES - is refused with a text naming FFE_WALK_SELF.  The accepted sets:
+   * FFE_WALK_SELF_EPISODES - is refused with a text naming FFE_WALK_SELF.  FFE_WALK_FLOOR_CONVEX is accepted only on top of exactly
+   * those two sets with FFE_WALK_SELF (see the bit).  The accepted sets:
    *   FFE_NO_CONTACT | FFE_NO_LIMIT                                                   smooth dynamics
    *   FFE_NO_CONTACT | FFE_WALK_JOINT_LIMITS                                          + joint limits
    *   FFE_NO_CONTACT | FFE_WALK_JOINT_LIMITS | FFE_WALK_FLOOR                         + the floor plane (bare physics)
@@ -203,7 +207,9 @@ typedef struct {
    *   FFE_NO_CONTACT | FFE_WALK_JOINT_LIMITS | FFE_WALK_EPISODES                      walk_imitation, floor off
    *   FFE_NO_CONTACT | FFE_WALK_JOINT_LIMITS | FFE_WALK_EPISODES | FFE_WALK_FLOOR     walk_imitation on the floor plane
    *   FFE_NO_CONTACT | FFE_WALK_JOINT_LIMITS | FFE_WALK_EPISODES | FFE_WALK_FLOOR | FFE_WALK_SELF | FFE_WALK_SELF_EPISODES
-   *                                                                                   + the fly's own contacts */
+   *                                                                                   + the fly's own contacts
+   *   FFE_NO_CONTACT | FFE_WALK_JOINT_LIMITS | FFE_WALK_EPISODES | FFE_WALK_FLOOR | FFE_WALK_SELF | FFE_WALK_SELF_EPISODES |
+   *   FFE_WALK_FLOOR_CONVEX                                                           + the floor against ellipsoids and cylinders */
   int32_t physics_flags;
   /* read only when physics_flags has FFE_WALK_EPISODES (a caller without the bit may pass the one int above alone) */
   const ffe_walk_task *task;  /* clips, tracked joints / sites, reward and termination constants: a float32 task layer of the env's
@@ -246,8 +252,8 @@ typedef struct {
  * all contacts kept (floor contacts of both kinds and fly-fly), int 3 the fly-fly ones, real 0 sums the normal forces of the floor
  * contacts of both kinds, real 1 is the smallest distance over all three kinds, bit value 1 = more contacts than slots (the 16 deepest
  * floor contacts of both kinds keep the first slots).  The plane-ellipsoid / plane-cylinder contacts among int 5 are reported in real 2:
- * that column is zero on every other bare-physics handle (on an environment with FFE_WALK_SELF it is the fly-fly count, and this bit is
- * refused there), whereas every int is taken.
+ * that column is zero on every other bare-physics handle, whereas every int is taken.  On an environment real 2 is the fly-fly count, so
+ * an environment created with FFE_WALK_FLOOR_CONVEX reports the plane-ellipsoid / plane-cylinder contacts in real 3 (see below).
  * A handle created with FFE_WALK_EPISODES is an environment (everything above still works on it): ffe_reset, ffe_reset_envs, ffe_step,
  * ffe_force_next_episode (the clip; the phase array is ignored), ffe_time_steps and ffe_time_kernel work as on a walk_on_ball handle,
  * and ffe_spec reports obs_dim 741 with the offsets of the row: accelerometer 3 | actuator_activation 59 | appendages_pos 21 |
@@ -269,6 +275,13 @@ typedef struct {
  *                       and fly-fly, real 2 = the fly-fly contacts among them (int 3 is needs_reset here; real 2 is zero on every other
  *                       handle), real 1 = the smallest distance over both kinds, and bit value 8 (a convex candidate pair left out)
  *                       joins bits 1 / 2 / 4 in step_bits, sticky per episode in episode_bits
+ *                       with FFE_WALK_FLOOR_CONVEX on top of that every column keeps its meaning again: int 5 = all contacts kept,
+ *                       floor contacts of both kinds and fly-fly, real 2 = the fly-fly ones, real 0 = the sum of the normal forces of
+ *                       the floor contacts of both kinds, real 1 = the smallest distance over all three kinds, and real 3 = the
+ *                       plane-ellipsoid / plane-cylinder contacts among int 5 (real 3 is zero on every other handle); bits 1 / 2 / 4 /
+ *                       8 unchanged.  Such a contact is a floor cone block: its force enters the force sensor of a tarsus only if its
+ *                       geom's link lies below that tarsus (none of the shipped model's does) and touch only on a claw's link; the
+ *                       accelerometer and the inertial half of the force sensors see it through qacc
  * A failure of the env's task layer is the env handle's error text. */
 int ffe_create_walk_physics(const void *model_blob, size_t blob_size, const ffe_walk_physics_task *task, int batch, int device,
                             ffe_handle *out);

@@ -4,8 +4,10 @@ floor off (csrc/walk_env.hip `imitation_step_kernel` and the four launches aroun
 there is no target.  `--self` compares the environment on the floor with the fly's own contacts (csrc/walk_imit_self_env.hip
 `imitation_self_step`; `walk_imitation(floor_contacts="primitives", self_contacts=True)`) with the one without them in one session:
 the two envs and the two action cases alternate window by window, and the summary holds the medians, their ratio and the flagged steps.
+`--full` does the same for the environment with the plane against ellipsoids and cylinders too (csrc/walk_imit_full_env.hip
+`imitation_full_step`; `floor_convex=True`) against the one with `self_contacts=True` alone.
 
-    python tools/bench_walk_env.py [--floor | --self] [--batch 4096] [--windows 5] [--iters 50] [--log profiles/bench_walk_env.log] [--no-trace]
+    python tools/bench_walk_env.py [--floor | --self | --full] [--batch 4096] [--windows 5] [--iters 50] [--log profiles/bench_walk_env.log] [--no-trace]
 
 Timing: `ffe_time_steps` (device events around `iters` step launches on the env's stream) per window; the cases - zero actions and
 uniform +-0.5 actions - alternate window by window so that clock and neighbours act on both alike; window 0 of each case warms up and
@@ -32,19 +34,22 @@ def launches(floor):
             "episode_close_kernel")
 
 
-def make_env(batch, floor=False, self_contacts=False):
+def make_env(batch, floor=False, self_contacts=False, floor_convex=False):
     from flybody_amd import fly_envs
 
-    return fly_envs.walk_imitation(floor_contacts="primitives" if floor else False, self_contacts=self_contacts, batch_size=batch)
+    return fly_envs.walk_imitation(floor_contacts="primitives" if floor else False, self_contacts=self_contacts, floor_convex=floor_convex,
+                                   batch_size=batch)
 
 
-def compare_self(args, say):
-    """`--self`: windows alternate between the env with the fly's own contacts and the floor env without them, case by case."""
+def compare_self(args, say, new="floor_self", old="floor"):
+    """`--self`: windows alternate between the env with the fly's own contacts and the floor env without them, case by case; `--full`:
+    between the env with the plane against ellipsoids and cylinders too (`floor_full`) and the one with the fly's own contacts."""
     import numpy as np
     import torch
 
     B = args.batch
-    envs = {"floor_self": make_env(B, True, True), "floor": make_env(B, True, False)}
+    kinds = {"floor": (True, False, False), "floor_self": (True, True, False), "floor_full": (True, True, True)}
+    envs = {new: make_env(B, *kinds[new]), old: make_env(B, *kinds[old])}
     cases = action_cases(torch, B)
     ms = {(e, c): [] for e in envs for c in cases}
     flagged = {e: 0 for e in envs}
@@ -63,10 +68,10 @@ def compare_self(args, say):
                     flagged[name] += nflag
     out = {"batch": B, "iters_per_window": args.iters, "windows": args.windows, "flagged_steps": flagged}
     for case in cases:
-        a, b = statistics.median(ms[("floor_self", case)]), statistics.median(ms[("floor", case)])
-        out[case] = {"floor_self_median_ms_per_step": a, "floor_median_ms_per_step": b, "ratio": a / b,
-                     "floor_self_step_kernel_alone_ms": envs["floor_self"].time_kernel(cases[case], args.iters),
-                     "floor_step_kernel_alone_ms": envs["floor"].time_kernel(cases[case], args.iters)}
+        a, b = statistics.median(ms[(new, case)]), statistics.median(ms[(old, case)])
+        out[case] = {new + "_median_ms_per_step": a, old + "_median_ms_per_step": b, "ratio": a / b,
+                     new + "_step_kernel_alone_ms": envs[new].time_kernel(cases[case], args.iters),
+                     old + "_step_kernel_alone_ms": envs[old].time_kernel(cases[case], args.iters)}
     say(out)
     for env in envs.values():
         env.close()
@@ -123,6 +128,8 @@ def main():
     ap.add_argument("--floor", action="store_true", help="the environment on the floor plane instead of the one with the floor off")
     ap.add_argument("--self", dest="self_contacts", action="store_true",
                     help="compare the environment on the floor with the fly's own contacts with the one without them (no trace)")
+    ap.add_argument("--full", dest="full", action="store_true",
+                    help="compare the environment with the plane against ellipsoids and cylinders too with the one with the fly's own contacts (no trace)")
     ap.add_argument("--no-trace", action="store_true", help="skip the rocprofv3 run")
     ap.add_argument("--trace-child", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--log", default=None, help="append the printed lines to this file")
@@ -137,8 +144,11 @@ def main():
         print(line, flush=True)
         lines.append(line)
 
-    if args.self_contacts:
-        compare_self(args, say)
+    if args.self_contacts or args.full:
+        if args.full:
+            compare_self(args, say, new="floor_full", old="floor_self")
+        else:
+            compare_self(args, say)
         if args.log:
             os.makedirs(os.path.dirname(os.path.abspath(args.log)), exist_ok=True)
             with open(args.log, "a") as f:
